@@ -28,7 +28,15 @@ Total work is fixed as N grows -> "scaling": "strong".  The N > 1 line verifies 
 sweeps the FULL lag set on its own GPU (`map_vs_single_gpu`), a CPU sample of 128 lag-points is evaluated by the oracle
 (`parity_vs_cpu_sample`), and `n_ranks_seen` is the size of the communicator the collective ran on.
 
-Prints ONE JSON line on rank 0 (see the driver contract) with `roofline` and `cpu_baseline` objects.
+A plain run (`--gpus 1 --steps K --warmup W`) does only what the headline figure needs: set-up, W warm-up steps, the K
+timed steps and the line (`value`, `ms_per_step` = milliseconds of one timed step).  Everything else it can measure or
+check -- `sustained`, `one_sweep_in_flight`, the single-launch kernel times and `roofline`, `pcie_inclusive`,
+`all_finite_image`, `map_vs_single_gpu`, the CPU baseline and parity sample, `parity_vs_reference_run` -- runs only with
+`--full`; without it those fields are null.  `--dump-outputs DIR` writes the correlation map of the last timed step to
+DIR/corr.npy (float64); the scene and lags are seeded, so two builds can be compared output for output.
+
+Prints ONE JSON line on rank 0 (see the driver contract); with `--full` it carries `roofline` and `cpu_baseline`
+objects.
 """
 import argparse
 import json
@@ -82,6 +90,16 @@ def log(*a):
 _LINE_PRINTED = [False]
 _STDOUT_FD = [None]     # the real stdout once fd 1 has been pointed at stderr
 _RUN_INFO = {"n_gpus": None, "n_ranks_seen": 0, "steps": None, "warmup": None}
+
+
+def dump_outputs(directory, **arrays):
+    """--dump-outputs: what the timed path computed in its last step, one DIR/<name>.npy (float64) per array."""
+    import numpy as np
+    if not directory:
+        return
+    os.makedirs(directory, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def _mark(what, rank):
@@ -307,17 +325,25 @@ def main_threads(args):
         elapsed = time.perf_counter() - t0
         st = m.last_stats()
         corr = corr.reshape(lag1.size, lag2.size)
-        single = m.handle(0).sweep_carrington(hs, grid, SOLAR_R, lags, order=ORDER).reshape(corr.shape)
-        small_h = small if args.small_f64 else small.astype(np.float32)
-        large_h = large.astype(np.float32)
-        times = []
-        for _ in range(5):
-            t0 = time.perf_counter()
-            m.set_small(small_h)
-            m.prepare_reference_carrington(large_h, hl, grid, SOLAR_R, ORDER)
-            out_host = m.sweep_carrington(hs, grid, SOLAR_R, lags, order=ORDER)
-            times.append(time.perf_counter() - t0)
-        best = min(times[1:])
+        dump_outputs(args.dump_outputs, corr=corr)
+        vs_single = pcie = None
+        if args.full:
+            single = m.handle(0).sweep_carrington(hs, grid, SOLAR_R, lags, order=ORDER).reshape(corr.shape)
+            vs_single = {"max_abs_diff": float(np.nanmax(np.abs(single - corr))),
+                         "same_argmax": bool(np.nanargmax(single) == np.nanargmax(corr)), "tolerance": 1e-12}
+            small_h = small if args.small_f64 else small.astype(np.float32)
+            large_h = large.astype(np.float32)
+            times = []
+            for _ in range(5):
+                t0 = time.perf_counter()
+                m.set_small(small_h)
+                m.prepare_reference_carrington(large_h, hl, grid, SOLAR_R, ORDER)
+                out_host = m.sweep_carrington(hs, grid, SOLAR_R, lags, order=ORDER)
+                times.append(time.perf_counter() - t0)
+            best = min(times[1:])
+            pcie = {"value": L / best, "unit": "lag-points/s", "ms_per_step": 1e3 * best, "n_gpus": m.size,
+                    "identical_to_resident_map": bool(np.array_equal(out_host.reshape(corr.shape), corr,
+                                                                     equal_nan=True))}
         am = np.unravel_index(np.nanargmax(corr), corr.shape)
         out = {"metric": METRIC, "value": L * args.steps / elapsed, "unit": "lag-points/s", "n_gpus": m.size,
                "n_ranks_seen": m.size, "steps": args.steps, "warmup": args.warmup,
@@ -329,11 +355,7 @@ def main_threads(args):
                           "parallelism": f"one process, {m.size} device threads, lag-plane blocks + 1 all-gather "
                                          f"({st['collective']})"},
                "per_rank": [{"rank": k, "kernel_ms": ms} for k, ms in enumerate(st["per_device_sweep_kernel_ms"])],
-               "map_vs_single_gpu": {"max_abs_diff": float(np.nanmax(np.abs(single - corr))),
-                                     "same_argmax": bool(np.nanargmax(single) == np.nanargmax(corr)), "tolerance": 1e-12},
-               "pcie_inclusive": {"value": L / best, "unit": "lag-points/s", "ms_per_step": 1e3 * best, "n_gpus": m.size,
-                                  "identical_to_resident_map": bool(np.array_equal(out_host.reshape(corr.shape), corr,
-                                                                                   equal_nan=True))},
+               "map_vs_single_gpu": vs_single, "pcie_inclusive": pcie,
                "argmax_lag_arcsec": [float(lag1[am[0]]), float(lag2[am[1]])],
                "injected_shift_arcsec": [truth["lag_crval1"], truth["lag_crval2"]],
                "roofline": None, "cpu_baseline": None}
@@ -465,6 +487,7 @@ def main_config(args):
     h.synchronize()
     elapsed = time.perf_counter() - t0
     corr = np.asarray(corr).reshape(lags.shape)
+    dump_outputs(args.dump_outputs, corr=corr)
     n_launch = max(1, int(st["n_sweep_launches"]))
     k_ms = float(np.mean(kern))                    # all launches of one sweep
     act = int(st["n_active_points"])               # per launch
@@ -524,7 +547,7 @@ def main_config(args):
                       "step": "one synchronous sweep call, correlation map copied to the host"},
            "roofline": roof, "precompute_ms": float(np.mean(pre)), "argmax_index": [int(i) for i in am],
            "cpu_baseline": None}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import coreg_oracle as O
         from tests import helpers as H
         try:
@@ -606,6 +629,12 @@ def main():
     ap.add_argument("--shard", choices=["auto", "lags", "points"], default="auto",
                     help="N > 1: cut the lag plane in blocks (+ one all-gather) or the target grid in point shares "
                          "(+ one all-reduce of the six sums per lag); auto = points below 128 lag-points per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure: sustained rate, one "
+                         "sweep in flight, single-launch kernel times and roofline, PCIe-inclusive call, all-finite "
+                         "image, map against one GPU, CPU baseline and parity samples, the reference run's entries")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the correlation map of the last timed step to DIR/corr.npy (float64)")
     args = ap.parse_args()
     args.steps_given, args.warmup_given = args.steps is not None, args.warmup is not None
     if args.config != "headline":
@@ -819,17 +848,20 @@ def main():
     if rank == fail_rank and fail_at == "hang":  # a rank that stays out of the next collective for ever
         time.sleep(1e6)
     elapsed = timed(args.steps, n_streams)
+    corr = result[0].cpu().numpy().reshape(lag1.size, lag2.size)  # the map of the last timed step
+    if rank == 0:
+        dump_outputs(args.dump_outputs, corr=corr)
     # the same steps for >= 2 s, so that the GPU is visibly busy to an outside observer and a clock that falls under
     # sustained load shows (the K-step region above lasts a second at most)
     sustained = None
-    if args.sustained_seconds > 0 and not dry:
+    if args.full and args.sustained_seconds > 0 and not dry:
         n_sus = max(args.steps, int(1.1 * args.sustained_seconds / max(elapsed / args.steps, 1e-6)) + 1)
         t_sus = timed(n_sus, n_streams)
         sustained = {"steps": n_sus, "seconds": t_sus, "ms_per_step": 1e3 * t_sus / n_sus, "value": L * n_sus / t_sus,
                      "unit": "lag-points/s", "sweeps_in_flight": n_streams}
     # the same steps with ONE sweep in flight (stream 0 only), for the record
     one_in_flight = None
-    if n_streams > 1 and not dry:
+    if args.full and n_streams > 1 and not dry:
         n1 = max(1, min(args.steps, 100))
         one_in_flight = timed(n1, 1) / n1
 
@@ -839,7 +871,9 @@ def main():
     # region, on identical steps issued ONE at a time
     stats = {"sweep_kernel_ms": 0.0, "precompute_ms": 0.0, "n_active_points": 0, "small_is_f32": 1, "used_lds": 1}
     kernel_ms, pre_ms = [], []
-    if not dry:
+    if not dry and not args.full and have_lags:
+        stats = h.last_stats()  # launch sizes and storage of the timed steps (their kernel times overlap: not used)
+    elif not dry and args.full:
         for _ in range(min(16, args.steps)):
             step_no[0] = 0  # handle / stream 0
             step(1)
@@ -849,9 +883,7 @@ def main():
                 pre_ms.append(stats["precompute_ms"])
             else:
                 torch.cuda.synchronize()
-    if not kernel_ms:
-        kernel_ms, pre_ms = [0.0], [0.0]
-    k_ms = float(np.mean(kernel_ms))
+    k_ms = float(np.mean(kernel_ms)) if kernel_ms else None
     per_rank = [{"rank": rank, "kernel_ms": k_ms, "lags": (hi1 - lo1) * (hi2 - lo2) if have_lags else 0,
                  "active_points": int(stats["n_active_points"])}]
     if use_dist:
@@ -859,7 +891,6 @@ def main():
         gathered_stats = [None] * world
         dist.all_gather_object(gathered_stats, per_rank[0])
         per_rank = gathered_stats
-    corr = result[0].cpu().numpy().reshape(lag1.size, lag2.size)
 
     # ---- BASELINE.md section 2 at every N: ONE call that is handed host images.  Every rank uploads its share of both
     # images (the float32 pixels a BITPIX=-32 FITS file holds: 16 + 36 MiB in all; image to align: with RCCL 1/N per rank +
@@ -868,7 +899,7 @@ def main():
     # the all-gather assembles the map and every rank copies it to the host.  Barrier on both sides, max over ranks,
     # best of 4 after one warm-up.
     pcie = None
-    if not args.no_pcie and not dry:
+    if args.full and not args.no_pcie and not dry:
         small_h = small_m if args.small_f64 else small_m.astype(np.float32)
         large_h = large.astype(np.float32)
         times = []
@@ -922,9 +953,9 @@ def main():
     # interior visits then run without the mask -- kernels.hpp point_lag, CLEAN).  One sweep in flight, handle 0.
     all_finite = None
     visits = None
-    if world == 1 and not dry and have_lags and not by_points:
+    if args.full and world == 1 and not dry and have_lags and not by_points:
         visits = h.last_visit_counts()
-    if world == 1 and not dry and have_lags and not by_points and not args.no_all_finite:
+    if args.full and world == 1 and not dry and have_lags and not by_points and not args.no_all_finite:
         filled = np.where(np.isfinite(small_m), small_m, np.float64(np.nanmedian(small_m)))
         if not args.small_f64:
             filled = filled.astype(np.float32).astype(np.float64)
@@ -948,7 +979,7 @@ def main():
 
     # ---- N > 1: the gathered map against ONE GPU sweeping everything (rank 0, after the timed region)
     vs_single = None
-    if world > 1 and not dry and rank == 0:
+    if args.full and world > 1 and not dry and rank == 0:
         single = h.sweep_carrington(hs, grid, SOLAR_R, _lib.LagSet(*lags), order=ORDER).reshape(corr.shape) \
             if not by_points else None
         if by_points:  # the handles are in point-shard mode: a fresh context for the unsharded sweep
@@ -964,50 +995,54 @@ def main():
 
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
-        G = GRID_SHAPE[0] * GRID_SHAPE[1]
-        S = 2048 * 2048
-        b_lag = G * 8 + S * 8  # reference grid value + small-image pixel, fp64, touched once per lag
-        lags_per_launch = (hi1 - lo1) * (hi2 - lo2)
-        act = int(stats["n_active_points"])
-        k_s = max(k_ms, 1e-9) * 1e-3
-        flops = act * lags_per_launch * FLOP_PER_POINT_LAG
-        achieved_tf = flops / k_s / 1e12
-        pmc, pmc_path = pmc_summary()
-        roof = {
-            # the binding resources are float64 VALU issue and the LDS gather, co-limited
-            "bound": "valu_fp64+lds", "achieved": achieved_tf, "peak": FP64_VALU_PEAK_TF, "unit": "TFLOP/s",
-            "frac": achieved_tf / FP64_VALU_PEAK_TF,
-            "kernel": "k_sweep<TRANSLATE,2,%s>" % ("f32" if stats["small_is_f32"] else "f64"), "kernel_ms": k_ms, "lags_per_launch": lags_per_launch,
-            "active_points": act, "tile_visits": visits, "flop_per_point_lag": FLOP_PER_POINT_LAG,
-            "f64_instr_per_point_lag": F64_INSTR_PER_POINT_LAG,
-            # the workload-independent figure: the throughput above scales with the share of the grid inside the small
-            # FOV (631 710 of 4 194 304 points on the README grid); this does not
-            "ps_per_point_lag": k_ms * 1e9 / max(1, act * lags_per_launch),
-            "traffic": None, "hbm_model": {
-                "algorithmic_bytes_per_lag": b_lag, "algorithmic_bytes_per_launch": b_lag * lags_per_launch,
-                "achieved_gbs": b_lag * lags_per_launch / k_s / 1e9, "peak_gbs": HBM_PEAK_GBS,
-                "hbm_model_frac": b_lag * lags_per_launch / k_s / 1e9 / HBM_PEAK_GBS,
-                "note": "SURVEY 8d one-lag-per-pass byte model; the kernel shares every staged byte between 256 lags "
-                        "and culls grid points outside the small FOV, so this fraction exceeds 1 and HBM is not the "
-                        "bound (see traffic)"},
-            "note": "achieved = counted float64 flop of the interior gather path x active points x lags / kernel_ms "
-                    "(HIP events around single, non-overlapped launches right after the timed region)"}
-        if pmc and world == 1:
-            if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
-                # KiB per dispatch; FETCH_SIZE doubled: gfx950 counts 128-B read requests as 64 B (MI355X_MICROARCH.md)
-                roof["traffic"] = (2.0 * pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024.0
-                roof["traffic_unit"] = "HBM bytes per launch"
-            if "SQ_INSTS_VALU" in pmc:
-                roof["valu_issue_frac"] = pmc["SQ_INSTS_VALU"] / k_s / VALU_ISSUE_PEAK
-            if "SQ_LDS_IDX_ACTIVE" in pmc:
-                roof["lds_busy_frac"] = pmc["SQ_LDS_IDX_ACTIVE"] / k_s / LDS_CYCLES_PEAK
-                if "SQ_LDS_BANK_CONFLICT" in pmc:
-                    roof["lds_conflict_cycle_frac"] = pmc["SQ_LDS_BANK_CONFLICT"] / pmc["SQ_LDS_IDX_ACTIVE"]
-            roof["pmc_source"] = f"{pmc_path} (rocprofv3 --pmc means per launch of this command, committed)"
-        prof_ms, prof_path = kernel_profile_ms()
-        if prof_ms is not None:
-            roof["kernel_profile_ms"] = prof_ms
-            roof["kernel_profile_source"] = f"{prof_path} (rocprofv3 --kernel-trace --stats of this command, committed)"
+        roof = None  # --full: kernel times from single launches after the timed region
+        if args.full and k_ms is not None:
+            G = GRID_SHAPE[0] * GRID_SHAPE[1]
+            S = 2048 * 2048
+            b_lag = G * 8 + S * 8  # reference grid value + small-image pixel, fp64, touched once per lag
+            lags_per_launch = (hi1 - lo1) * (hi2 - lo2)
+            act = int(stats["n_active_points"])
+            k_s = max(k_ms, 1e-9) * 1e-3
+            flops = act * lags_per_launch * FLOP_PER_POINT_LAG
+            achieved_tf = flops / k_s / 1e12
+            pmc, pmc_path = pmc_summary()
+            roof = {
+                # the binding resources are float64 VALU issue and the LDS gather, co-limited
+                "bound": "valu_fp64+lds", "achieved": achieved_tf, "peak": FP64_VALU_PEAK_TF, "unit": "TFLOP/s",
+                "frac": achieved_tf / FP64_VALU_PEAK_TF,
+                "kernel": "k_sweep<TRANSLATE,2,%s>" % ("f32" if stats["small_is_f32"] else "f64"), "kernel_ms": k_ms,
+                "lags_per_launch": lags_per_launch,
+                "active_points": act, "tile_visits": visits, "flop_per_point_lag": FLOP_PER_POINT_LAG,
+                "f64_instr_per_point_lag": F64_INSTR_PER_POINT_LAG,
+                # the workload-independent figure: the throughput above scales with the share of the grid inside the
+                # small FOV (631 710 of 4 194 304 points on the README grid); this does not
+                "ps_per_point_lag": k_ms * 1e9 / max(1, act * lags_per_launch),
+                "traffic": None, "hbm_model": {
+                    "algorithmic_bytes_per_lag": b_lag, "algorithmic_bytes_per_launch": b_lag * lags_per_launch,
+                    "achieved_gbs": b_lag * lags_per_launch / k_s / 1e9, "peak_gbs": HBM_PEAK_GBS,
+                    "hbm_model_frac": b_lag * lags_per_launch / k_s / 1e9 / HBM_PEAK_GBS,
+                    "note": "SURVEY 8d one-lag-per-pass byte model; the kernel shares every staged byte between 256 "
+                            "lags and culls grid points outside the small FOV, so this fraction exceeds 1 and HBM is "
+                            "not the bound (see traffic)"},
+                "note": "achieved = counted float64 flop of the interior gather path x active points x lags / "
+                        "kernel_ms (HIP events around single, non-overlapped launches right after the timed region)"}
+            if pmc and world == 1:
+                if "FETCH_SIZE" in pmc and "WRITE_SIZE" in pmc:
+                    # KiB per dispatch; FETCH_SIZE doubled: gfx950 counts 128-B read requests as 64 B
+                    roof["traffic"] = (2.0 * pmc["FETCH_SIZE"] + pmc["WRITE_SIZE"]) * 1024.0
+                    roof["traffic_unit"] = "HBM bytes per launch"
+                if "SQ_INSTS_VALU" in pmc:
+                    roof["valu_issue_frac"] = pmc["SQ_INSTS_VALU"] / k_s / VALU_ISSUE_PEAK
+                if "SQ_LDS_IDX_ACTIVE" in pmc:
+                    roof["lds_busy_frac"] = pmc["SQ_LDS_IDX_ACTIVE"] / k_s / LDS_CYCLES_PEAK
+                    if "SQ_LDS_BANK_CONFLICT" in pmc:
+                        roof["lds_conflict_cycle_frac"] = pmc["SQ_LDS_BANK_CONFLICT"] / pmc["SQ_LDS_IDX_ACTIVE"]
+                roof["pmc_source"] = f"{pmc_path} (rocprofv3 --pmc means per launch of this command, committed)"
+            prof_ms, prof_path = kernel_profile_ms()
+            if prof_ms is not None:
+                roof["kernel_profile_ms"] = prof_ms
+                roof["kernel_profile_source"] = (f"{prof_path} (rocprofv3 --kernel-trace --stats of this command, "
+                                                 "committed)")
         am = np.unravel_index(np.nanargmax(corr), corr.shape)
         out = {
             "metric": METRIC,
@@ -1034,7 +1069,7 @@ def main():
             "sustained": sustained,
             "roofline": roof,
             "per_rank": per_rank,
-            "precompute_ms": float(np.mean(pre_ms)),
+            "precompute_ms": float(np.mean(pre_ms)) if pre_ms else None,
             "pcie_inclusive": pcie,
             "all_finite_image": all_finite,
             "map_vs_single_gpu": vs_single,
@@ -1050,7 +1085,7 @@ def main():
             with mp.get_context("fork").Pool(2) as pool:
                 out["dry_run_pool_ok"] = pool.map(abs, [-1, -2]) == [1, 2]
             time.sleep(0.3)
-        if not args.no_cpu_baseline and world > 1 and not dry:
+        if args.full and not args.no_cpu_baseline and world > 1 and not dry:
             # N > 1: no CPU timing (that leg belongs to the N = 1 line), but the assembled map is still checked against
             # the oracle on a seeded sample of 128 lag-points
             log("[bench] CPU parity sample: 128 lag-points ...")
@@ -1065,7 +1100,7 @@ def main():
                                            "argmax_on_sample_equal": bool(np.nanargmax(corr.ravel()[subset]) ==
                                                                           np.nanargmax(corr_cpu.ravel()[subset]))}
             out["cpu_baseline"] = None
-        elif not args.no_cpu_baseline and world == 1 and not dry:  # the CPU leg is timed at N = 1 only
+        elif args.full and not args.no_cpu_baseline and world == 1 and not dry:  # the CPU leg is timed at N = 1 only
             # the GPU box gives one GPU's job a 16-core share whatever os.cpu_count() says
             try:
                 avail = len(os.sched_getaffinity(0))
@@ -1083,7 +1118,7 @@ def main():
         else:
             out["cpu_baseline"] = None
         if not dry:
-            out["parity_vs_reference_run"] = reference_run_points(np, small, large, corr)
+            out["parity_vs_reference_run"] = reference_run_points(np, small, large, corr) if args.full else None
         print_line_once(json.dumps(out))
     for hk in handles:
         hk.close()

@@ -361,15 +361,18 @@ def _run_bench(extra_env, *argv, timeout=600):
     return json.loads(lines[0])
 
 
-def test_bench_self_launches_its_ranks_gloo_world2():
+def test_bench_self_launches_its_ranks_gloo_world2(tmp_path):
     """`python bench.py --gpus 2` with no torchrun environment starts its two ranks itself (children, before any GPU
     call), runs the process group + the one all-gather + the block permutation, and rank 0 prints ONE JSON line.  Dry
-    run: no GPU on this box, each rank fills its lag block with the raveled lag indices instead of sweeping."""
+    run: no GPU on this box, each rank fills its lag block with the raveled lag indices instead of sweeping.
+    `--dump-outputs` writes the assembled map of the last timed step."""
     out = _run_bench({"COREG_BENCH_BACKEND": "gloo", "COREG_BENCH_DRY": "1"}, "--gpus", "2", "--steps", "3", "--warmup",
-                     "1")
+                     "1", "--dump-outputs", str(tmp_path / "out"))
     assert out["n_gpus"] == 2 and out["n_ranks_seen"] == 2 and out["steps"] == 3 and out["warmup"] == 1
     assert out["dry_run"] is True and out["value"] is None
     assert out["dry_run_map_ok"] is True  # gathered blocks + permutation == C-order raveled lag map
+    dumped = np.load(tmp_path / "out" / "corr.npy")
+    assert dumped.dtype == np.float64 and np.array_equal(dumped, np.arange(3600, dtype=np.float64).reshape(60, 60))
     assert out["dry_run_pool_ok"] is True and "error" not in out  # a forked pool's SIGTERM is not this rank's
     assert [r["rank"] for r in out["per_rank"]] == [0, 1] and sum(r["lags"] for r in out["per_rank"]) == 3600
     assert out["scaling"] == "strong" and out["config"]["resident"] is True

@@ -125,12 +125,29 @@ def test_alignment_spice_l2_dropin():
     H.assert_corr_close(resc.corr, wantc, 1e-10, "AlignmentSpice.align_using_carrington")
 
 
+def test_bench_plain_run_times_the_headline_and_dumps_its_map(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W`: exactly K timed steps and nothing beyond the headline figure
+    (the `--full` fields are null); `--dump-outputs` writes the map of the last timed step, whose argmax is the line's."""
+    from tests.test_api_cpu import _run_bench
+    out = _run_bench({}, "--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(tmp_path), timeout=600)
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["n_gpus"] == 1 and "error" not in out
+    assert out["value"] > 0 and out["ms_per_step"] > 0 and out["unit"] == "lag-points/s" and out["dtype"] == "f64"
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 3600) < 1e-6 * 3600
+    for k in ("sustained", "one_sweep_in_flight", "roofline", "pcie_inclusive", "all_finite_image", "cpu_baseline",
+              "parity_vs_reference_run"):
+        assert out[k] is None, k
+    corr = np.load(tmp_path / "corr.npy")
+    assert corr.dtype == np.float64 and corr.shape == (60, 60)
+    am = np.unravel_index(np.nanargmax(corr), corr.shape)
+    assert [float(np.arange(-30, 30)[i]) for i in am] == out["argmax_lag_arcsec"] == out["injected_shift_arcsec"][:2]
+
+
 def test_bench_two_ranks_on_one_gpu_gloo():
     """bench.py --gpus 2 started as a plain command on the one-GPU box (ranks share the device, all-gather over gloo):
     real sweeps on both ranks, the assembled map has the injected shift as its argmax, per-rank kernel times present."""
     from tests.test_api_cpu import _run_bench
     out = _run_bench({"COREG_BENCH_BACKEND": "gloo", "COREG_CPU_CORES": "8"}, "--gpus", "2", "--steps", "4",
-                     "--warmup", "2", timeout=900)
+                     "--warmup", "2", "--full", timeout=900)
     assert out["n_gpus"] == 2 and out["n_ranks_seen"] == 2 and out["value"] > 0
     assert out["argmax_lag_arcsec"] == out["injected_shift_arcsec"][:2] == [17.0, -9.0]
     assert len(out["per_rank"]) == 2 and all(r["kernel_ms"] > 0 and r["lags"] == 1800 for r in out["per_rank"])
@@ -152,7 +169,7 @@ def test_bench_two_ranks_point_sharded_gloo():
     the grid's points, one all-reduce of the six sums per lag."""
     from tests.test_api_cpu import _run_bench
     out = _run_bench({"COREG_BENCH_BACKEND": "gloo"}, "--gpus", "2", "--steps", "4", "--warmup", "2",
-                     "--no-cpu-baseline", "--shard", "points", timeout=900)
+                     "--no-cpu-baseline", "--shard", "points", "--full", timeout=900)
     assert out["n_gpus"] == 2 and out["n_ranks_seen"] == 2 and out["value"] > 0
     assert "all-reduce" in out["config"]["parallelism"]
     assert out["argmax_lag_arcsec"] == out["injected_shift_arcsec"][:2] == [17.0, -9.0]
@@ -288,7 +305,7 @@ def test_bench_config_lines_carry_the_variant_s_roofline(name):
     that config checked against the map."""
     from tests.test_api_cpu import _run_bench
     out = _run_bench({"COREG_CPU_CORES": "8"}, "--config", name, "--steps", "2", "--warmup", "1", "--cpu-sample", "8",
-                     timeout=600)
+                     "--full", timeout=600)
     r = out["roofline"]
     assert out["config"]["name"] == name and out["n_gpus"] == 1 and out["value"] > 0 and out["unit"] == "lag-points/s"
     assert r["flop_per_point_lag"] == {"order1": 23.0, "cfg4": 62.0}[name] and 0.0 < r["frac"] < 1.0

@@ -280,7 +280,7 @@ def test_bench_launch_threads_two_virtual_devices():
     on the one GPU of the box): the headline map with the injected shift as argmax, equal to device 0 sweeping alone."""
     from tests.test_api_cpu import _run_bench
     out = _run_bench({"COREG_VIRTUAL_DEVICES": "2"}, "--gpus", "2", "--launch", "threads", "--steps", "3", "--warmup",
-                     "1", timeout=900)
+                     "1", "--full", timeout=900)
     assert out["n_gpus"] == 2 and out["n_ranks_seen"] == 2 and out["value"] > 0
     assert out["config"]["launch"] == "threads" and out["config"]["lag_sharding"] == "blocks"
     assert out["argmax_lag_arcsec"] == out["injected_shift_arcsec"][:2] == [17.0, -9.0]
