@@ -227,6 +227,14 @@ SYMBOLS = [
     ("coreg_fit_gaussian2d", C.c_int,
      [C.c_int32, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32, _P,
       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    # iterative-context sweep (AlignementSpiceIterativeContextRaster)
+    ("coreg_set_context_frames", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int, _WP, C.POINTER(_P)]),
+    ("coreg_context_frame_from_small", C.c_int, [_P, C.c_int32]),
+    ("coreg_sweep_context", C.c_int,
+     [_P, _WP, _WP, C.POINTER(C.c_int32), C.POINTER(Lags), C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int,
+      C.c_double, C.c_int64, C.c_int64, _P, C.c_int]),
+    ("coreg_context_lag_headers", C.c_int,
+     [_WP, _WP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _WP, _WP, _WP]),
     # all GPUs of the node from one process
     ("coreg_device_count", C.c_int, []),
     ("coreg_physical_device_count", C.c_int, []),
@@ -618,6 +626,64 @@ class CoregHandle:
                                                         _P(ptr), on_dev))
         return out
 
+    # -- iterative-context sweep (include/coreg_hip.h: coreg_set_context_frames, coreg_sweep_context)
+    def set_context_frames(self, frames, headers, dtype=None):
+        """The imager frames of an iterative-context sweep, resident on the device.  Each frame: a float32 / float64
+        array, or a RawImage / CompressedImage (utils/fits_io.py), decoded on the GPU by the upload path of `set_small`.
+        `dtype`: of the device stack (default: float32 when every frame is stored as float32)."""
+        frames = list(frames)
+        if len(frames) != len(headers) or not frames:
+            raise ValueError("one header per frame, at least one frame")
+
+        def stored(f):
+            if _is_tiled(f):
+                return np.float32 if int(f.zbitpix) == -32 else np.float64
+            if _is_raw(f):
+                return np.float32 if int(f.bitpix) == -32 else np.float64
+            return np.float32 if np.asarray(f).dtype == np.float32 else np.float64
+        if dtype is None:
+            dtype = np.float32 if all(stored(f) == np.float32 for f in frames) else np.float64
+        dtype = np.dtype(dtype)
+        shape = tuple(frames[0].shape)
+        if any(tuple(f.shape) != shape for f in frames) or len(shape) != 2:
+            raise ValueError("all frames must be 2-D images of one shape")
+        hdrs = (Wcs2d * len(frames))(*[wcs_from_header(hh) for hh in headers])
+        host = []
+        ptrs = (_P * len(frames))()
+        for k, f in enumerate(frames):
+            if _is_tiled(f) or _is_raw(f):
+                continue
+            a = np.ascontiguousarray(f, dtype=dtype)
+            host.append(a)
+            ptrs[k] = a.ctypes.data
+        self._chk(self._lib.coreg_set_context_frames(self._h, len(frames), shape[0], shape[1],
+                                                     COREG_F32 if dtype == np.float32 else COREG_F64, hdrs, ptrs))
+        for k, f in enumerate(frames):
+            if _is_tiled(f) or _is_raw(f):
+                self.set_small(f)
+                self._chk(self._lib.coreg_context_frame_from_small(self._h, k))
+        self._context_frames = (len(frames), shape, dtype)
+
+    def sweep_context(self, hdr_target, hdr_small, col_frame, lags: LagSet, order=2, method=METHOD_CORRELATION,
+                      cdelt_semantics=CDELT_INTENDED, vmin=None, vmax=None, lag_begin=0, lag_end=None, out_dev_ptr=None):
+        """One iterative-context sweep over lag indices [lag_begin, lag_end) (C order of `lags`); the SPICE image is the
+        one `set_small` uploaded last (after `set_context_frames`)."""
+        lag_end = lags.size if lag_end is None else int(lag_end)
+        wt, w = wcs_from_header(hdr_target), wcs_from_header(hdr_small)
+        cf = np.ascontiguousarray(col_frame, dtype=np.int32)
+        if cf.size != w.naxis1:
+            raise ValueError("col_frame needs one entry per raster column")
+        if out_dev_ptr is None:
+            out = np.empty(lag_end - lag_begin, dtype=np.float64)
+            ptr, on_dev = out.ctypes.data, 0
+        else:
+            out, ptr, on_dev = None, int(out_dev_ptr), 1
+        self._chk(self._lib.coreg_sweep_context(
+            self._h, C.byref(wt), C.byref(w), cf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(lags.c), int(order),
+            int(method), int(cdelt_semantics), int(vmin is not None), float(0.0 if vmin is None else vmin),
+            int(vmax is not None), float(0.0 if vmax is None else vmax), int(lag_begin), lag_end, _P(ptr), on_dev))
+        return out
+
     # -- multi-GPU point sharding (see include/coreg_hip.h, coreg_finalize_sums)
     def set_point_shard(self, rank, world):
         self.set_option("shard_world", int(world))
@@ -1005,6 +1071,29 @@ def car_tile_margin(hdr_target, hdr_shifted, tile_w, tile_abs_lat_rad):
     if rc != COREG_OK:
         raise CoregError(rc, "coreg_car_tile_margin: bad arguments")
     return m.value
+
+
+def context_lag_headers(hdr_target, hdr_small, d_crval1, d_crval2, d_cdelt1, d_cdelt2, d_crota,
+                        cdelt_semantics=CDELT_INTENDED):
+    """The three headers of one lag-point of the iterative-context sweep (host, no GPU): (ctx, grid, shifted) as Wcs2d,
+    or None when the lag-point has no header to evaluate.  See include/coreg_hip.h: coreg_context_lag_headers."""
+    lib = load_library()
+    wt, w = wcs_from_header(hdr_target), wcs_from_header(hdr_small)
+    out = [Wcs2d(), Wcs2d(), Wcs2d()]
+    rc = lib.coreg_context_lag_headers(C.byref(wt), C.byref(w), float(d_crval1), float(d_crval2), float(d_cdelt1),
+                                       float(d_cdelt2), float(d_crota), int(cdelt_semantics), *[C.byref(o) for o in out])
+    if rc < 0:
+        raise CoregError(rc, "coreg_context_lag_headers: bad arguments")
+    return None if rc else tuple(out)
+
+
+def wcs_to_dict(w: Wcs2d) -> dict:
+    """Header cards of a Wcs2d (TAN; angles in the struct's own unit)."""
+    unit = {v: k for k, v in _UNIT_TO_DEG.items()}.get(w.unit_to_deg, "deg")
+    return {"NAXIS1": w.naxis1, "NAXIS2": w.naxis2, "CRPIX1": w.crpix1, "CRPIX2": w.crpix2, "CRVAL1": w.crval1,
+            "CRVAL2": w.crval2, "CDELT1": w.cdelt1, "CDELT2": w.cdelt2, "PC1_1": w.pc1_1, "PC1_2": w.pc1_2,
+            "PC2_1": w.pc2_1, "PC2_2": w.pc2_2, "CROTA": w.crota, "CUNIT1": unit, "CUNIT2": unit,
+            "CTYPE1": "HPLN-TAN", "CTYPE2": "HPLT-TAN", "LONPOLE": w.lonpole}
 
 
 def wcslib_pixel_to_pixel(hdr_from, hdr_to, px, py):

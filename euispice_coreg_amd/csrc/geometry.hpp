@@ -9,7 +9,9 @@
 #pragma once
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -953,6 +955,68 @@ inline void carr_tables(const coreg_carr_grid& g, double crln_obs, CarrTables& t
         t.cos_lat[j] = g.lat_cos ? g.lat_cos[j] : (float)std::cos((double)latr);
         t.sin_lat[j] = g.lat_sin ? g.lat_sin[j] : (float)std::sin((double)latr);
     }
+}
+
+// ---- iterative-context sweep (AlignementSpiceIterativeContextRaster, alignment_spice.py:357-469) ------------------
+// A float as a FITS card holds it: astropy 4.3.1's Card formatting (f"{v:.16G}", at most 20 characters, the mantissa cut
+// before an exponent) -- what WCS(header) parses back for a keyword _shift_header wrote.
+inline double card_float(double v) {
+    if (!std::isfinite(v)) return v;
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.16G", v);
+    std::string s(buf);
+    if (s.find('.') == std::string::npos && s.find('E') == std::string::npos) s += ".0";
+    if (s.size() > 20) {
+        const size_t e = s.find('E');
+        s = e == std::string::npos ? s.substr(0, 20) : s.substr(0, 20 - (s.size() - e)) + s.substr(e);
+    }
+    return std::strtod(s.c_str(), nullptr);
+}
+// wcslib's WCSHDO_P14 (astropy's WCS.to_header): 14 significant digits
+inline double p14(double v) {
+    if (!std::isfinite(v)) return v;
+    char buf[64];
+    std::snprintf(buf, sizeof buf, "%.14G", v);
+    return std::strtod(buf, nullptr);
+}
+// The three headers of one lag-point of the iterative-context sweep.
+//   target4: celestial part of the UNFLATTENED SPICE header, in degrees (CRVAL / CDELT / PCi_j / CRPIX of the two
+//            helioprojective axes, not rounded); its CRVAL / CROTA are replaced by the flattened header's (the *_ref
+//            values of alignment.py:799-814, which _shift_header adds the lag to, :404 / :412 / :445)
+//   small:   the flattened 2-D SPICE header (hdr_small: degrees, 14 digits)
+// ctx = _shift_header(target4): the grid on which map_builder.py:247-288 takes the sky positions of the slit pixels;
+// grid = ctx as to_header() prints it (map_builder.py:288 -> the composed header's pointing keys, :143-146);
+// shifted = _shift_header(small) as WCS(header) reads the cards back (alignment_spice.py:361-366).
+// Returns shift_header's status (non-zero: the lag-point stays NaN).
+inline int context_lag_headers(const coreg_wcs2d& target4, const coreg_wcs2d& small, double d_crval1, double d_crval2,
+                               double d_cdelt1, double d_cdelt2, double d_crota, int cdelt_semantics, coreg_wcs2d* ctx,
+                               coreg_wcs2d* grid, coreg_wcs2d* shifted) {
+    coreg_wcs2d t = target4;
+    t.crval1 = small.crval1;
+    t.crval2 = small.crval2;
+    t.crota = small.crota;
+    int rc = shift_header(t, d_crval1, d_crval2, d_cdelt1, d_cdelt2, d_crota, cdelt_semantics, ctx);
+    if (rc) return rc;
+    rc = shift_header(small, d_crval1, d_crval2, d_cdelt1, d_cdelt2, d_crota, cdelt_semantics, shifted);
+    if (rc) return rc;
+    *grid = *ctx;
+    double* g[] = {&grid->crpix1, &grid->crpix2, &grid->crval1, &grid->crval2, &grid->cdelt1, &grid->cdelt2,
+                   &grid->pc1_1, &grid->pc1_2, &grid->pc2_1, &grid->pc2_2};
+    for (double* v : g) *v = p14(*v);
+    grid->naxis1 = small.naxis1;
+    grid->naxis2 = small.naxis2;
+    // the cards _shift_header rewrote (CRVAL always; CDELT / PCi_j when it rebuilt them) go through a card's text
+    shifted->crval1 = card_float(shifted->crval1);
+    shifted->crval2 = card_float(shifted->crval2);
+    if (shifted->cdelt1 != small.cdelt1) shifted->cdelt1 = card_float(shifted->cdelt1);
+    if (shifted->cdelt2 != small.cdelt2) shifted->cdelt2 = card_float(shifted->cdelt2);
+    if (d_cdelt1 != 0.0 || d_cdelt2 != 0.0 || d_crota != 0.0) {
+        shifted->pc1_1 = card_float(shifted->pc1_1);
+        shifted->pc1_2 = card_float(shifted->pc1_2);
+        shifted->pc2_1 = card_float(shifted->pc2_1);
+        shifted->pc2_2 = card_float(shifted->pc2_2);
+    }
+    return 0;
 }
 
 }  // namespace coreg

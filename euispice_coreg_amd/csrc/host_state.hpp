@@ -112,11 +112,15 @@ struct FixLaunch {
     bool empty() const { return border.empty() && parity.empty() && !have_tap; }
 };
 
+struct ContextState;  // frames and work space of the iterative-context sweep (host_context.hpp)
+
 struct coreg_handle {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::string err;
+
+    ContextState* ctx = nullptr;  // created by coreg_set_context_frames
 
     // small image
     DevBuf small;

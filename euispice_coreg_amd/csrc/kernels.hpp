@@ -26,3 +26,4 @@
 #include "kernels_sweep.hpp"     // Taps, gathers, point_lag, tile_points, k_sweep
 #include "kernels_fix.hpp"       // noise-decided samples: border / parity / tap scan + fix
 #include "kernels_finalize.hpp"  // k_finalize, k_refine_list, k_refine
+#include "kernels_context.hpp"   // iterative-context sweep (per-lag synthetic rasters)

@@ -12,6 +12,8 @@ Differences from the reference, all deliberate:
 """
 from __future__ import annotations
 
+import datetime as _dt
+
 import numpy as np
 
 from .. import _lib
@@ -209,3 +211,139 @@ class AlignmentSpice(Alignment):
         self.hdr_small = spice_header.celestial_header(hdr)
         self.hdr_small["NAXIS1"] = self.data_small.shape[-1]
         self.hdr_small["NAXIS2"] = self.data_small.shape[-2]
+
+
+class AlignementSpiceIterativeContextRaster(AlignmentSpice):
+    """Drop-in for euispice_coreg.hdrshift.AlignementSpiceIterativeContextRaster (alignment_spice.py:357-469): the
+    context image is composed anew for every candidate header -- each raster column an order-2 sample of the imager
+    frame nearest in time to that slit, at the SHIFTED SPICE pointing (SPICEComposedMapBuilder.process_from_header) --
+    and the SPICE image is resampled onto that grid and correlated with it (`_step`, :361-421).  The whole lag sweep is
+    one library call (include/coreg_hip.h: coreg_sweep_context); every imager file is read once per call and the frames
+    the raster uses stay resident on the GPU.
+
+    Differences from the reference, all deliberate:
+      * the reference cannot run as committed: its __init__ passes `use_tqdm`, `small_fov_value_min` /
+        `small_fov_value_max` to an AlignmentSpice.__init__ that takes none of them, and align_using_helioprojective
+        passes `index_amplitude=` to `_extract_spice_data_header(level, coeff)` (TypeError either way); its map builder
+        returns os.path.join(None, ...) from process_from_header (TypeError after the map is made); its `_step`
+        shifts the 4-D SPICE header, whose CUNIT is arcsec, with lags already converted to the flattened header's
+        degrees, and _shift_header raises "lag.unit and cUNIT are not the same"; and the serial branch of its sweep
+        driver never calls `_step` at all (alignment.py:765-797 calls `_step_no_shmm`).  Here every lag-point does what
+        `_step` says, with the 4-D header's celestial cards taken in degrees;
+      * `parallelism` is accepted and the sweep runs on one GPU (multi-GPU sharding of this sweep is not implemented);
+      * level-3 input raises NotImplementedError (the reference's `_prepare_spice_from_l3` never sets the unflattened
+        header its `_extract_imager_data_header` reads: AttributeError);
+      * `cdelt_semantics` as on `Alignment` (default "intended"; "reference" reproduces _shift_header's CDELT handling).
+    """
+
+    def __init__(self, large_fov_list_paths, small_fov_to_correct, threshold_time, lag_crval1, lag_crval2, lag_cdelt1,
+                 lag_cdelt2, lag_crota, small_fov_value_min=None, parallelism=False, small_fov_value_max=None,
+                 counts_cpu_max=40, large_fov_window=-1, small_fov_window=-1, use_tqdm=False, path_save_figure=None,
+                 cdelt_semantics="intended", device=None):
+        super().__init__(large_fov_known_pointing="No_specific_path", small_fov_to_correct=small_fov_to_correct,
+                         lag_crval1=lag_crval1, lag_crval2=lag_crval2, lag_cdelt1=lag_cdelt1, lag_cdelt2=lag_cdelt2,
+                         lag_crota=lag_crota, lag_solar_r=None, parallelism=parallelism, counts_cpu_max=counts_cpu_max,
+                         large_fov_window=large_fov_window, small_fov_window=small_fov_window,
+                         display_progress_bar=use_tqdm, path_save_figure=path_save_figure,
+                         cdelt_semantics=cdelt_semantics, device=device)
+        self.small_fov_value_min = small_fov_value_min
+        self.small_fov_value_max = small_fov_value_max
+        self.step_figure = False
+        self.large_fov_list_paths = list(large_fov_list_paths)
+        self.threshold_time = threshold_time
+        self.header_spice_unflattened = None
+        self.col_frame = None  # imager file (index into large_fov_list_paths) of every raster column, after a call
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _prepare_spice_from_l2(self, cube, hdr):
+        """alignment_spice.py:467-469: keep the 4-D header, then prepare as AlignmentSpice does."""
+        self.header_spice_unflattened = fits_io.Header(hdr).copy()
+        super()._prepare_spice_from_l2(cube, hdr)
+
+    def _frame_of_columns(self, hdr4, headers):
+        """map_builder.py:95-110: the imager frame closest in time to every raster column (the time axis of the 4-D
+        header, averaged along the slit), ValueError when none is within `threshold_time`.  The lags move only the
+        celestial cards, so the choice is the same for every lag-point."""
+        from ..synras.map_builder import _seconds
+        col_seconds, t_ref = spice_header.column_times(hdr4)
+        dates = [spice_header.parse_date(h["DATE-AVG"]) for h in headers]
+        threshold = _seconds(self.threshold_time)
+        out = np.empty(len(col_seconds), dtype=np.int64)
+        for ii, s in enumerate(col_seconds):
+            utc = t_ref + _dt.timedelta(seconds=float(s))
+            dt = np.array([abs((utc - d).total_seconds()) for d in dates], dtype=np.float64)
+            if dt.min() > threshold:
+                raise ValueError(f"dt={dt.min()} s: Could not find imager sufficiently close in time")
+            out[ii] = int(dt.argmin())
+        return out
+
+    @staticmethod
+    def _celestial_degrees(hdr4, hdr_small):
+        """The helioprojective part of the 4-D header in degrees, not rounded (what map_builder.py:253-280 evaluates
+        the slit positions with); CRVAL / CROTA come from the flattened header inside the library (the *_ref values)."""
+        lon, lat = spice_header._axes(hdr4)
+        s1 = hdrutil.unit_to_deg(str(hdr4.get("CUNIT%d" % lon, "deg")).strip() or "deg")
+        s2 = hdrutil.unit_to_deg(str(hdr4.get("CUNIT%d" % lat, "deg")).strip() or "deg")
+        t = {"NAXIS1": int(hdr_small["NAXIS1"]), "NAXIS2": int(hdr_small["NAXIS2"]),
+             "CRPIX1": float(hdr4.get("CRPIX%d" % lon, 0.0)), "CRPIX2": float(hdr4.get("CRPIX%d" % lat, 0.0)),
+             "CRVAL1": float(hdr4.get("CRVAL%d" % lon, 0.0)) * s1, "CRVAL2": float(hdr4.get("CRVAL%d" % lat, 0.0)) * s2,
+             "CDELT1": float(hdr4.get("CDELT%d" % lon, 1.0)) * s1, "CDELT2": float(hdr4.get("CDELT%d" % lat, 1.0)) * s2,
+             "CUNIT1": "deg", "CUNIT2": "deg", "CTYPE1": "HPLN-TAN", "CTYPE2": "HPLT-TAN",
+             "LONPOLE": float(hdr4.get("LONPOLE", 180.0)), "CROTA": float(hdr_small.get("CROTA", 0.0))}
+        for i, a in ((1, lon), (2, lat)):
+            for j, b in ((1, lon), (2, lat)):
+                t[f"PC{i}_{j}"] = float(hdr4.get(f"PC{a}_{b}", 1.0 if a == b else 0.0))
+        return t
+
+    def align_using_helioprojective(self, method="correlation", index_amplitude=None, extend_pixel_size=False):
+        """alignment_spice.py:437-465."""
+        self.lonlims = self.latlims = self.shape = self.reference_date = None
+        self.method = method
+        self.coordinate_frame = "final_helioprojective"
+        self.extend_pixel_size = extend_pixel_size
+        level = self._level()
+        if level == 3:
+            raise NotImplementedError("AlignementSpiceIterativeContextRaster: level-3 input (the reference's L3 path "
+                                      "never sets the unflattened header it composes the context from)")
+        # every imager file once: header and (memory-mapped / compressed) pixels
+        loaded = [(fits_io.load_for_upload if self.raw_fits_upload else fits_io.read_image)(p, self.large_fov_window)
+                  for p in self.large_fov_list_paths]
+        headers = [fits_io.Header(h) for _, h in loaded]
+        self.hdr_large = headers[0]  # (WAVELNTH for extend_pixel_size, _correct_solar_rotation)
+        self._extract_spice_data_header(level=level, coeff=index_amplitude)
+        hdr4 = self.header_spice_unflattened
+        self.col_frame = self._frame_of_columns(hdr4, headers)
+        used = sorted(set(int(i) for i in self.col_frame))
+        col_slot = np.searchsorted(np.asarray(used), self.col_frame).astype(np.int32)
+        frame_headers = []
+        for i in used:
+            hw = headers[i].copy()
+            hdrutil.check_and_create_pcij_matrix(hw, False, warn=False)
+            frame_headers.append(hw)
+        # the composed header: the imager header of the middle column, SPICE pointing on top (map_builder.py:133-153)
+        self.hdr_large = headers[int(self.col_frame[len(self.col_frame) // 2])]
+        self._set_initial_header_values(True)
+        if self.unit_lag != self.hdr_small["CUNIT1"]:
+            raise ValueError("lag.unit and cUNIT are not the same")
+        if self.method == "correlation":
+            m = _lib.METHOD_CORRELATION
+        elif self.method == "residus":
+            m = _lib.METHOD_RESIDUS
+        else:
+            raise NotImplementedError
+        device = -1 if self.device is None else self.device
+        h = _lib.shared_handle(device, self._handle_slot)
+        h.reference_tag = None  # (the frames and the SPICE image replace whatever the handle held)
+        frames = [fits_io.native_pixels(loaded[i][0]) if not isinstance(loaded[i][0], (fits_io.RawImage,
+                                                                                    fits_io.CompressedImage))
+                  else loaded[i][0] for i in used]
+        h.set_context_frames(frames, frame_headers)
+        h.set_small(np.asarray(self.data_small, dtype=np.float64))
+        lags = _lib.LagSet(self.lag_crval1, self.lag_crval2, self.lag_cdelt1, self.lag_cdelt2, self.lag_crota)
+        sem = _lib.CDELT_INTENDED if self.cdelt_semantics == "intended" else _lib.CDELT_REFERENCE
+        target = self._celestial_degrees(hdr4, self.hdr_small)
+        corr = h.sweep_context(target, self.hdr_small, col_slot, lags, order=self.order, method=m,
+                               cdelt_semantics=sem, vmin=self.small_fov_value_min, vmax=self.small_fov_value_max)
+        self.last_stats = h.last_stats()
+        results = np.asarray(corr).reshape(lags.shape + (1,))
+        return self._wrap(results, "AlignmentResults", restore_units=True)

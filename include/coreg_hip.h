@@ -466,6 +466,41 @@ int coreg_fit_gaussian2d(int32_t m, const double* x, const double* y, const doub
                          int32_t max_nfev, double* popt, int32_t* nfev, int32_t* status);
 
 
+/* Iterative-context sweep (AlignementSpiceIterativeContextRaster, hdrshift/alignment_spice.py:357-469): for every
+ * lag-point the context is composed anew on the SHIFTED SPICE grid -- each raster column an order-2 sample of the imager
+ * frame nearest in time to that slit (synras/map_builder.py:89-131) -- and the SPICE image is resampled onto that grid
+ * (order `order`, float32 destination, alignment.py:1018-1029); both samples of every (grid point, lag) are taken in
+ * one kernel (csrc/kernels_context.hpp) and finished by the Pearson / residus kernels of the other sweeps.
+ *   coreg_set_context_frames        the N imager frames [ny][nx] (all of one shape), resident as a device stack of
+ *                                   `dtype` (COREG_F32: samples float32-rounded, as interpol2d writes into a float32
+ *                                   array), and their headers.  pixels may be NULL, or hold NULL entries: such frames are
+ *                                   filled by coreg_context_frame_from_small
+ *   coreg_context_frame_from_small  frame k := the image the last coreg_set_small / _fits / _tiled call decoded (raw
+ *                                   big-endian FITS pixels and Rice-tiled images go through those decode paths)
+ *   coreg_sweep_context             hdr_target: the celestial part of the UNFLATTENED 4-D SPICE header in degrees (its
+ *                                   CRVAL / CROTA are taken from hdr_small, whose *_ref values the lags are added to);
+ *                                   hdr_small: the flattened 2-D header (alignment_spice.py:250-323), whose image is the
+ *                                   one set by coreg_set_small; col_frame[hdr_small.naxis1]: frame of every column;
+ *                                   thresholds (has_min / has_max) apply to the float32 SPICE samples; order even (0, 2,
+ *                                   4: at odd orders the tap set of every near-integer sample is noise-decided).  Same
+ *                                   lag slicing and output contract as coreg_sweep_helioprojective, except that a device
+ *                                   output is complete when the call returns.  Planned on the host per lag
+ *                                   (geometry.hpp: context_lag_headers); the border samples of the SPICE resample, whose
+ *                                   bounds rule hangs on wcslib's rounding, are decided by wcslib's own arithmetic.
+ *   coreg_context_lag_headers       host only: the three headers of one lag-point (ctx: the shifted grid the slit
+ *                                   positions come from; grid: ctx as to_header() prints it, 14 digits; shifted:
+ *                                   _shift_header(hdr_small) as its cards read back) */
+int coreg_set_context_frames(coreg_handle* h, int32_t n_frames, int32_t ny, int32_t nx, int dtype,
+                             const coreg_wcs2d* hdrs, const void* const* pixels);
+int coreg_context_frame_from_small(coreg_handle* h, int32_t k);
+int coreg_sweep_context(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small,
+                        const int32_t* col_frame, const coreg_lags* lags, int order, int method, int cdelt_semantics,
+                        int has_min, double vmin, int has_max, double vmax, int64_t lag_begin, int64_t lag_end,
+                        double* corr_out, int out_on_device);
+int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small, double d_crval1,
+                              double d_crval2, double d_cdelt1, double d_cdelt2, double d_crota, int cdelt_semantics,
+                              coreg_wcs2d* ctx, coreg_wcs2d* grid, coreg_wcs2d* shifted);
+
 /* ---- All GPUs of the node from ONE process ------------------------------------------------------------------------
  * The reference's `Alignment(..., parallelism=True, counts_cpu_max=N)` uses the whole machine from a plain
  * `python script.py`: its lag loop is fanned out over a process pool (hdrshift/alignment.py:692-744, README.md:47-87).
