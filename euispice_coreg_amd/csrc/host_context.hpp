@@ -189,6 +189,9 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
     h->stats.n_grid_points = (long long)gW * gH;
     h->stats.n_active_points = (long long)gW * gH;
     h->stats.n_lags = n_out;
+    // re-evaluated lag-points of THIS sweep (coreg_last_visit_counts "refined_lag_points"), summed over its launches
+    HIPCHK(h->counters.reserve(8 * sizeof(long long)));
+    HIPCHK(hipMemsetAsync(h->counters.p, 0, 8 * sizeof(long long), h->stream));
     if (n_out == 0) return COREG_OK;
 
     HIPCHK(c->mean.reserve(2 * sizeof(double)));
@@ -309,9 +312,10 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
             f.lag_begin = lag_begin;
             f.out = out_dev;
             f.part_stride = ns_;
+            f.refine_count = h->counters.as<long long>();
             RefineArgs& r = f.refine;
-            r.enabled = 1;
-            r.cond = kRefineCond;
+            r.enabled = h->opt_refine ? 1 : 0;  // (options "refine", "refine_cond_log10")
+            r.cond = std::pow(10.0, (double)h->opt_refine_cond_log10);
             r.flags = c->flags.as<int>();
             r.slot_pivots = c->slot_pivots.as<double>();
             r.list = c->list.as<int>();
@@ -321,15 +325,17 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
             r.out = out_dev;
             hipLaunchKernelGGL(k_finalize, dim3((unsigned)((ns_ + kFinSlots - 1) / kFinSlots)), dim3(kFinThreads), 0,
                                h->stream, f);
-            hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, r, ns_, (long long*)nullptr);
-            if (c->f32 && h->small_f32)
-                hipLaunchKernelGGL((k_refine_context<float, float>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
-            else if (c->f32)
-                hipLaunchKernelGGL((k_refine_context<float, double>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
-            else if (h->small_f32)
-                hipLaunchKernelGGL((k_refine_context<double, float>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
-            else
-                hipLaunchKernelGGL((k_refine_context<double, double>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
+            if (r.enabled) {
+                hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, r, ns_, h->counters.as<long long>());
+                if (c->f32 && h->small_f32)
+                    hipLaunchKernelGGL((k_refine_context<float, float>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
+                else if (c->f32)
+                    hipLaunchKernelGGL((k_refine_context<float, double>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
+                else if (h->small_f32)
+                    hipLaunchKernelGGL((k_refine_context<double, float>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
+                else
+                    hipLaunchKernelGGL((k_refine_context<double, double>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
+            }
             HIPCHK(hipGetLastError());
         }
         HIPCHK(hipEventSynchronize(c->ev_b));

@@ -150,7 +150,9 @@ __global__ void __launch_bounds__(kCtxThreads) k_context_sweep(const ContextArgs
 }
 
 // 'residus': np.std over the thresholded samples (one-pass moments, as k_finalize's residus branch); NaN when a selected
-// sample is NaN or nothing is selected
+// sample is NaN or nothing is selected, and when a term is infinite (a = 0 with b != 0): np.std's mean is then infinite,
+// its deviations NaN, while s4 / n - m * m would be inf - inf and fmax(NaN, 0) = 0, the best possible score.  (Unlike the
+// main sweeps, whose point_lag drops a non-finite term, ctx_accumulate adds every selected term.)
 __global__ void k_finalize_context_residus(const double* partials, int n_groups, long long n_slots,
                                            long long lag_begin, const long long* out_index, double* out) {
     const long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -163,7 +165,10 @@ __global__ void k_finalize_context_residus(const double* partials, int n_groups,
         s4 += p[4 * n_slots];
     }
     double r = __builtin_nan("");
-    if (n > 0.0 && s2 == s2 && s4 == s4) {
+    if (n > 0.0 && isfinite(s2) && s4 == s4) {
+        // m * m rounded on its own, not fused with the subtraction: the fma would leave the product's rounding error
+        // (up to half an ulp of m * m), so one selected sample, or equal terms, would give sqrt(that) instead of 0
+#pragma clang fp contract(off)
         const double m = s2 / n;
         r = sqrt(fmax(s4 / n - m * m, 0.0));
     }

@@ -487,6 +487,8 @@ int coreg_fit_gaussian2d(int32_t m, const double* x, const double* y, const doub
  *                                   output is complete when the call returns.  Planned on the host per lag
  *                                   (geometry.hpp: context_lag_headers); the border samples of the SPICE resample, whose
  *                                   bounds rule hangs on wcslib's rounding, are decided by wcslib's own arithmetic.
+ *                                   Options "refine" / "refine_cond_log10" apply as to the other sweeps, and
+ *                                   coreg_last_visit_counts counts this sweep's re-evaluated lag-points.
  *   coreg_context_lag_headers       host only: the three headers of one lag-point (ctx: the shifted grid the slit
  *                                   positions come from; grid: ctx as to_header() prints it, 14 digits; shifted:
  *                                   _shift_header(hdr_small) as its cards read back) */
