@@ -140,17 +140,7 @@ int coreg_nansum_planes_be(const void* cube, int32_t bitpix, int64_t n_pixels, c
             }
         }
     };
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int nt = (int)std::min<int64_t>(std::min<unsigned>(hw, 12u), std::max<int64_t>(1, n_pixels * std::max(n_sel, 1) / (1 << 18)));
-    if (nt <= 1) {
-        work(0, n_pixels);
-        return COREG_OK;
-    }
-    std::vector<std::thread> th;
-    const int64_t per = ((n_pixels + nt - 1) / nt + 7) & ~(int64_t)7;
-    for (int t = 1; t < nt; ++t) th.emplace_back(work, std::min<int64_t>(n_pixels, t * per), std::min<int64_t>(n_pixels, (t + 1) * per));
-    work(0, std::min<int64_t>(n_pixels, per));
-    for (auto& t : th) t.join();
+    parallel_for(n_pixels, (unsigned)std::min<int64_t>(12, n_pixels * std::max(n_sel, 1) / (1 << 18)), 0, work);
     return COREG_OK;
 }
 

@@ -150,24 +150,13 @@ int coreg_decode_tiled_host(const coreg_fits_tiled* t, void* out, int dtype, int
     im.out = out;
     im.out_dtype = dtype == COREG_F32 ? coregrice::OUT_F32 : coregrice::OUT_F64;
     const int nt = t->n_tiles;
-    const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
-    const int n_thr = (int)std::min<long long>(std::min<unsigned>(hw, 12u),
-                                               std::max<long long>(1, (long long)t->naxis1 * t->naxis2 / (1 << 16)));
     auto work = [&](int lo, int hi) {
         for (int k = lo; k < hi; ++k) {
             const int e = coregrice::decode_tile(im, k);
             if (tile_status) tile_status[k] = e;
         }
     };
-    if (n_thr <= 1) {
-        work(0, nt);
-        return COREG_OK;
-    }
-    std::vector<std::thread> th;
-    const int per = (nt + n_thr - 1) / n_thr;
-    for (int k = 1; k < n_thr; ++k) th.emplace_back(work, std::min(nt, k * per), std::min(nt, (k + 1) * per));
-    work(0, std::min(nt, per));
-    for (auto& x : th) x.join();
+    parallel_for(nt, (unsigned)std::min<long long>(12, (long long)t->naxis1 * t->naxis2 / (1 << 16)), 0, work);
     return COREG_OK;
 }
 

@@ -1,6 +1,142 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order; round 6 split by concern,
 // no behaviour change): C ABI: coreg_sweep_carrington / coreg_sweep_helioprojective, grid-shared sums, pivots, stats.
 #pragma once
+namespace {
+// ---- the steps every sweep shares ---------------------------------------------------------------------------------
+// A sweep call between open_sweep and end_sweep: its lag set and slice, and where the results go.
+struct SweepCall {
+    const coreg_lags* lags = nullptr;
+    LagDims d;
+    int order = 0, method = 0, sem = 0;
+    long long lag_begin = 0, lag_end = 0, n_out = 0;
+    double* corr_out = nullptr;
+    int out_on_device = 0;
+    double* out_dev = nullptr;
+    long long row() const { return (long long)d.n2 * d.nc; }  // lag indices per CRVAL1 value
+    int i1_lo() const { return (int)(lag_begin / row()); }
+    int i1_hi() const { return (int)((lag_end - 1) / row()); }
+};
+
+// The checks and set-up of the public sweeps, in this order: method, order, the entry point's own checks (`own_checks`),
+// the lag set with the combination range the entry point took off the handle, the device, the reference-on-grid shape
+// (`grid_w` x `grid_h`, `grid_what` names it), begin_sweep.  With nothing to sweep (call->n_out == 0) the caller returns
+// end_sweep at once.
+template <typename OwnChecks>
+int open_sweep(coreg_handle* h, ComboRange combo, OwnChecks own_checks, const coreg_lags* lags, int order, int method,
+               int sem, int64_t lag_begin, int64_t lag_end, int grid_w, int grid_h, const char* grid_what,
+               double* corr_out, int out_on_device, SweepCall* call) {
+    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS)
+        return fail(h, COREG_ENOTIMPL, "method must be COREG_METHOD_CORRELATION or COREG_METHOD_RESIDUS");
+    RETCHK(check_order(h, order));
+    RETCHK(own_checks());
+    RETCHK(check_lags(h, lags, &call->d, lag_begin, lag_end, combo));
+    RETCHK(bind_device_nowait(h));  // (the image to align is joined right before k_sweep: launch_sweep)
+    if (h->ref.p && (h->gW != grid_w || h->gH != grid_h))
+        return fail(h, COREG_EINVAL, std::string("reference-on-grid shape differs from ") + grid_what);
+    call->lags = lags;
+    call->order = order;
+    call->method = method;
+    call->sem = sem;
+    call->lag_begin = lag_begin;
+    call->lag_end = lag_end;
+    call->n_out = lag_end - lag_begin;
+    call->corr_out = corr_out;
+    call->out_on_device = out_on_device;
+    return begin_sweep(h, call->n_out, corr_out, out_on_device, &call->out_dev);
+}
+
+int close_sweep(coreg_handle* h, const SweepCall& call) {
+    return end_sweep(h, call.n_out, call.corr_out, call.out_on_device, call.out_dev);
+}
+
+// a plan without a launch: every lag-point NaN
+int close_empty_sweep(coreg_handle* h, const SweepCall& call) {
+    RETCHK(fill_nan(h, call.out_dev, call.n_out));
+    return close_sweep(h, call);
+}
+
+// Local geometry from the maps of the central CRVAL lag and of that lag plus one mean step on either axis, about the
+// middle of the target grid.  at(v1, v2, u, v, &x, &y): target pixel (u, v) under the CRVAL lag (v1, v2); false: that
+// lag has no map (any plan will do then, its lanes are NaN).
+template <typename MapAt>
+Geometry local_geometry(const coreg_wcs2d& target, const SweepCall& call, MapAt at) {
+    const coreg_lags& l = *call.lags;
+    int e1[3], e2[3];
+    extreme_lags(l.crval1, call.d.n1, e1);
+    extreme_lags(l.crval2, call.d.n2, e2);
+    const double v1 = l.crval1[e1[1]], v2 = l.crval2[e2[1]];
+    const double s1 = lag_step(l.crval1, call.d.n1), s2 = lag_step(l.crval2, call.d.n2);
+    const double u = target.naxis1 * 0.5, v = target.naxis2 * 0.5;
+    double x0, y0, xi, yi, xj, yj, xa, ya, xb, yb;
+    Geometry g;
+    if (!at(v1, v2, u, v, &x0, &y0) || !at(v1, v2, u + 1, v, &xi, &yi) || !at(v1, v2, u, v + 1, &xj, &yj) ||
+        !at(v1 + s1, v2, u, v, &xa, &ya) || !at(v1, v2 + s2, u, v, &xb, &yb))
+        return g;
+    g.dx_di = xi - x0;
+    g.dy_di = yi - y0;
+    g.dx_dj = xj - x0;
+    g.dy_dj = yj - y0;
+    g.ax = xa - x0;
+    g.ay = ya - y0;
+    g.bx = xb - x0;
+    g.by = yb - y0;
+    return g;
+}
+
+// tile shape + lag patch for the CRVAL1 rows of the slice
+Plan plan_sweep(coreg_handle* h, const Geometry& geo, const SweepCall& call) {
+    return choose_plan(h, geo, call.i1_hi() - call.i1_lo() + 1, call.d.n2, h->opt_use_lds ? lds_window_elems(h) : (1LL << 40));
+}
+
+// Combination c of the sweep: its (CDELT, CROTA)-shifted header and its lag slots.  False: nothing of it to launch (no
+// lag of the slice, or a lag that kills the reference's worker: NaN, already filled).  Pure: called from threads.
+bool combo_slots(const SweepCall& call, const coreg_wcs2d& small, const Plan& plan, long long c, coreg_wcs2d* hc,
+                 SlotList* slots) {
+    const long long first = (call.lag_begin - c + call.d.nc - 1) / call.d.nc;  // smallest k with k*nc + c >= begin
+    if (first * call.d.nc + c >= call.lag_end) return false;
+    int i3, i4, i5;
+    call.d.inner(c, &i3, &i4, &i5);
+    if (shift_header(small, 0.0, 0.0, call.lags->cdelt1[i3], call.lags->cdelt2[i4], call.lags->crota[i5], call.sem, hc))
+        return false;
+    build_slots(call.d, c, call.lag_begin, call.lag_end, plan.sw, plan.sh, slots);
+    return slots->n_batches > 0;
+}
+
+// launch_precompute (unless `launch` is false: the compacted points are still those of the same arguments), and keep how
+// to launch it again: a grid-shared sweep's coreg_finalize_sums re-evaluates a launch after later launches have run
+template <int MODE>
+int precompute(coreg_handle* h, const PrecomputeArgs& pa, int n_tiles, int n_groups, int n_batches, bool launch = true) {
+    if (launch) RETCHK(launch_precompute<MODE>(h, pa, n_tiles, n_groups, n_batches));
+    h->last_precompute = [pa, n_tiles, n_groups, n_batches](coreg_handle* hh) {
+        return launch_precompute<MODE>(hh, pa, n_tiles, n_groups, n_batches);
+    };
+    return COREG_OK;
+}
+
+// k_finalize of pending launch `pf` of a grid-shared sweep, from the reduced sums (work-space pointers taken afresh: a
+// later launch of the sweep may have grown the buffers)
+int finalize_pending(coreg_handle* h, const coreg_handle::PendingFinalize& pf, long long* refine_count, double* out_dev,
+                     FinalizeArgs* f) {
+    *f = FinalizeArgs{};
+    RETCHK(fill_refine(h, &f->refine, pf.refine.mode, pf.refine.order, pf.refine.lane_params, pf.refine.car_inv,
+                       pf.n_slots));
+    f->refine.enabled = pf.refine.enabled;
+    f->refine_count = refine_count;
+    f->partials = h->sums.as<double>() + pf.slot_off;
+    f->n_groups = 1;
+    f->n_slots = pf.n_slots;
+    f->part_stride = h->sums_slots;
+    f->out_index = h->fin_outidx.as<long long>() + pf.slot_off;
+    f->lag_begin = pf.lag_begin;
+    f->out = out_dev;
+    f->residus = pf.residus;
+    f->n_required = (long long)h->gW * h->gH;
+    hipLaunchKernelGGL(k_finalize, dim3((unsigned)((pf.n_slots + kFinSlots - 1) / kFinSlots)),
+                       dim3(kFinSlots * kFinLanes), 0, h->stream, *f);
+    return COREG_OK;
+}
+}  // namespace
+
 extern "C" {
 int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const coreg_carr_grid* grid, double solar_r,
                            const coreg_lags* lags, int order, int method, int cdelt_semantics, int64_t lag_begin,
@@ -9,21 +145,17 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
     const ComboRange combo = take_combo_range(h);
     trace("sweep_carrington: enter");
     if (!hdr_small || !grid) return fail(h, COREG_EINVAL, "sweep_carrington: null header/grid");
-    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS)
-        return fail(h, COREG_ENOTIMPL, "method must be COREG_METHOD_CORRELATION or COREG_METHOD_RESIDUS");
-    RETCHK(check_order(h, order));
-    RETCHK(check_wcs(h, hdr_small, true));
-    RETCHK(check_grid(h, grid));
-    if (!std::isfinite(solar_r) || !(solar_r > 0.0)) return fail(h, COREG_EINVAL, "solar_r must be positive");
-    LagDims d;
-    RETCHK(check_lags(h, lags, &d, lag_begin, lag_end, combo));
-    RETCHK(bind_device_nowait(h));  // (the image to align is joined right before k_sweep: launch_sweep)
-    if (h->ref.p && (h->gW != grid->n_lon || h->gH != grid->n_lat))
-        return fail(h, COREG_EINVAL, "reference-on-grid shape differs from the Carrington grid");
-    const long long n_out = lag_end - lag_begin;
-    double* out_dev = nullptr;
-    RETCHK(begin_sweep(h, n_out, corr_out, out_on_device, &out_dev));
-    if (n_out == 0) return end_sweep(h, n_out, corr_out, out_on_device, out_dev);  // (nothing to fill)
+    auto own_checks = [&] {
+        RETCHK(check_wcs(h, hdr_small, true));
+        RETCHK(check_grid(h, grid));
+        if (!std::isfinite(solar_r) || !(solar_r > 0.0)) return fail(h, COREG_EINVAL, "solar_r must be positive");
+        return COREG_OK;
+    };
+    SweepCall call;
+    RETCHK(open_sweep(h, combo, own_checks, lags, order, method, cdelt_semantics, lag_begin, lag_end, grid->n_lon,
+                      grid->n_lat, "the Carrington grid", corr_out, out_on_device, &call));
+    if (call.n_out == 0) return close_sweep(h, call);  // (nothing to fill)
+    const LagDims& d = call.d;
 
     CarrDev cd;
     std::memset(&cd, 0, sizeof(cd));
@@ -49,19 +181,10 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
         geo.bx = c0.sr * s2 / hdr_small->cdelt1;
         geo.by = c0.cr * s2 / hdr_small->cdelt2;
     }
-    const long long row = (long long)d.n2 * d.nc;
-    const int m1 = (int)((lag_end - 1) / row) - (int)(lag_begin / row) + 1;
-    const Plan plan = choose_plan(h, geo, m1, d.n2, h->opt_use_lds ? lds_window_elems(h) : (1LL << 40));
-
+    const Plan plan = plan_sweep(h, geo, call);
     PrecomputeArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    {
-        const int th = kTilePts / plan.tile_w;
-        RETCHK(reserve_tiles(h, ((h->gW + plan.tile_w - 1) / plan.tile_w) * ((h->gH + th - 1) / th)));
-    }
-    fill_precompute_common(h, &pa, plan.tile_w);
-    pa.residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
-    const int n_tiles = pa.tiles_x * pa.tiles_y;
+    int n_tiles;
+    RETCHK(setup_precompute(h, plan, method, &pa, &n_tiles));
 
     // ---- every (cdelt1, cdelt2, crota) combination = one precompute + one sweep launch; all lag parameters of all
     //      launches are staged together and uploaded once
@@ -76,18 +199,8 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
     std::vector<long long> outidx;
     SlotList slots;
     for (long long c = 0; c < d.nc; ++c) {
-        {
-            const long long first = (lag_begin - c + d.nc - 1) / d.nc;  // smallest k with k*nc + c >= begin
-            if (first * d.nc + c >= lag_end) continue;
-        }
-        int i3, i4, i5;
-        d.inner(c, &i3, &i4, &i5);
         coreg_wcs2d hc;
-        if (shift_header(*hdr_small, 0.0, 0.0, lags->cdelt1[i3], lags->cdelt2[i4], lags->crota[i5], cdelt_semantics,
-                         &hc))
-            continue;  // reference semantics: this lag kills the worker -> NaN (already filled)
-        build_slots(d, c, lag_begin, lag_end, plan.sw, plan.sh, &slots);
-        if (slots.n_batches == 0) continue;
+        if (!combo_slots(call, *hdr_small, plan, c, &hc, &slots)) continue;
         const size_t ns = slots.i1.size();
         Launch L;
         L.slot_off = outidx.size();
@@ -129,12 +242,9 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
         L.f1hi = (double)(h->sH - 1) - y0min;
         launches.push_back(L);
     }
-    if (launches.empty()) {
-        RETCHK(fill_nan(h, out_dev, n_out));
-        return end_sweep(h, n_out, corr_out, out_on_device, out_dev);
-    }
-    RETCHK(upload_plan(h, params, outidx, out_dev, n_out));
-    RETCHK(prepare_sharded(h, outidx.size(), n_out, lag_begin));
+    if (launches.empty()) return close_empty_sweep(h, call);
+    RETCHK(upload_plan(h, params, outidx, call.out_dev, call.n_out));
+    RETCHK(prepare_sharded(h, outidx.size(), call.n_out, lag_begin));
     for (const Launch& L : launches) {
         set_carr_common(&cd, L.cc);
         pa.carr = cd;
@@ -153,20 +263,14 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
             pa.dlon = grid->n_lon > 1 ? (std::fabs(grid->lon1 - grid->lon0) / (grid->n_lon - 1) * 1.001 + 1e-4) * kDeg2Rad : 0.0;
             pa.dlat = grid->n_lat > 1 ? (std::fabs(grid->lat1 - grid->lat0) / (grid->n_lat - 1) * 1.001 + 1e-4) * kDeg2Rad : 0.0;
         }
-        {
-            const int ng = pick_groups(h, L.n_batches, n_tiles), nb = L.n_batches;
-            RETCHK(launch_precompute<MODE_TRANSLATE>(h, pa, n_tiles, ng, nb));
-            h->last_precompute = [pa, n_tiles, ng, nb](coreg_handle* hh) {
-                return launch_precompute<MODE_TRANSLATE>(hh, pa, n_tiles, ng, nb);
-            };
-        }
+        RETCHK(precompute<MODE_TRANSLATE>(h, pa, n_tiles, pick_groups(h, L.n_batches, n_tiles), L.n_batches));
         // SoA block of this launch starts at 2 * slot_off doubles (every earlier launch contributed 2 per slot)
         RETCHK(launch_sweep(h, MODE_TRANSLATE, order, method, h->lane_params.as<double>() + 2 * L.slot_off,
-                            h->out_index.as<long long>() + L.slot_off, L.n_batches, n_tiles, lag_begin, out_dev, nullptr,
-                            nullptr, (long long)L.slot_off,
+                            h->out_index.as<long long>() + L.slot_off, L.n_batches, n_tiles, lag_begin, call.out_dev,
+                            nullptr, nullptr, (long long)L.slot_off,
                             pick_pitch(h, plan, h->opt_use_lds ? lds_window_elems(h) : 0, order)));
     }
-    return end_sweep(h, n_out, corr_out, out_on_device, out_dev);
+    return close_sweep(h, call);
 }
 
 // Plate-carree maps on both sides (Alignment.align_using_initial_carrington, alignment.py:344-399 ->
@@ -174,10 +278,10 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
 // the native frames of the two maps (a CRVAL2 lag makes the shifted map oblique).  One precompute (native angles of
 // the target pixels), one sweep launch per (cdelt1, cdelt2, crota) combination (its native -> pixel affine map is a
 // launch constant).  Lags whose header has no valid native pole get NaN (astropy raises for them).
-static int sweep_car(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small, const coreg_lags* lags,
-                     const LagDims& d, int order, int method, int cdelt_semantics, int64_t lag_begin, int64_t lag_end,
-                     double* corr_out, int out_on_device, double* out_dev) {
-    const long long n_out = lag_end - lag_begin;
+static int sweep_car(coreg_handle* h, const SweepCall& call, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small) {
+    const coreg_lags* lags = call.lags;
+    const LagDims& d = call.d;
+    const int order = call.order;
     Mat3 r_target;
     if (car_native_to_celestial(*hdr_target, &r_target))
         return fail(h, COREG_EINVAL, "hdr_target: no valid native pole for this CRVAL2 / LONPOLE (CAR)");
@@ -190,43 +294,16 @@ static int sweep_car(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg
     auto shifted = [&](const coreg_wcs2d& base, int i1, int i2) {
         return shifted_by(base, lags->crval1[i1], lags->crval2[i2]);
     };
-    // ---- plan: local geometry from the maps of a central lag and of that lag plus one mean step on either axis
-    Geometry geo;
-    {
-        int e1[3], e2[3];
-        extreme_lags(lags->crval1, d.n1, e1);
-        extreme_lags(lags->crval2, d.n2, e2);
-        const double v1 = lags->crval1[e1[1]], v2 = lags->crval2[e2[1]];
-        CarMapHost m0, m1h, m2h;
-        if (m0.init(*hdr_target, shifted_by(*hdr_small, v1, v2)) ||
-            m1h.init(*hdr_target, shifted_by(*hdr_small, v1 + lag_step(lags->crval1, d.n1), v2)) ||
-            m2h.init(*hdr_target, shifted_by(*hdr_small, v1, v2 + lag_step(lags->crval2, d.n2)))) {
-            geo.dx_di = geo.dy_dj = 1.0;  // central lag invalid: any plan will do, its lanes are NaN
-            geo.dy_di = geo.dx_dj = geo.ax = geo.ay = geo.bx = geo.by = 0.0;
-        } else {
-            const double u = hdr_target->naxis1 * 0.5, v = hdr_target->naxis2 * 0.5;
-            double x0, y0, x1, y1;
-            m0.apply(u, v, &x0, &y0);
-            m0.apply(u + 1, v, &x1, &y1);
-            geo.dx_di = x1 - x0;
-            geo.dy_di = y1 - y0;
-            m0.apply(u, v + 1, &x1, &y1);
-            geo.dx_dj = x1 - x0;
-            geo.dy_dj = y1 - y0;
-            m1h.apply(u, v, &x1, &y1);
-            geo.ax = x1 - x0;
-            geo.ay = y1 - y0;
-            m2h.apply(u, v, &x1, &y1);
-            geo.bx = x1 - x0;
-            geo.by = y1 - y0;
-        }
-    }
-    const long long row = (long long)d.n2 * d.nc;
-    const int m1 = (int)((lag_end - 1) / row) - (int)(lag_begin / row) + 1;
-    const Plan plan = choose_plan(h, geo, m1, d.n2, h->opt_use_lds ? lds_window_elems(h) : (1LL << 40));
+    const Plan plan = plan_sweep(h, local_geometry(*hdr_target, call, [&](double v1, double v2, double u, double v,
+                                                                        double* x, double* y) {
+        CarMapHost m;
+        if (m.init(*hdr_target, shifted_by(*hdr_small, v1, v2))) return false;
+        m.apply(u, v, x, y);
+        return true;
+    }), call);
 
     // rotation of every (CRVAL1, CRVAL2) lag: R = R_small(lag)^T * R_target  (PC / CDELT do not enter it)
-    const int i1_lo = (int)(lag_begin / row), i1_hi = (int)((lag_end - 1) / row);
+    const int i1_lo = call.i1_lo(), i1_hi = call.i1_hi();
     std::vector<double> rot((size_t)(i1_hi - i1_lo + 1) * d.n2 * 9);
     const double nanv = std::numeric_limits<double>::quiet_NaN();
     for (int i1 = i1_lo; i1 <= i1_hi; ++i1)
@@ -269,7 +346,7 @@ static int sweep_car(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg
     // (geometry.hpp WcslibCar, bit-exact) decides.  "border_fix" 0: rotation path for that lag-point too.
     long long identity_out = -1;
     BorderFix id_fix;
-    std::vector<unsigned char> id_flags;
+    std::vector<std::vector<unsigned char>> id_flags;
     auto same_header = [](const coreg_wcs2d& a, const coreg_wcs2d& b) {
         auto eq = [](double x, double y) { return x == y || (x != x && y != y); };
         return a.proj == b.proj && a.crpix1 == b.crpix1 && a.crpix2 == b.crpix2 && a.crval1 == b.crval1 &&
@@ -278,16 +355,8 @@ static int sweep_car(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg
                eq(a.lonpole, b.lonpole) && eq(a.latpole, b.latpole) && a.naxis1 == b.naxis1 && a.naxis2 == b.naxis2;
     };
     for (long long c = 0; c < d.nc; ++c) {
-        const long long first = (lag_begin - c + d.nc - 1) / d.nc;
-        if (first * d.nc + c >= lag_end) continue;
-        int i3, i4, i5;
-        d.inner(c, &i3, &i4, &i5);
         coreg_wcs2d hc;
-        if (shift_header(*hdr_small, 0.0, 0.0, lags->cdelt1[i3], lags->cdelt2[i4], lags->crota[i5], cdelt_semantics,
-                         &hc))
-            continue;  // reference semantics: this lag kills the worker -> NaN (already filled)
-        build_slots(d, c, lag_begin, lag_end, plan.sw, plan.sh, &slots);
-        if (slots.n_batches == 0) continue;
+        if (!combo_slots(call, *hdr_small, plan, c, &hc, &slots)) continue;
         const size_t ns = slots.i1.size();
         Launch L;
         L.slot_off = outidx.size();
@@ -360,29 +429,20 @@ static int sweep_car(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg
             it.flags_off = -1;
             if (order & 1) {
                 it.flags_off = 0;
-                id_flags = wcslib_tap_shift_flags(h, *hdr_target, *hdr_target, inv);
+                id_flags.push_back(wcslib_tap_shift_flags(h, *hdr_target, *hdr_target, inv));
             }
             if (it.n > 0 || it.flags_off >= 0) id_fix.items.push_back(it);
         }
     }
-    if (launches.empty()) {
-        RETCHK(fill_nan(h, out_dev, n_out));
-        return end_sweep(h, n_out, corr_out, out_on_device, out_dev);
-    }
+    if (launches.empty()) return close_empty_sweep(h, call);
     trace("sweep_helioprojective: lane parameters laid out");
-    RETCHK(upload_plan(h, params, outidx, out_dev, n_out));
-    RETCHK(prepare_sharded(h, outidx.size(), n_out, lag_begin));
+    RETCHK(upload_plan(h, params, outidx, call.out_dev, call.n_out));
+    RETCHK(prepare_sharded(h, outidx.size(), call.n_out, call.lag_begin));
     trace("sweep_helioprojective: plan in page-locked memory");
 
     PrecomputeArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    {
-        const int th = kTilePts / plan.tile_w;
-        RETCHK(reserve_tiles(h, ((h->gW + plan.tile_w - 1) / plan.tile_w) * ((h->gH + th - 1) / th)));
-    }
-    fill_precompute_common(h, &pa, plan.tile_w);
-    pa.residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
-    const int n_tiles = pa.tiles_x * pa.tiles_y;
+    int n_tiles;
+    RETCHK(setup_precompute(h, plan, call.method, &pa, &n_tiles));
     const Affine2 fwd = car_pix_to_native(*hdr_target);
     pa.car_fwd.m00 = fwd.m00;
     pa.car_fwd.m01 = fwd.m01;
@@ -394,37 +454,23 @@ static int sweep_car(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg
     pa.f0lo = pa.f1lo = -inf;  // no culling by position: only non-finite reference values drop out
     pa.f0hi = pa.f1hi = inf;
     if (!id_fix.items.empty()) RETCHK(upload_border_pixels(h, id_fix.pixels));
-    if (!id_flags.empty()) {
-        HIPCHK(h->border_flags.reserve(id_flags.size()));
-        HIPCHK(hipStreamSynchronize(h->stream));  // (pageable source, rare path)
-        HIPCHK(hipMemcpy(h->border_flags.p, id_flags.data(), id_flags.size(), hipMemcpyHostToDevice));
-    }
+    RETCHK(upload_border_flags(h, id_flags));
     int last_groups = -1, last_batches = -1;
     for (const Launch& L : launches) {
         if (L.identity) {
             // target pixel -> the same pixel of the map to align: base coordinates = pixel indices, no culling by position
             PrecomputeArgs pi = pa;
             std::memset(&pi.car_fwd, 0, sizeof(pi.car_fwd));
-            const int ng = pick_groups(h, 1, n_tiles);
-            RETCHK(launch_precompute<MODE_HOMOGRAPHY>(h, pi, n_tiles, ng, 1));
-            h->last_precompute = [pi, n_tiles, ng](coreg_handle* hh) {
-                return launch_precompute<MODE_HOMOGRAPHY>(hh, pi, n_tiles, ng, 1);
-            };
+            RETCHK(precompute<MODE_HOMOGRAPHY>(h, pi, n_tiles, pick_groups(h, 1, n_tiles), 1));
             last_groups = last_batches = -1;  // (the compacted points now hold pixel indices, not unit vectors)
-            RETCHK(launch_sweep(h, MODE_HOMOGRAPHY, order, method, h->lane_params.as<double>() + 9 * L.slot_off,
-                                h->out_index.as<long long>() + L.slot_off, 1, n_tiles, lag_begin, out_dev, nullptr, &id_fix,
-                                (long long)L.slot_off));
+            RETCHK(launch_sweep(h, MODE_HOMOGRAPHY, order, call.method, h->lane_params.as<double>() + 9 * L.slot_off,
+                                h->out_index.as<long long>() + L.slot_off, 1, n_tiles, call.lag_begin, call.out_dev, nullptr,
+                                &id_fix, (long long)L.slot_off));
             continue;
         }
         // the work partition (k_tile_list) depends on the group count of the launch: redo it only when that changes
         const int ng = pick_groups(h, L.n_batches, n_tiles);
-        if (ng != last_groups || L.n_batches != last_batches) RETCHK(launch_precompute<MODE_CAR>(h, pa, n_tiles, ng, L.n_batches));
-        {
-            const int nb = L.n_batches;
-            h->last_precompute = [pa, n_tiles, ng, nb](coreg_handle* hh) {
-                return launch_precompute<MODE_CAR>(hh, pa, n_tiles, ng, nb);
-            };
-        }
+        RETCHK(precompute<MODE_CAR>(h, pa, n_tiles, ng, L.n_batches, ng != last_groups || L.n_batches != last_batches));
         last_groups = ng;
         last_batches = L.n_batches;
         BorderFix tap;  // (no whole-grid items here: the identity lag has its own launch)
@@ -436,11 +482,11 @@ static int sweep_car(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg
                 [&](int slot) { return shifted(L.hc, L.i1[(size_t)slot], L.i2[(size_t)slot]); }, &tap,
                 h->lane_params.as<double>() + 9 * L.slot_off, &L.inv, &pa.car_fwd));
         }
-        RETCHK(launch_sweep(h, MODE_CAR, order, method, h->lane_params.as<double>() + 9 * L.slot_off,
-                            h->out_index.as<long long>() + L.slot_off, L.n_batches, n_tiles, lag_begin, out_dev,
+        RETCHK(launch_sweep(h, MODE_CAR, order, call.method, h->lane_params.as<double>() + 9 * L.slot_off,
+                            h->out_index.as<long long>() + L.slot_off, L.n_batches, n_tiles, call.lag_begin, call.out_dev,
                             &L.inv, L.tap_any ? &tap : nullptr, (long long)L.slot_off));
     }
-    return end_sweep(h, n_out, corr_out, out_on_device, out_dev);
+    return close_sweep(h, call);
 }
 
 int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small,
@@ -451,61 +497,28 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
     if (!hdr_target || !hdr_small) return fail(h, COREG_EINVAL, "sweep_helioprojective: null header");
     if (hdr_target->proj != hdr_small->proj || (hdr_small->proj != COREG_PROJ_TAN && hdr_small->proj != COREG_PROJ_CAR))
         return fail(h, COREG_ENOTIMPL, "both headers must be TAN (helioprojective) or both CAR (Carrington maps)");
-    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS)
-        return fail(h, COREG_ENOTIMPL, "method must be COREG_METHOD_CORRELATION or COREG_METHOD_RESIDUS");
-    RETCHK(check_order(h, order));
-    RETCHK(check_wcs(h, hdr_target, false));
-    RETCHK(check_wcs(h, hdr_small, false));
-    LagDims d;
-    RETCHK(check_lags(h, lags, &d, lag_begin, lag_end, combo));
-    RETCHK(bind_device_nowait(h));
-    if (h->ref.p && (h->gW != hdr_target->naxis1 || h->gH != hdr_target->naxis2))
-        return fail(h, COREG_EINVAL, "reference-on-grid shape differs from hdr_target NAXIS1/NAXIS2");
-    const long long n_out = lag_end - lag_begin;
-    double* out_dev = nullptr;
-    RETCHK(begin_sweep(h, n_out, corr_out, out_on_device, &out_dev));
-    if (n_out == 0) return end_sweep(h, n_out, corr_out, out_on_device, out_dev);  // (nothing to fill)
-    if (hdr_small->proj == COREG_PROJ_CAR)
-        return sweep_car(h, hdr_target, hdr_small, lags, d, order, method, cdelt_semantics, lag_begin, lag_end, corr_out,
-                         out_on_device, out_dev);
+    auto own_checks = [&] {
+        RETCHK(check_wcs(h, hdr_target, false));
+        return check_wcs(h, hdr_small, false);
+    };
+    SweepCall call;
+    RETCHK(open_sweep(h, combo, own_checks, lags, order, method, cdelt_semantics, lag_begin, lag_end,
+                      hdr_target->naxis1, hdr_target->naxis2, "hdr_target NAXIS1/NAXIS2", corr_out, out_on_device, &call));
+    if (call.n_out == 0) return close_sweep(h, call);  // (nothing to fill)
+    if (hdr_small->proj == COREG_PROJ_CAR) return sweep_car(h, call, hdr_target, hdr_small);
+    const LagDims& d = call.d;
 
     trace("sweep_helioprojective: enter (checks done)");
-    // ---- plan: local geometry from the maps of the central lag and of its two neighbours
-    Geometry geo;
-    {
-        auto map_of = [&](double v1, double v2, double hm[9]) {
-            coreg_wcs2d hl = *hdr_small;
-            hl.crval1 = hdr_small->crval1 + v1;
-            hl.crval2 = hdr_small->crval2 + v2;
-            homography(*hdr_target, hl, hm);
-        };
-        int e1[3], e2[3];
-        extreme_lags(lags->crval1, d.n1, e1);
-        extreme_lags(lags->crval2, d.n2, e2);
-        const double v1 = lags->crval1[e1[1]], v2 = lags->crval2[e2[1]];
-        double m0[9], m1h[9], m2h[9];
-        map_of(v1, v2, m0);
-        map_of(v1 + lag_step(lags->crval1, d.n1), v2, m1h);
-        map_of(v1, v2 + lag_step(lags->crval2, d.n2), m2h);
-        const double u = hdr_target->naxis1 * 0.5, v = hdr_target->naxis2 * 0.5;
-        double x0, y0, x1, y1;
-        apply_h(m0, u, v, &x0, &y0);
-        apply_h(m0, u + 1, v, &x1, &y1);
-        geo.dx_di = x1 - x0;
-        geo.dy_di = y1 - y0;
-        apply_h(m0, u, v + 1, &x1, &y1);
-        geo.dx_dj = x1 - x0;
-        geo.dy_dj = y1 - y0;
-        apply_h(m1h, u, v, &x1, &y1);
-        geo.ax = x1 - x0;
-        geo.ay = y1 - y0;
-        apply_h(m2h, u, v, &x1, &y1);
-        geo.bx = x1 - x0;
-        geo.by = y1 - y0;
-    }
-    const long long row = (long long)d.n2 * d.nc;
-    const int m1 = (int)((lag_end - 1) / row) - (int)(lag_begin / row) + 1;
-    const Plan plan = choose_plan(h, geo, m1, d.n2, h->opt_use_lds ? lds_window_elems(h) : (1LL << 40));
+    const Plan plan = plan_sweep(h, local_geometry(*hdr_target, call, [&](double v1, double v2, double u, double v,
+                                                                        double* x, double* y) {
+        coreg_wcs2d hl = *hdr_small;
+        hl.crval1 = hdr_small->crval1 + v1;
+        hl.crval2 = hdr_small->crval2 + v2;
+        double hm[9];
+        homography(*hdr_target, hl, hm);
+        apply_h(hm, u, v, x, y);
+        return true;
+    }), call);
 
     // ---- all slots of all (cdelt1, cdelt2, crota) combinations -> ONE launch
     // Two passes.  (1) per combination, independent of every other and of the handle -- a few host threads share them
@@ -530,7 +543,7 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
     std::vector<coreg_wcs2d> tap_combo;      // the (cdelt, crota)-shifted header of each combination
     std::vector<int> tap_slot_combo, tap_slot_i1, tap_slot_i2;
     std::vector<unsigned char> tap_skip;     // padding lanes and lag-points the structured fix handles
-    const int i1_lo = (int)(lag_begin / row), i1_hi = (int)((lag_end - 1) / row);
+    const int i1_lo = call.i1_lo(), i1_hi = call.i1_hi();
     fam.fill_products(i1_lo, i1_hi);  // (read-only from here on: `get` is safe to call from several threads)
     const double nanv = std::numeric_limits<double>::quiet_NaN();
     struct ComboPlan {
@@ -550,16 +563,8 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
     extreme_lags(lags->crval2, d.n2, e2);
     auto plan_combo = [&](long long c) {
         ComboPlan& cp = cps[(size_t)c];
-        const long long first = (lag_begin - c + d.nc - 1) / d.nc;
-        if (first * d.nc + c >= lag_end) return;
-        int i3, i4, i5;
-        d.inner(c, &i3, &i4, &i5);
-        if (shift_header(*hdr_small, 0.0, 0.0, lags->cdelt1[i3], lags->cdelt2[i4], lags->crota[i5], cdelt_semantics,
-                         &cp.hc))
-            return;
-        build_slots(d, c, lag_begin, lag_end, plan.sw, plan.sh, &cp.slots);
-        if (cp.slots.n_batches == 0) return;
-        cp.used = true;
+        cp.used = combo_slots(call, *hdr_small, plan, c, &cp.hc, &cp.slots);
+        if (!cp.used) return;
         const Mat3d B = HomographyFamily::combo(cp.hc);
         const size_t n = cp.slots.i1.size();
         cp.hs.resize(9 * n);
@@ -589,21 +594,10 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
             }
     };
     trace("sweep_helioprojective: geometry + lag family ready");
-    const unsigned plan_threads = (d.nc >= 2 && (long long)d.nc * d.n1 * d.n2 >= 16384)
-                                      ? std::min<unsigned>({8u, (unsigned)d.nc, std::max(1u, std::thread::hardware_concurrency())})
-                                      : 1u;
-    if (plan_threads <= 1) {
-        for (long long c = 0; c < d.nc; ++c) plan_combo(c);
-    } else {
-        std::atomic<long long> next(0);
-        auto worker = [&] {
-            for (long long c = next.fetch_add(1); c < d.nc; c = next.fetch_add(1)) plan_combo(c);
-        };
-        std::vector<std::thread> th;
-        for (unsigned t = 1; t < plan_threads; ++t) th.emplace_back(worker);
-        worker();
-        for (auto& x : th) x.join();
-    }
+    const unsigned plan_threads = (d.nc >= 2 && (long long)d.nc * d.n1 * d.n2 >= 16384) ? 8u : 1u;
+    parallel_for(d.nc, plan_threads, 1, [&](long long lo, long long hi) {
+        for (long long c = lo; c < hi; ++c) plan_combo(c);
+    });
     for (long long c = 0; c < d.nc; ++c) {
         ComboPlan& cp = cps[(size_t)c];
         if (!cp.used) continue;
@@ -656,10 +650,7 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
         outidx.insert(outidx.end(), slots.outidx.begin(), slots.outidx.end());
         n_batches += slots.n_batches;
     }
-    if (n_batches == 0) {
-        RETCHK(fill_nan(h, out_dev, n_out));
-        return end_sweep(h, n_out, corr_out, out_on_device, out_dev);
-    }
+    if (n_batches == 0) return close_empty_sweep(h, call);
     trace("sweep_helioprojective: combinations planned");
     const size_t ns = outidx.size();
     std::vector<double> params(9 * ns);
@@ -682,55 +673,27 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
             }
             eps_of[(size_t)c] = em;
         };
-        if (plan_threads <= 1) {
-            for (long long c = 0; c < d.nc; ++c) transpose(c);
-        } else {
-            std::atomic<long long> next(0);
-            auto worker = [&] {
-                for (long long c = next.fetch_add(1); c < d.nc; c = next.fetch_add(1)) transpose(c);
-            };
-            std::vector<std::thread> th;
-            for (unsigned t = 1; t < plan_threads; ++t) th.emplace_back(worker);
-            worker();
-            for (auto& x : th) x.join();
-        }
+        parallel_for(d.nc, plan_threads, 1, [&](long long lo, long long hi) {
+            for (long long c = lo; c < hi; ++c) transpose(c);
+        });
         for (double e : eps_of) eps_max = std::max(eps_max, e);
     }
     // 1/(1 + eps) = 1 - eps + eps^2 is exact to float64 below ~4e-6 (eps^3 < 1e-16); wider fields divide exactly
     const int sweep_mode = (h->opt_h_series && eps_max < 4.0e-6) ? MODE_HOMOGRAPHY_SERIES : MODE_HOMOGRAPHY;
-    RETCHK(upload_plan(h, params, outidx, out_dev, n_out));
-    RETCHK(prepare_sharded(h, outidx.size(), n_out, lag_begin));
+    RETCHK(upload_plan(h, params, outidx, call.out_dev, call.n_out));
+    RETCHK(prepare_sharded(h, outidx.size(), call.n_out, lag_begin));
 
     PrecomputeArgs pa;
-    std::memset(&pa, 0, sizeof(pa));
-    {
-        const int th = kTilePts / plan.tile_w;
-        RETCHK(reserve_tiles(h, ((h->gW + plan.tile_w - 1) / plan.tile_w) * ((h->gH + th - 1) / th)));
-    }
-    fill_precompute_common(h, &pa, plan.tile_w);
-    pa.residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
-    const int n_tiles = pa.tiles_x * pa.tiles_y;
+    int n_tiles;
+    RETCHK(setup_precompute(h, plan, method, &pa, &n_tiles));
     // the maps are projective and the image corners bound its interior
     pa.f0lo = std::floor(fx0) - 3.0;
     pa.f0hi = std::ceil(fx1) + 3.0;
     pa.f1lo = std::floor(fy0) - 3.0;
     pa.f1hi = std::ceil(fy1) + 3.0;
     if (!fix.items.empty()) RETCHK(upload_border_pixels(h, fix.pixels));
-    if (!flags_host.empty()) {
-        const size_t each = (size_t)h->gW * h->gH;
-        HIPCHK(h->border_flags.reserve(each * flags_host.size()));
-        HIPCHK(hipStreamSynchronize(h->stream));  // (pageable source, rare path: blocking copies are fine)
-        for (size_t k = 0; k < flags_host.size(); ++k)
-            HIPCHK(hipMemcpy(h->border_flags.as<unsigned char>() + k * each, flags_host[k].data(), each,
-                             hipMemcpyHostToDevice));
-    }
-    {
-        const int ng = pick_groups(h, n_batches, n_tiles);
-        RETCHK(launch_precompute<MODE_HOMOGRAPHY>(h, pa, n_tiles, ng, n_batches));
-        h->last_precompute = [pa, n_tiles, ng, n_batches](coreg_handle* hh) {
-            return launch_precompute<MODE_HOMOGRAPHY>(hh, pa, n_tiles, ng, n_batches);
-        };
-    }
+    RETCHK(upload_border_flags(h, flags_host));
+    RETCHK(precompute<MODE_HOMOGRAPHY>(h, pa, n_tiles, pick_groups(h, n_batches, n_tiles), n_batches));
     h->tap_last[0] = h->tap_last[1] = h->tap_last[2] = 0;
     const double tap_box[4] = {pa.f0lo, pa.f0hi, pa.f1lo, pa.f1hi};
     trace("sweep_helioprojective: precompute launched");
@@ -746,10 +709,11 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
             &fix));
     trace("sweep_helioprojective: single-sample scan done");
     RETCHK(launch_sweep(h, sweep_mode, order, method, h->lane_params.as<double>(), h->out_index.as<long long>(), n_batches,
-                        n_tiles, lag_begin, out_dev, nullptr, &fix, 0,
+                        n_tiles, lag_begin, call.out_dev, nullptr, &fix, 0,
                         pick_pitch(h, plan, h->opt_use_lds ? lds_window_elems(h) : 0, order)));
-    return end_sweep(h, n_out, corr_out, out_on_device, out_dev);
+    return close_sweep(h, call);
 }
+
 
 int coreg_sums_size(coreg_handle* h, int64_t* n_doubles) {
     if (!h || !n_doubles) return COREG_EINVAL;
@@ -803,22 +767,9 @@ int coreg_finalize_sums(coreg_handle* h, const double* sums, int sums_on_device,
         HIPCHK(hipMemsetAsync(probe, 0, sizeof(long long), h->stream));
         for (size_t ip = 0; ip < n_pending; ++ip) {
             const coreg_handle::PendingFinalize& pf = h->pending_fin[ip];
-            FinalizeArgs f = {};
-            RETCHK(fill_refine(h, &f.refine, pf.refine.mode, pf.refine.order, pf.refine.lane_params, pf.refine.car_inv,
-                               pf.n_slots));
-            f.refine.enabled = pf.refine.enabled;
-            f.refine_count = nullptr;  // (the counters of the sweep are written by the pass that re-evaluates)
-            f.partials = h->sums.as<double>() + pf.slot_off;
-            f.n_groups = 1;
-            f.n_slots = pf.n_slots;
-            f.part_stride = h->sums_slots;
-            f.out_index = h->fin_outidx.as<long long>() + pf.slot_off;
-            f.lag_begin = pf.lag_begin;
-            f.out = out_dev;
-            f.residus = pf.residus;
-            f.n_required = (long long)h->gW * h->gH;
-            hipLaunchKernelGGL(k_finalize, dim3((unsigned)((pf.n_slots + kFinSlots - 1) / kFinSlots)),
-                               dim3(kFinSlots * kFinLanes), 0, h->stream, f);
+            // (the counters of the sweep are written by the pass that re-evaluates)
+            FinalizeArgs f;
+            RETCHK(finalize_pending(h, pf, nullptr, out_dev, &f));
             if (f.refine.enabled)
                 hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, f.refine, pf.n_slots, probe);
         }
@@ -830,27 +781,10 @@ int coreg_finalize_sums(coreg_handle* h, const double* sums, int sums_on_device,
     }
     for (size_t ip = 0; ip < n_pending && !probe_says_nothing_flagged; ++ip) {
         const coreg_handle::PendingFinalize& pf = h->pending_fin[ip];
-        FinalizeArgs f = {};
-        // flags from the REDUCED sums: the same on every rank.  (work-space pointers taken afresh: a later launch of the
-        // sweep may have grown the buffers)
-        RETCHK(fill_refine(h, &f.refine, pf.refine.mode, pf.refine.order, pf.refine.lane_params, pf.refine.car_inv,
-                           pf.n_slots));
-        f.refine.enabled = pf.refine.enabled;
+        // flags from the REDUCED sums: the same on every rank
+        FinalizeArgs f;
+        RETCHK(finalize_pending(h, pf, h->counters.as<long long>(), out_dev, &f));
         const RefineArgs rf = f.refine;
-        f.refine_count = h->counters.as<long long>();
-        f.partials = h->sums.as<double>() + pf.slot_off;
-        f.n_groups = 1;
-        f.n_slots = pf.n_slots;
-        f.part_stride = h->sums_slots;
-        f.out_index = h->fin_outidx.as<long long>() + pf.slot_off;
-        f.lag_begin = pf.lag_begin;
-        f.out = out_dev;
-        f.residus = pf.residus;
-        f.n_required = (long long)h->gW * h->gH;
-        f.sums_out = nullptr;
-        f.sums_stride = f.sums_off = 0;
-        hipLaunchKernelGGL(k_finalize, dim3((unsigned)((pf.n_slots + kFinSlots - 1) / kFinSlots)), dim3(kFinSlots * kFinLanes),
-                           0, h->stream, f);
         if (!rf.enabled) continue;
         // Ill-conditioned lag-points: every rank holds both images and re-evaluates them over the WHOLE grid (not its
         // share) with the same kernels in the same order -- identical coefficients on every rank, and equal to the

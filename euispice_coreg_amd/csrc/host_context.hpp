@@ -91,19 +91,16 @@ int context_frame_from_small(coreg_handle* h, int k) {
 
 // Plan of slots [s0, s1) of a launch whose first slot is lag index `first`: homographies and border decisions.
 void context_plan_range(const ContextState& c, const coreg_wcs2d& target4, const coreg_wcs2d& small,
-                        const coreg_lags& lags, int sem, long long first, long long s0, long long s1, int sW, int sH,
-                        double* h_ctx, double* h_sp, unsigned char* edge) {
+                        const coreg_lags& lags, const LagDims& d, int sem, long long first, long long s0, long long s1,
+                        int sW, int sH, double* h_ctx, double* h_sp, unsigned char* edge) {
     const int gW = small.naxis1, gH = small.naxis2;
     const int ne = 2 * (gW + gH);
-    const long long n5 = lags.n_crota, n4 = lags.n_cdelt2, n3 = lags.n_cdelt1, n2 = lags.n_crval2;
     const double nan = std::numeric_limits<double>::quiet_NaN();
     for (long long s = s0; s < s1; ++s) {
-        long long r = first + s;
-        const int i5 = (int)(r % n5); r /= n5;
-        const int i4 = (int)(r % n4); r /= n4;
-        const int i3 = (int)(r % n3); r /= n3;
-        const int i2 = (int)(r % n2); r /= n2;
-        const int i1 = (int)r;
+        const long long r = first + s;
+        const int i1 = (int)(r / (d.n2 * d.nc)), i2 = (int)(r / d.nc % d.n2);
+        int i3, i4, i5;
+        d.inner(r % d.nc, &i3, &i4, &i5);
         coreg_wcs2d ctx, grid, shifted;
         const int rc = context_lag_headers(target4, small, lags.crval1[i1], lags.crval2[i2], lags.cdelt1[i3],
                                            lags.cdelt2[i4], lags.crota[i5], sem, &ctx, &grid, &shifted);
@@ -143,9 +140,22 @@ void context_plan_range(const ContextState& c, const coreg_wcs2d& target4, const
     }
 }
 
+// fn(F(), S()) with F, S the element types of the frame stack and of the SPICE image (float or double)
+template <typename Fn>
+void context_types(bool frames_f32, bool small_f32, Fn fn) {
+    if (frames_f32 && small_f32) fn(float(), float());
+    else if (frames_f32) fn(float(), double());
+    else if (small_f32) fn(double(), float());
+    else fn(double(), double());
+}
+
 int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d* small, const int32_t* col_frame,
                   const coreg_lags* lags, int order, int method, int sem, int has_min, double vmin, int has_max,
                   double vmax, long long lag_begin, long long lag_end, double* corr_out, int out_on_device) {
+    // the combination range of a grid-shared sweep does not apply here: refused, and off the handle either way
+    const ComboRange combo = take_combo_range(h);
+    if (combo.begin != 0 || combo.end != 0)
+        return fail(h, COREG_EINVAL, "sweep_context: combo_begin/combo_end do not apply to this sweep");
     ContextState* c = h->ctx;
     if (!c) return fail(h, COREG_ESTATE, "sweep_context: coreg_set_context_frames has not been called");
     if (!h->small.p) return fail(h, COREG_ESTATE, "sweep_context: coreg_set_small (the SPICE image) has not been called");
@@ -154,7 +164,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
         if (const char* why = wcs_problem(*w, false)) return fail(h, COREG_EINVAL, std::string("sweep_context: ") + why);
     if (target4->proj != COREG_PROJ_TAN || small->proj != COREG_PROJ_TAN)
         return fail(h, COREG_EINVAL, "sweep_context: SPICE headers must be HPLN-TAN / HPLT-TAN");
-    if (order < 0 || order > 5) return fail(h, COREG_EINVAL, "sweep_context: order must be in 0..5");
+    RETCHK(check_order(h, order));
     // odd orders: scipy's first tap is floor(c), and every SPICE sample of this near-identity map sits within wcslib's
     // noise of an integer -- the tap set of EVERY sample would be noise-decided
     if (order & 1) return fail(h, COREG_ENOTIMPL, "sweep_context: odd reprojection orders are not implemented");
@@ -165,30 +175,16 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
     const int gW = small->naxis1, gH = small->naxis2;
     if (gW != h->sW || gH != h->sH)
         return fail(h, COREG_EINVAL, "sweep_context: the SPICE image does not have the shape of its header");
-    const coreg_lags& L = *lags;
-    const double* axes[] = {L.crval1, L.crval2, L.cdelt1, L.cdelt2, L.crota};
-    const int ns[] = {L.n_crval1, L.n_crval2, L.n_cdelt1, L.n_cdelt2, L.n_crota};
-    long long total = 1;
-    for (int k = 0; k < 5; ++k) {
-        if (ns[k] < 1 || !axes[k]) return fail(h, COREG_EINVAL, "sweep_context: empty lag axis");
-        for (int q = 0; q < ns[k]; ++q)
-            if (!std::isfinite(axes[k][q])) return fail(h, COREG_EINVAL, "sweep_context: non-finite lag");
-        total *= ns[k];
-    }
-    if (lag_begin < 0 || lag_end > total || lag_begin > lag_end)
-        return fail(h, COREG_EINVAL, "sweep_context: bad lag slice");
+    LagDims d;
+    RETCHK(check_lags(h, lags, &d, lag_begin, lag_end));
     for (int i = 0; i < gW; ++i)
         if (col_frame[i] < 0 || col_frame[i] >= c->n) return fail(h, COREG_EINVAL, "sweep_context: col_frame out of range");
     const long long n_out = lag_end - lag_begin;
     if (n_out > 0 && !corr_out) return fail(h, COREG_EINVAL, "sweep_context: corr_out is null");
     RETCHK(bind_device(h));
-    (void)collect_stats(h);
-    h->stats_pending = false;
-    std::memset(&h->stats, 0, sizeof(h->stats));
-    h->stats.small_is_f32 = h->small_f32 ? 1 : 0;
-    h->stats.n_grid_points = (long long)gW * gH;
+    h->stats_pending = false;  // (as begin_sweep: the timings of an uncollected device-output sweep are dropped)
+    reset_stats(h, (long long)gW * gH, n_out);
     h->stats.n_active_points = (long long)gW * gH;
-    h->stats.n_lags = n_out;
     // re-evaluated lag-points of THIS sweep (coreg_last_visit_counts "refined_lag_points"), summed over its launches
     HIPCHK(h->counters.reserve(8 * sizeof(long long)));
     HIPCHK(hipMemsetAsync(h->counters.p, 0, 8 * sizeof(long long), h->stream));
@@ -232,17 +228,10 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
         oi.resize((size_t)ns_);
         for (long long s = 0; s < ns_; ++s) oi[s] = b0 + s;
         // the plan on the host: a few microseconds per (frame, lag) homography and per wcslib border evaluation
-        const int nt = (int)std::max<long long>(1, std::min<long long>({16, (long long)std::thread::hardware_concurrency(),
-                                                                        (ns_ + 31) / 32}));
-        std::vector<std::thread> pool;
-        for (int t = 0; t < nt; ++t) {
-            const long long s0 = ns_ * t / nt, s1 = ns_ * (t + 1) / nt;
-            pool.emplace_back([&, s0, s1] {
-                context_plan_range(*c, *target4, *small, L, sem, b0, s0, s1, h->sW, h->sH, hc.data(), hs.data(),
-                                   ed.data());
-            });
-        }
-        for (auto& th : pool) th.join();
+        parallel_for(ns_, 16, 32, [&](long long s0, long long s1) {
+            context_plan_range(*c, *target4, *small, *lags, d, sem, b0, s0, s1, h->sW, h->sH, hc.data(), hs.data(),
+                               ed.data());
+        });
         HIPCHK(hipStreamSynchronize(h->stream));  // (the previous launch's plan buffers)
         HIPCHK(c->h_ctx.reserve(hc.size() * sizeof(double)));
         HIPCHK(c->h_sp.reserve(hs.size() * sizeof(double)));
@@ -288,14 +277,9 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
         a.partials = c->partials.as<double>();
         const dim3 grid((unsigned)n_groups, (unsigned)((ns_ + kCtxLags - 1) / kCtxLags));
         HIPCHK(hipEventRecord(c->ev_a, h->stream));
-        if (c->f32 && h->small_f32)
-            hipLaunchKernelGGL((k_context_sweep<float, float>), grid, dim3(kCtxThreads), 0, h->stream, a);
-        else if (c->f32)
-            hipLaunchKernelGGL((k_context_sweep<float, double>), grid, dim3(kCtxThreads), 0, h->stream, a);
-        else if (h->small_f32)
-            hipLaunchKernelGGL((k_context_sweep<double, float>), grid, dim3(kCtxThreads), 0, h->stream, a);
-        else
-            hipLaunchKernelGGL((k_context_sweep<double, double>), grid, dim3(kCtxThreads), 0, h->stream, a);
+        context_types(c->f32, h->small_f32, [&](auto frame, auto spice) {
+            hipLaunchKernelGGL((k_context_sweep<decltype(frame), decltype(spice)>), grid, dim3(kCtxThreads), 0, h->stream, a);
+        });
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(c->ev_b, h->stream));
         ++launches;
@@ -327,14 +311,10 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
                                h->stream, f);
             if (r.enabled) {
                 hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, r, ns_, h->counters.as<long long>());
-                if (c->f32 && h->small_f32)
-                    hipLaunchKernelGGL((k_refine_context<float, float>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
-                else if (c->f32)
-                    hipLaunchKernelGGL((k_refine_context<float, double>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
-                else if (h->small_f32)
-                    hipLaunchKernelGGL((k_refine_context<double, float>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
-                else
-                    hipLaunchKernelGGL((k_refine_context<double, double>), dim3(256), dim3(kCtxThreads), 0, h->stream, a, r);
+                context_types(c->f32, h->small_f32, [&](auto frame, auto spice) {
+                    hipLaunchKernelGGL((k_refine_context<decltype(frame), decltype(spice)>), dim3(256), dim3(kCtxThreads), 0,
+                                       h->stream, a, r);
+                });
             }
             HIPCHK(hipGetLastError());
         }

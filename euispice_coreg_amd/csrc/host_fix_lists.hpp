@@ -73,19 +73,7 @@ void wcslib_dropped_border_pixels_t(coreg_handle* h, const coreg_wcs2d& target, 
                 drop[k] = !((x >= 0.0) && (x <= wmax) && (y >= 0.0) && (y <= hmax));  // NaN -> dropped
             }
         };
-        unsigned nt = std::min<unsigned>(8, std::max(1u, std::thread::hardware_concurrency()));
-        if (cand.size() < 2048) nt = 1;
-        if (nt <= 1) {
-            work(0, cand.size());
-        } else {
-            std::vector<std::thread> th;
-            const size_t step = (cand.size() + nt - 1) / nt;
-            for (unsigned t = 0; t < nt; ++t) {
-                const size_t lo = std::min(cand.size(), (size_t)t * step), hi = std::min(cand.size(), lo + step);
-                if (hi > lo) th.emplace_back(work, lo, hi);
-            }
-            for (auto& x : th) x.join();
-        }
+        parallel_for((long long)cand.size(), cand.size() < 2048 ? 1 : 8, 0, work);
         std::vector<int> dropped;
         for (size_t k = 0; k < cand.size(); ++k)
             if (drop[k]) dropped.push_back(cand[k]);
@@ -135,19 +123,7 @@ const std::vector<unsigned char>& wcslib_tap_shift_flags_t(coreg_handle* h, cons
                 flags[(size_t)j * gw + i] = f;
             }
     };
-    unsigned nt = std::min<unsigned>(12, std::max(1u, std::thread::hardware_concurrency()));
-    if ((long long)gw * gh < 4096) nt = 1;
-    if (nt <= 1) {
-        work(0, gh);
-    } else {
-        std::vector<std::thread> th;
-        const int step = (gh + (int)nt - 1) / (int)nt;
-        for (unsigned t = 0; t < nt; ++t) {
-            const int lo = std::min(gh, (int)t * step), hi = std::min(gh, lo + step);
-            if (hi > lo) th.emplace_back(work, lo, hi);
-        }
-        for (auto& x : th) x.join();
-    }
+    parallel_for(gh, (long long)gw * gh < 4096 ? 1 : 12, 0, work);
     if (h->flags_cache.size() >= 4) h->flags_cache.clear();
     return h->flags_cache.emplace(std::move(key), std::move(flags)).first->second;
 }
@@ -167,6 +143,17 @@ int upload_border_pixels(coreg_handle* h, const std::vector<int>& pixels) {
     if (!pixels.empty())
         HIPCHK(hipMemcpyAsync(h->border_dev.p, h->pin_border.p, pixels.size() * sizeof(int), hipMemcpyHostToDevice,
                               h->stream));
+    return COREG_OK;
+}
+
+// the tap-shift flags of the noise-decided lag-points (odd orders; one grid each, BorderFix::Item::flags_off)
+int upload_border_flags(coreg_handle* h, const std::vector<std::vector<unsigned char>>& flags) {
+    if (flags.empty()) return COREG_OK;
+    const size_t each = (size_t)h->gW * h->gH;
+    HIPCHK(h->border_flags.reserve(each * flags.size()));
+    HIPCHK(hipStreamSynchronize(h->stream));  // (pageable source, rare path: blocking copies are fine)
+    for (size_t k = 0; k < flags.size(); ++k)
+        HIPCHK(hipMemcpy(h->border_flags.as<unsigned char>() + k * each, flags[k].data(), each, hipMemcpyHostToDevice));
     return COREG_OK;
 }
 
@@ -286,7 +273,7 @@ int prepare_tap_fix(coreg_handle* h, int sweep_mode, int order, const coreg_wcs2
     if (car) wfc.init(target);
     else wf.init(target);
     const int gw = h->gW;
-    auto work = [&](int s0, int s1) {
+    auto work = [&](int s0, int s1) {  // (one segment at a time: the threads share the entries about evenly)
         for (int sg = s0; sg < s1; ++sg) {
             std::sort(pixel.begin() + seg_begin[sg], pixel.begin() + seg_begin[sg + 1]);
             if (car) {
@@ -302,24 +289,7 @@ int prepare_tap_fix(coreg_handle* h, int sweep_mode, int order, const coreg_wcs2
             }
         }
     };
-    unsigned nt = std::min<unsigned>(12, std::max(1u, std::thread::hardware_concurrency()));
-    if (count < 4096 || n_seg < 2) nt = 1;
-    if (nt <= 1) {
-        work(0, n_seg);
-    } else {
-        // segments dealt in runs of about equal entry counts
-        std::vector<std::thread> th;
-        int s0 = 0;
-        for (unsigned t = 0; t < nt && s0 < n_seg; ++t) {
-            const long long want = (long long)count * (t + 1) / nt;
-            int s1 = s0 + 1;
-            while (s1 < n_seg && seg_begin[s1] < want) ++s1;
-            if (t + 1 == nt) s1 = n_seg;
-            th.emplace_back(work, s0, s1);
-            s0 = s1;
-        }
-        for (auto& x : th) x.join();
-    }
+    parallel_for(n_seg, count < 4096 ? 1 : 12, 1, work);
     HIPCHK(h->tap_seg_slot.reserve((size_t)n_seg * sizeof(int)));
     HIPCHK(h->tap_seg_begin.reserve((size_t)(n_seg + 1) * sizeof(int)));
     HIPCHK(h->tap_pixel.reserve((size_t)count * sizeof(unsigned)));

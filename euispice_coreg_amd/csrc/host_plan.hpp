@@ -2,6 +2,30 @@
 // no behaviour change): planning of a sweep: lag dimensions and checks, tile shape + lag patch, lag slots, tile groups, precompute launch, LDS pitch.
 #pragma once
 namespace {
+// ---- host fork/join ---------------------------------------------------------------------------------------------
+// fn(lo, hi) over [0, n) in chunks of `grain` items (0: one even share per thread) dealt from a shared counter, on up to
+// `max_threads` threads, this one included, and never more than there are chunks or cores.  Every caller's items are
+// independent of one another, so the split never changes a result.  Work run here must not touch the handle's caches.
+template <typename Fn>
+void parallel_for(long long n, unsigned max_threads, long long grain, Fn fn) {
+    if (n <= 0) return;
+    const long long nt_max = std::max<long long>(1, std::min(max_threads, std::thread::hardware_concurrency()));
+    if (grain <= 0) grain = (n + nt_max - 1) / nt_max;
+    const long long nt = std::min(nt_max, (n + grain - 1) / grain);
+    if (nt <= 1) {
+        fn(0ll, n);
+        return;
+    }
+    std::atomic<long long> next(0);
+    auto worker = [&] {
+        for (long long lo = next.fetch_add(grain); lo < n; lo = next.fetch_add(grain)) fn(lo, std::min(n, lo + grain));
+    };
+    std::vector<std::thread> th;
+    for (long long t = 1; t < nt; ++t) th.emplace_back(worker);
+    worker();
+    for (auto& x : th) x.join();
+}
+
 // ---- lag batching ---------------------------------------------------------------------------------------------
 struct LagDims {
     int n1, n2, n3, n4, n5;
@@ -296,18 +320,24 @@ int reserve_tiles(coreg_handle* h, int n_tiles) {
     return COREG_OK;
 }
 
-void fill_precompute_common(coreg_handle* h, PrecomputeArgs* a, int tile_w) {
+// the precompute arguments every sweep shares (the rest zero), with the tile buffers reserved for the plan's tile shape
+int setup_precompute(coreg_handle* h, const Plan& plan, int method, PrecomputeArgs* a, int* n_tiles) {
+    std::memset(a, 0, sizeof(*a));
+    a->tile_w = plan.tile_w;
+    a->tile_h = kTilePts / plan.tile_w;
+    a->tiles_x = (h->gW + a->tile_w - 1) / a->tile_w;
+    a->tiles_y = (h->gH + a->tile_h - 1) / a->tile_h;
+    *n_tiles = a->tiles_x * a->tiles_y;
+    RETCHK(reserve_tiles(h, *n_tiles));
     a->ref = h->ref.p;
     a->gw = h->gW;
     a->gh = h->gH;
-    a->tile_w = tile_w;
-    a->tile_h = kTilePts / tile_w;
-    a->tiles_x = (h->gW + a->tile_w - 1) / a->tile_w;
-    a->tiles_y = (h->gH + a->tile_h - 1) / a->tile_h;
     a->pivot_a = h->pivots.as<double>();
     a->pts = h->pts.as<Pt>();
     a->tile_count = h->tile_count.as<int>();
     a->tile_bbox = h->tile_bbox.as<double>();
+    a->residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
+    return COREG_OK;
 }
 
 // one sweep-kernel launch + finalize over n_batches * 256 slots whose parameters (SoA [np][n_slots]) and output

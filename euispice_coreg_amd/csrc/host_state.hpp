@@ -91,14 +91,8 @@ struct EventPair {
 // own pivots (launch_sweep, coreg_finalize_sums).  The device lists the arguments point to live until the next sweep.
 // (a launch's single-sample lists kept past the next launch of the same sweep: grid-shared plate-carree sweeps)
 struct KeptTapLists {
-    DevBuf seg_slot, seg_begin, pixel, xw, yw;
-    ~KeptTapLists() {
-        seg_slot.release();
-        seg_begin.release();
-        pixel.release();
-        xw.release();
-        yw.release();
-    }
+    DevBuf all;  // the five lists of TapFixArgs, one after another (launch_sweep)
+    ~KeptTapLists() { all.release(); }
 };
 struct FixLaunch {
     std::vector<BorderFixArgs> border;

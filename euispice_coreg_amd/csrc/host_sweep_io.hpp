@@ -4,6 +4,14 @@
 namespace {
 int collect_stats(coreg_handle* h);
 
+// the statistics of a new sweep call
+void reset_stats(coreg_handle* h, long long n_grid_points, long long n_lags) {
+    std::memset(&h->stats, 0, sizeof(h->stats));
+    h->stats.small_is_f32 = h->small_f32 ? 1 : 0;
+    h->stats.n_grid_points = n_grid_points;
+    h->stats.n_lags = n_lags;
+}
+
 int begin_sweep(coreg_handle* h, long long n_out, double* corr_out, int out_on_device, double** out_dev) {
     // timings of a still-uncollected device-output sweep are dropped (its events are re-recorded below): starting the
     // next sweep never waits for the previous one
@@ -28,10 +36,7 @@ int begin_sweep(coreg_handle* h, long long n_out, double* corr_out, int out_on_d
     if (!corr_out && n_out > 0) return fail(h, COREG_EINVAL, "corr_out is null");
     h->ev_sweep_used = 0;
     h->ev_pre_used = 0;
-    std::memset(&h->stats, 0, sizeof(h->stats));
-    h->stats.small_is_f32 = h->small_f32 ? 1 : 0;
-    h->stats.n_grid_points = (long long)h->gW * h->gH;
-    h->stats.n_lags = n_out;
+    reset_stats(h, (long long)h->gW * h->gH, n_out);
     if (out_on_device) {
         *out_dev = corr_out;
     } else {

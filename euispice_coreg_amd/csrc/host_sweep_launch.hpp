@@ -259,25 +259,27 @@ int launch_sweep(coreg_handle* h, int mode, int order, int method, const double*
         // a plate-carree sweep has one launch per combination and every launch lists its single samples anew in the
         // handle's buffers: this launch's lists are COPIED (round 6, closes DESIGN 9 open 3 of round 5) so that
         // coreg_finalize_sums can run the fix kernels a second time about the flagged slots' pivots, as FixLaunch lets it
-        // do for the one-launch helioprojective sweeps.  Rare path (unrotated maps, single-axis lags): blocking copies.
+        // do for the one-launch helioprojective sweeps.  Rare path (unrotated maps, single-axis lags).  The copies are
+        // ordered on the handle's stream after the kernels that read the sources; the next launch's prepare_tap_fix
+        // waits for that stream before it writes the sources again.
         if (mode == MODE_CAR && fl.have_tap) {
             auto kept = std::make_shared<KeptTapLists>();
             const size_t nseg = (size_t)fl.tap_segs, cnt = (size_t)fl.tap_count;
-            HIPCHK(kept->seg_slot.reserve(std::max<size_t>(nseg, 1) * sizeof(int)));
-            HIPCHK(kept->seg_begin.reserve((nseg + 1) * sizeof(int)));
-            HIPCHK(kept->pixel.reserve(std::max<size_t>(cnt, 1) * sizeof(unsigned)));
-            HIPCHK(kept->xw.reserve(std::max<size_t>(cnt, 1) * sizeof(double)));
-            HIPCHK(kept->yw.reserve(std::max<size_t>(cnt, 1) * sizeof(double)));
-            HIPCHK(hipMemcpy(kept->seg_slot.p, fl.tap.seg_slot, nseg * sizeof(int), hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(kept->seg_begin.p, fl.tap.seg_begin, (nseg + 1) * sizeof(int), hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(kept->pixel.p, fl.tap.pixel, cnt * sizeof(unsigned), hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(kept->xw.p, fl.tap.xw, cnt * sizeof(double), hipMemcpyDeviceToDevice));
-            HIPCHK(hipMemcpy(kept->yw.p, fl.tap.yw, cnt * sizeof(double), hipMemcpyDeviceToDevice));
-            pf.fixes.tap.seg_slot = kept->seg_slot.as<int>();
-            pf.fixes.tap.seg_begin = kept->seg_begin.as<int>();
-            pf.fixes.tap.pixel = kept->pixel.as<unsigned>();
-            pf.fixes.tap.xw = kept->xw.as<double>();
-            pf.fixes.tap.yw = kept->yw.as<double>();
+            TapFixArgs& t = pf.fixes.tap;
+            const void* src[5] = {t.xw, t.yw, t.pixel, t.seg_begin, t.seg_slot};
+            const size_t bytes[5] = {cnt * sizeof(double), cnt * sizeof(double), cnt * sizeof(unsigned),
+                                     (nseg + 1) * sizeof(int), nseg * sizeof(int)};
+            size_t off[6] = {0};
+            for (int k = 0; k < 5; ++k) off[k + 1] = off[k] + ((bytes[k] + 7) & ~(size_t)7);
+            HIPCHK(kept->all.reserve(off[5]));
+            char* all = kept->all.as<char>();
+            for (int k = 0; k < 5; ++k)
+                if (bytes[k]) HIPCHK(hipMemcpyAsync(all + off[k], src[k], bytes[k], hipMemcpyDeviceToDevice, h->stream));
+            t.xw = (const double*)(all + off[0]);
+            t.yw = (const double*)(all + off[1]);
+            t.pixel = (const unsigned*)(all + off[2]);
+            t.seg_begin = (const int*)(all + off[3]);
+            t.seg_slot = (const int*)(all + off[4]);
             pf.fixes.kept = kept;
         }
         h->pending_fin.push_back(pf);

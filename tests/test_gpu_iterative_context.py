@@ -166,3 +166,24 @@ def test_write_corrected_fits_on_the_result(tmp_path):
         d = hdr[f"CRVAL{k}"] - h4[f"CRVAL{k}"]
         assert min(lag) - 1e-6 <= d <= max(lag) + 1e-6, (k, d)
     assert hdr["NAXIS1"] == h4["NAXIS1"] and hdr["CDELT1"] == h4["CDELT1"]
+
+
+def test_a_combination_range_is_refused_and_does_not_outlive_the_context_sweep():
+    """combo_begin / combo_end (the one-shot combination range of a grid-shared sweep) do not apply to the context
+    sweep: it refuses them and takes them off the handle, so the next helioprojective sweep covers every lag."""
+    from euispice_coreg_amd import _lib
+    from tests import context_cases as CC
+    from tests import helpers as H
+    small, hs, large, hl, _ = H.scene(small_n=64, large_n=112)
+    lags = (2.0 * (np.arange(5) - 2), 2.0 * (np.arange(4) - 2), None, None, [0.0, 0.5])
+    with _lib.CoregHandle(0) as fresh:
+        want = H.gpu_helio(fresh, small, hs, large, hl, lags)
+    with _lib.CoregHandle(0) as h:
+        h.set_option("combo_begin", 0)
+        h.set_option("combo_end", 1)
+        with pytest.raises(_lib.CoregError) as e:
+            CC.gpu(h, CC.make_case(0))
+        assert e.value.code == _lib.COREG_EINVAL
+        got = H.gpu_helio(h, small, hs, large, hl, lags)
+    assert got.shape == want.shape
+    assert np.array_equal(got, want, equal_nan=True)
