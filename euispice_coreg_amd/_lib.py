@@ -159,6 +159,41 @@ def _fits_pixels(raw) -> FitsPixels:
     return FitsPixels(raw.ptr, int(raw.bitpix), 0, float(raw.bscale), float(raw.bzero))
 
 
+def _image_kind(img):
+    """(kind, stored as float32?) of an image argument, without touching its pixels.  kind: "tiled" (a CompressedImage
+    the GPU decodes), "fits" (a RawImage: the data unit as the file stores it) or "array"."""
+    if _is_tiled(img):
+        return "tiled", int(img.zbitpix) == -32
+    if _is_raw(img):
+        return "fits", int(img.bitpix) == -32
+    return "array", np.asarray(img).dtype == np.float32
+
+
+def _image_args(img, what="image"):
+    """An image argument classified once: (kind, the C arguments that describe it, what must stay alive while the
+    library reads it).  kind: "tiled" / "fits" as _image_kind, "f32" (float32 arrays -- FITS BITPIX=-32 pixels -- go up as
+    they are) or "f64" (anything else goes up as float64)."""
+    kind, f32 = _image_kind(img)
+    if kind == "tiled":
+        t, keep = _fits_tiled(img)
+        return kind, (C.byref(t),), (img, t, keep)
+    if kind == "fits":
+        px = _fits_pixels(img)
+        return kind, (C.byref(px), img.shape[0], img.shape[1]), (img, px)
+    if np.ndim(img) != 2:
+        raise ValueError(f"{what} must be 2-D")
+    a = np.ascontiguousarray(img, dtype=np.float32 if f32 else np.float64)
+    return ("f32" if f32 else "f64"), (a.ctypes.data, a.shape[0], a.shape[1]), a
+
+
+def _sweep_out(n, out_dev_ptr):
+    """Where a sweep leaves its map: (host array to return, pointer, 0), or (None, the caller's device pointer, 1)."""
+    if out_dev_ptr is None:
+        out = np.empty(n, dtype=np.float64)
+        return out, _P(out.ctypes.data), 0
+    return None, _P(int(out_dev_ptr)), 1
+
+
 # every symbol include/coreg_hip.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 _WP = C.POINTER(Wcs2d)
@@ -403,8 +438,53 @@ class Grid:
                           self.n_lat, cp, sp)
 
 
-class CoregHandle:
+class _ImageIntake:
+    """The calls that bring an image to the device, shared by CoregHandle and MultiHandle.  A subclass names its C
+    functions (`_prefix`), the attribute that holds its handle (`_ptr`) and how the kinds of image argument map onto
+    them (`_variants`: kind -> (symbol suffix, does a dtype code follow the pixel pointer?))."""
+
+    def _intake(self, stem, img, what, *tail):
+        kind, args, keep = _image_args(img, what)
+        suffix, dtype_arg = self._variants[kind]
+        if dtype_arg:
+            args = (args[0], COREG_F32 if kind == "f32" else COREG_F64) + args[1:]
+        self._chk(getattr(self._lib, self._prefix + stem + suffix)(getattr(self, self._ptr), *args, *tail))
+        return kind, keep
+
+    def set_small(self, img):
+        """Image to align.  A CompressedImage / RawImage (utils/fits_io.py) goes up as the file stores it and is decoded
+        on the GPU; float32 arrays (FITS BITPIX=-32 pixels) go up as they are; anything else as float64."""
+        # (option "async_upload": the library's upload thread reads the pixels after this call has returned -- the object
+        # that owns them is kept until the next upload replaces it; the caller must not modify them meanwhile)
+        # (the PREVIOUS buffer stays referenced until the library call has returned -- that call joins the upload job
+        # that may still be reading it -- and only then is it let go)
+        previous = getattr(self, "_small_keepalive", None)
+        kind, keep = self._intake("set_small", img, "small image")
+        if kind in ("fits", "f32"):  # (the sources the upload thread serves)
+            self._small_keepalive = keep
+            del previous
+
+    def drop_small_keepalive(self):
+        """The caller knows that the image has been read (a sweep has returned): let go of the pixel buffer held for the
+        upload thread, so that it is freed where the caller frees it and not inside the next upload."""
+        self._small_keepalive = None
+
+    def prepare_reference_carrington(self, large, hdr_large, grid: Grid, solar_r, order=2):
+        w = wcs_from_header(hdr_large, carrington=True)
+        self.reference_tag = None
+        self._intake("prepare_reference_carrington", large, "reference image", C.byref(w), C.byref(grid.c),
+                     float(solar_r), int(order))
+
+    def prepare_reference_helioprojective(self, large, hdr_large, hdr_small, order=2):
+        wl, ws = wcs_from_header(hdr_large), wcs_from_header(hdr_small)
+        self.reference_tag = None
+        self._intake("prepare_reference_helioprojective", large, "reference image", C.byref(wl), C.byref(ws), int(order))
+
+
+class CoregHandle(_ImageIntake):
     """One GPU context of libcoreg_hip (RAII over coreg_create / coreg_destroy)."""
+    _prefix, _ptr = "coreg_", "_h"
+    _variants = {"tiled": ("_tiled", False), "fits": ("_fits", False), "f32": ("_f32", False), "f64": ("", False)}
 
     def __init__(self, device=-1):
         self._lib = load_library()
@@ -448,42 +528,7 @@ class CoregHandle:
     def synchronize(self):
         self._chk(self._lib.coreg_synchronize(self._h))
 
-    # -- images
-    def set_small(self, img):
-        """Image to align.  A RawImage (utils/fits_io.py) goes up as the file stores it and is decoded on the GPU;
-        float32 arrays (FITS BITPIX=-32 pixels) go up as they are; anything else as float64."""
-        if _is_tiled(img):  # a tile-compressed image: the compressed bytes go up, the GPU decodes them
-            t, keep = _fits_tiled(img)
-            self._chk(self._lib.coreg_set_small_tiled(self._h, C.byref(t)))
-            return
-        # (option "async_upload": the library's upload thread reads the pixels after this call has returned -- the object
-        # that owns them is kept until the next upload replaces it; the caller must not modify them meanwhile)
-        # (ADVICE r05: the PREVIOUS buffer stays referenced until the library call has returned -- that call joins the
-        # upload job that may still be reading it -- and only then is it let go)
-        previous = getattr(self, "_small_keepalive", None)
-        if _is_raw(img):
-            px = _fits_pixels(img)
-            self._chk(self._lib.coreg_set_small_fits(self._h, C.byref(px), img.shape[0], img.shape[1]))
-            self._small_keepalive = (img, px)
-            del previous
-            return
-        img = np.asarray(img)
-        if img.ndim != 2:
-            raise ValueError("small image must be 2-D")
-        if img.dtype == np.float32:
-            img = np.ascontiguousarray(img)
-            self._chk(self._lib.coreg_set_small_f32(self._h, img.ctypes.data, img.shape[0], img.shape[1]))
-            self._small_keepalive = img
-            del previous
-        else:
-            img = np.ascontiguousarray(img, dtype=np.float64)
-            self._chk(self._lib.coreg_set_small(self._h, img.ctypes.data, img.shape[0], img.shape[1]))
-
-    def drop_small_keepalive(self):
-        """The caller knows that the image has been read (a sweep has returned): let go of the pixel buffer held for the
-        upload thread, so that it is freed where the caller frees it and not inside the next upload."""
-        self._small_keepalive = None
-
+    # -- images (set_small and the reference preparations: _ImageIntake)
     def threshold_small(self, vmin=None, vmax=None) -> int:
         """|v| < vmin or |v| > vmax -> NaN on the resident image to align (alignment.py:876-887); returns the number of
         finite pixels left."""
@@ -500,54 +545,7 @@ class CoregHandle:
         self.reference_tag = None
         self._chk(self._lib.coreg_set_reference_on_grid(self._h, ref.ctypes.data, dt, ref.shape[0], ref.shape[1]))
 
-    @staticmethod
-    def _reference_pixels(large):
-        """float32 arrays (FITS BITPIX=-32 pixels) go up as they are, anything else as float64."""
-        large = np.asarray(large)
-        if large.ndim != 2:
-            raise ValueError("reference image must be 2-D")
-        if large.dtype == np.float32:
-            return np.ascontiguousarray(large), True
-        return np.ascontiguousarray(large, dtype=np.float64), False
-
-    def prepare_reference_carrington(self, large, hdr_large, grid: Grid, solar_r, order=2):
-        w = wcs_from_header(hdr_large, carrington=True)
-        self.reference_tag = None
-        if _is_tiled(large):
-            t, keep = _fits_tiled(large)
-            self._chk(self._lib.coreg_prepare_reference_carrington_tiled(self._h, C.byref(t), C.byref(w), C.byref(grid.c),
-                                                                         float(solar_r), int(order)))
-            return
-        if _is_raw(large):
-            px = _fits_pixels(large)
-            self._chk(self._lib.coreg_prepare_reference_carrington_fits(
-                self._h, C.byref(px), large.shape[0], large.shape[1], C.byref(w), C.byref(grid.c), float(solar_r),
-                int(order)))
-            return
-        large, f32 = self._reference_pixels(large)
-        fn = self._lib.coreg_prepare_reference_carrington_f32 if f32 else self._lib.coreg_prepare_reference_carrington
-        self._chk(fn(self._h, large.ctypes.data, large.shape[0], large.shape[1], C.byref(w), C.byref(grid.c),
-                     float(solar_r), int(order)))
-
-    def prepare_reference_helioprojective(self, large, hdr_large, hdr_small, order=2):
-        wl, ws = wcs_from_header(hdr_large), wcs_from_header(hdr_small)
-        self.reference_tag = None
-        if _is_tiled(large):
-            t, keep = _fits_tiled(large)
-            self._chk(self._lib.coreg_prepare_reference_helioprojective_tiled(self._h, C.byref(t), C.byref(wl), C.byref(ws),
-                                                                              int(order)))
-            return
-        if _is_raw(large):
-            px = _fits_pixels(large)
-            self._chk(self._lib.coreg_prepare_reference_helioprojective_fits(
-                self._h, C.byref(px), large.shape[0], large.shape[1], C.byref(wl), C.byref(ws), int(order)))
-            return
-        large, f32 = self._reference_pixels(large)
-        fn = self._lib.coreg_prepare_reference_helioprojective_f32 if f32 else \
-            self._lib.coreg_prepare_reference_helioprojective
-        self._chk(fn(self._h, large.ctypes.data, large.shape[0], large.shape[1], C.byref(wl), C.byref(ws), int(order)))
-
-    # -- the same with the pixels already on this GPU (device pointer + shape + numpy dtype float32 / float64)
+    # -- image hand-over with the pixels already on this GPU (device pointer + shape + numpy dtype float32 / float64)
     @staticmethod
     def _dev_dtype(dtype):
         dt = np.dtype(dtype)
@@ -602,28 +600,20 @@ class CoregHandle:
                          cdelt_semantics=CDELT_INTENDED, lag_begin=0, lag_end=None, out_dev_ptr=None):
         lag_end = lags.size if lag_end is None else int(lag_end)
         w = wcs_from_header(hdr_small, carrington=True)
-        if out_dev_ptr is None:
-            out = np.empty(lag_end - lag_begin, dtype=np.float64)
-            ptr, on_dev = out.ctypes.data, 0
-        else:
-            out, ptr, on_dev = None, int(out_dev_ptr), 1
+        out, ptr, on_dev = _sweep_out(lag_end - lag_begin, out_dev_ptr)
         self._chk(self._lib.coreg_sweep_carrington(self._h, C.byref(w), C.byref(grid.c), float(solar_r),
                                                    C.byref(lags.c), int(order), int(method), int(cdelt_semantics),
-                                                   int(lag_begin), lag_end, _P(ptr), on_dev))
+                                                   int(lag_begin), lag_end, ptr, on_dev))
         return out
 
     def sweep_helioprojective(self, hdr_target, hdr_small, lags: LagSet, order=2, method=METHOD_CORRELATION,
                               cdelt_semantics=CDELT_INTENDED, lag_begin=0, lag_end=None, out_dev_ptr=None):
         lag_end = lags.size if lag_end is None else int(lag_end)
         wt, w = wcs_from_header(hdr_target), wcs_from_header(hdr_small)
-        if out_dev_ptr is None:
-            out = np.empty(lag_end - lag_begin, dtype=np.float64)
-            ptr, on_dev = out.ctypes.data, 0
-        else:
-            out, ptr, on_dev = None, int(out_dev_ptr), 1
+        out, ptr, on_dev = _sweep_out(lag_end - lag_begin, out_dev_ptr)
         self._chk(self._lib.coreg_sweep_helioprojective(self._h, C.byref(wt), C.byref(w), C.byref(lags.c), int(order),
                                                         int(method), int(cdelt_semantics), int(lag_begin), lag_end,
-                                                        _P(ptr), on_dev))
+                                                        ptr, on_dev))
         return out
 
     # -- iterative-context sweep (include/coreg_hip.h: coreg_set_context_frames, coreg_sweep_context)
@@ -635,14 +625,9 @@ class CoregHandle:
         if len(frames) != len(headers) or not frames:
             raise ValueError("one header per frame, at least one frame")
 
-        def stored(f):
-            if _is_tiled(f):
-                return np.float32 if int(f.zbitpix) == -32 else np.float64
-            if _is_raw(f):
-                return np.float32 if int(f.bitpix) == -32 else np.float64
-            return np.float32 if np.asarray(f).dtype == np.float32 else np.float64
+        kinds = [_image_kind(f) for f in frames]  # (kind, stored as float32?)
         if dtype is None:
-            dtype = np.float32 if all(stored(f) == np.float32 for f in frames) else np.float64
+            dtype = np.float32 if all(f32 for _, f32 in kinds) else np.float64
         dtype = np.dtype(dtype)
         shape = tuple(frames[0].shape)
         if any(tuple(f.shape) != shape for f in frames) or len(shape) != 2:
@@ -651,7 +636,7 @@ class CoregHandle:
         host = []
         ptrs = (_P * len(frames))()
         for k, f in enumerate(frames):
-            if _is_tiled(f) or _is_raw(f):
+            if kinds[k][0] != "array":
                 continue
             a = np.ascontiguousarray(f, dtype=dtype)
             host.append(a)
@@ -659,7 +644,7 @@ class CoregHandle:
         self._chk(self._lib.coreg_set_context_frames(self._h, len(frames), shape[0], shape[1],
                                                      COREG_F32 if dtype == np.float32 else COREG_F64, hdrs, ptrs))
         for k, f in enumerate(frames):
-            if _is_tiled(f) or _is_raw(f):
+            if kinds[k][0] != "array":
                 self.set_small(f)
                 self._chk(self._lib.coreg_context_frame_from_small(self._h, k))
         self._context_frames = (len(frames), shape, dtype)
@@ -673,15 +658,11 @@ class CoregHandle:
         cf = np.ascontiguousarray(col_frame, dtype=np.int32)
         if cf.size != w.naxis1:
             raise ValueError("col_frame needs one entry per raster column")
-        if out_dev_ptr is None:
-            out = np.empty(lag_end - lag_begin, dtype=np.float64)
-            ptr, on_dev = out.ctypes.data, 0
-        else:
-            out, ptr, on_dev = None, int(out_dev_ptr), 1
+        out, ptr, on_dev = _sweep_out(lag_end - lag_begin, out_dev_ptr)
         self._chk(self._lib.coreg_sweep_context(
             self._h, C.byref(wt), C.byref(w), cf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(lags.c), int(order),
             int(method), int(cdelt_semantics), int(vmin is not None), float(0.0 if vmin is None else vmin),
-            int(vmax is not None), float(0.0 if vmax is None else vmax), int(lag_begin), lag_end, _P(ptr), on_dev))
+            int(vmax is not None), float(0.0 if vmax is None else vmax), int(lag_begin), lag_end, ptr, on_dev))
         return out
 
     # -- multi-GPU point sharding (see include/coreg_hip.h, coreg_finalize_sums)
@@ -784,11 +765,13 @@ def multi_plan(n_crval1, n_crval2, n_inner, world, per_combo_launch=True):
     return MULTI_MODES[mode.value], gc.value, g1.value, g2.value
 
 
-class MultiHandle:
+class MultiHandle(_ImageIntake):
     """Every GPU of the node from this one process (include/coreg_hip.h, coreg_multi): one host thread + library context
     per device inside the library, full image replicas, lag-plane blocks, ONE RCCL all-gather of the per-lag
     coefficients.  Same calling surface as CoregHandle for what `hdrshift.Alignment` needs; sweeps always return the
     whole map (lag_begin / lag_end must span it)."""
+    _prefix, _ptr = "coreg_multi_", "_m"
+    _variants = {"tiled": ("_tiled", False), "fits": ("_fits", False), "f32": ("", True), "f64": ("", True)}
 
     def __init__(self, n_devices=0, device_ids=None):
         self._lib = load_library()
@@ -852,27 +835,6 @@ class MultiHandle:
         for k in range(self.size):
             self.handle(k).synchronize()
 
-    @staticmethod
-    def _pixels(img):
-        img = np.asarray(img)
-        if img.ndim != 2:
-            raise ValueError("image must be 2-D")
-        if img.dtype == np.float32:
-            return np.ascontiguousarray(img), COREG_F32
-        return np.ascontiguousarray(img, dtype=np.float64), COREG_F64
-
-    def set_small(self, img):
-        if _is_tiled(img):
-            t, keep = _fits_tiled(img)
-            self._chk(self._lib.coreg_multi_set_small_tiled(self._m, C.byref(t)))
-            return
-        if _is_raw(img):
-            px = _fits_pixels(img)
-            self._chk(self._lib.coreg_multi_set_small_fits(self._m, C.byref(px), img.shape[0], img.shape[1]))
-            return
-        img, dt = self._pixels(img)
-        self._chk(self._lib.coreg_multi_set_small(self._m, img.ctypes.data, dt, img.shape[0], img.shape[1]))
-
     def threshold_small(self, vmin=None, vmax=None) -> int:
         n = C.c_longlong(0)
         self._chk(self._lib.coreg_multi_threshold_small(self._m, int(vmin is not None), float(vmin or 0.0),
@@ -886,42 +848,6 @@ class MultiHandle:
         self.reference_tag = None
         self._chk(self._lib.coreg_multi_set_reference_on_grid(
             self._m, ref.ctypes.data, COREG_F32 if ref.dtype == np.float32 else COREG_F64, ref.shape[0], ref.shape[1]))
-
-    def prepare_reference_carrington(self, large, hdr_large, grid: Grid, solar_r, order=2):
-        w = wcs_from_header(hdr_large, carrington=True)
-        self.reference_tag = None
-        if _is_tiled(large):
-            t, keep = _fits_tiled(large)
-            self._chk(self._lib.coreg_multi_prepare_reference_carrington_tiled(self._m, C.byref(t), C.byref(w),
-                                                                               C.byref(grid.c), float(solar_r), int(order)))
-            return
-        if _is_raw(large):
-            px = _fits_pixels(large)
-            self._chk(self._lib.coreg_multi_prepare_reference_carrington_fits(
-                self._m, C.byref(px), large.shape[0], large.shape[1], C.byref(w), C.byref(grid.c), float(solar_r),
-                int(order)))
-            return
-        large, dt = self._pixels(large)
-        self._chk(self._lib.coreg_multi_prepare_reference_carrington(
-            self._m, large.ctypes.data, dt, large.shape[0], large.shape[1], C.byref(w), C.byref(grid.c), float(solar_r),
-            int(order)))
-
-    def prepare_reference_helioprojective(self, large, hdr_large, hdr_small, order=2):
-        wl, ws = wcs_from_header(hdr_large), wcs_from_header(hdr_small)
-        self.reference_tag = None
-        if _is_tiled(large):
-            t, keep = _fits_tiled(large)
-            self._chk(self._lib.coreg_multi_prepare_reference_helioprojective_tiled(self._m, C.byref(t), C.byref(wl),
-                                                                                    C.byref(ws), int(order)))
-            return
-        if _is_raw(large):
-            px = _fits_pixels(large)
-            self._chk(self._lib.coreg_multi_prepare_reference_helioprojective_fits(
-                self._m, C.byref(px), large.shape[0], large.shape[1], C.byref(wl), C.byref(ws), int(order)))
-            return
-        large, dt = self._pixels(large)
-        self._chk(self._lib.coreg_multi_prepare_reference_helioprojective(
-            self._m, large.ctypes.data, dt, large.shape[0], large.shape[1], C.byref(wl), C.byref(ws), int(order)))
 
     def _whole(self, lags, lag_begin, lag_end):
         if int(lag_begin) != 0 or (lag_end is not None and int(lag_end) != lags.size):

@@ -2,143 +2,108 @@
 // no behaviour change): C ABI: image to align, thresholds, reference on the grid / prepared on the GPU, resampling.
 #pragma once
 extern "C" {
-int coreg_set_small(coreg_handle* h, const double* img, int32_t ny, int32_t nx) {
-    if (!h) return COREG_EINVAL;
-    if (!img || ny < 1 || nx < 1 || too_many(ny, nx)) return fail(h, COREG_EINVAL, "set_small: bad image");
-    RETCHK(bind_device(h));
-    const size_t n = (size_t)ny * nx;
-    RETCHK(upload_image(h, img, n, h->small, &h->small_f32));
+// the checks every image hand-over shares: a pointer, a shape, fewer than 2^31 pixels
+static int check_image(coreg_handle* h, const void* img, int32_t ny, int32_t nx, const char* who) {
+    if (!img || ny < 1 || nx < 1 || too_many(ny, nx))
+        return fail(h, COREG_EINVAL, std::string(who) + ": bad image (null pointer, empty, or more than 2^31 - 1 pixels)");
+    return COREG_OK;
+}
+static bool is_dtype(int dtype) { return dtype == COREG_F32 || dtype == COREG_F64; }
+
+// The image to align is on the device (h->small): record shape and type and enqueue its pivot on `s`, the stream that
+// brought it; when that is the upload stream, leave the event the first reader of the image joins on (join_small).
+static int adopt_small(coreg_handle* h, int32_t ny, int32_t nx, bool f32, hipStream_t s) {
     h->sW = nx;
     h->sH = ny;
-    if (h->small_f32)
-        RETCHK(device_mean<float>(h, h->small.as<float>(), (long long)n, h->pivots.as<double>() + 1));
-    else
-        RETCHK(device_mean<double>(h, h->small.as<double>(), (long long)n, h->pivots.as<double>() + 1));
-    return COREG_OK;
+    h->small_f32 = f32;
+    HIPCHK(buffer_mean(h, h->small.p, f32, (long long)ny * nx, h->pivots.as<double>() + 1, s));
+    return end_small_upload(h, s);
+}
+
+// Image to align from any source: `src` holds ny x nx pixels of format `fmt` in memory of `kind`, or (SRC_TILED) is a
+// coreg_fits_tiled.  Pageable float32 pixels -- native, or BITPIX = -32 without scaling (what an EUI level-2 file without
+// tile compression holds) -- go up on the upload stream, so that a reference preparation called next does not wait for
+// them, and with "async_upload" from the handle's upload thread.  Everything else runs on the handle's stream.
+static int set_small_from(coreg_handle* h, const void* src, const PixFmt& fmt, SrcKind kind, int32_t ny, int32_t nx) {
+    RETCHK(check_image(h, src, ny, nx, "set_small"));
+    const size_t n = (size_t)ny * nx;
+    if (kind == SRC_HOST && (fmt.raw() ? fmt.swap_only() : fmt.f32)) {
+        trace("set_small_f32: enter");
+        RETCHK(bind_device(h));
+        HIPCHK(h->small.reserve(n * sizeof(float)));
+        hipStream_t s;
+        RETCHK(begin_small_upload(h, &s));
+        if (h->opt_async_upload && s != h->stream) {
+            // the worker issues copies, byte swap and pivot and records ev_small itself; the caller's buffer must stay
+            // valid until the next call that reads the image returns
+            h->small_f32 = true;
+            h->sW = nx;
+            h->sH = ny;
+            void* dev = h->small.p;
+            const bool swap32 = fmt.raw();
+            post_upload(h, [h, dev, src, n, swap32, s] { return upload_small_worker(h, dev, src, n, swap32, s); });
+            h->small_pending = true;  // (join_small: waits for the worker to have issued everything, then for ev_small)
+            trace("set_small_f32: handed to the upload thread");
+            return COREG_OK;
+        }
+        // through pinned staging: the caller's buffer is free again on return, the copy itself is asynchronous
+        RETCHK(staged_upload(h, h->small.p, src, n * sizeof(float), s));
+        if (fmt.raw()) fits_swap32(h->small.p, n, s);
+        RETCHK(adopt_small(h, ny, nx, true, s));
+        trace("set_small_f32: issued");
+        return COREG_OK;
+    }
+    RETCHK(bind_device(h));
+    bool f32 = true;
+    if (kind == SRC_TILED) {
+        RETCHK(decode_tiled_device(h, (const coreg_fits_tiled*)src, h->small, &f32));
+    } else if (fmt.raw()) {  // raw bytes up, decode on the GPU (an unscaled BITPIX = -32 is swapped where it lands)
+        DevBuf& dst = fmt.swap_only() ? h->small : h->up_raw;
+        HIPCHK(dst.reserve(n * fmt.elem()));
+        RETCHK(copy_in(h, dst.p, src, n * fmt.elem(), kind));
+        RETCHK(fits_decode(h, fmt, dst.p, n, h->small, &f32));
+    } else if (fmt.f32) {  // page-locked or device memory: one asynchronous copy, no staging
+        HIPCHK(h->small.reserve(n * sizeof(float)));
+        RETCHK(copy_in(h, h->small.p, src, n * sizeof(float), kind));
+    } else {
+        RETCHK(upload_image(h, (const double*)src, n, h->small, &f32, kind));
+    }
+    return adopt_small(h, ny, nx, f32, h->stream);
+}
+
+int coreg_set_small(coreg_handle* h, const double* img, int32_t ny, int32_t nx) {
+    if (!h) return COREG_EINVAL;
+    return set_small_from(h, img, PixFmt::native(false), SRC_HOST, ny, nx);
 }
 
 int coreg_set_small_f32(coreg_handle* h, const float* img, int32_t ny, int32_t nx) {
     if (!h) return COREG_EINVAL;
-    if (!img || ny < 1 || nx < 1 || too_many(ny, nx)) return fail(h, COREG_EINVAL, "set_small_f32: bad image");
-    trace("set_small_f32: enter");
-    RETCHK(bind_device(h));
-    const size_t n = (size_t)ny * nx;
-    HIPCHK(h->small.reserve(n * sizeof(float)));
-    // through pinned staging: the caller's buffer is free again on return, the copy itself is asynchronous -- and on the
-    // upload stream, so that a reference preparation called next does not wait for it
-    hipStream_t s;
-    RETCHK(begin_small_upload(h, &s));
-    if (h->opt_async_upload && s != h->stream) {
-        h->small_f32 = true;
-        h->sW = nx;
-        h->sH = ny;
-        void* dev = h->small.p;
-        post_upload(h, [h, dev, img, n, s] { return upload_small_worker(h, dev, img, n, false, s); });
-        h->small_pending = true;  // (join_small: waits for the worker to have issued everything, then for ev_small)
-        trace("set_small_f32: handed to the upload thread");
-        return COREG_OK;
-    }
-    RETCHK(staged_upload(h, h->small.p, img, n * sizeof(float), s));
-    h->small_f32 = true;
-    h->sW = nx;
-    h->sH = ny;
-    RETCHK(device_mean<float>(h, h->small.as<float>(), (long long)n, h->pivots.as<double>() + 1, s));
-    trace("set_small_f32: issued");
-    return end_small_upload(h, s);
-}
-
-// image to align from pinned host memory or from this GPU's memory (one asynchronous copy, no staging)
-static int set_small_direct(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx, SrcKind kind) {
-    if (!h) return COREG_EINVAL;
-    if (!img || ny < 1 || nx < 1 || too_many(ny, nx) || (dtype != COREG_F32 && dtype != COREG_F64))
-        return fail(h, COREG_EINVAL, "set_small: bad argument");
-    RETCHK(bind_device(h));
-    const size_t n = (size_t)ny * nx;
-    if (dtype == COREG_F32) {
-        HIPCHK(h->small.reserve(n * sizeof(float)));
-        HIPCHK(hipMemcpyAsync(h->small.p, img, n * sizeof(float),
-                              kind == SRC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-        h->small_f32 = true;
-    } else {
-        RETCHK(upload_image(h, (const double*)img, n, h->small, &h->small_f32, kind));
-    }
-    h->sW = nx;
-    h->sH = ny;
-    if (h->small_f32) return device_mean<float>(h, h->small.as<float>(), (long long)n, h->pivots.as<double>() + 1);
-    return device_mean<double>(h, h->small.as<double>(), (long long)n, h->pivots.as<double>() + 1);
+    return set_small_from(h, img, PixFmt::native(true), SRC_HOST, ny, nx);
 }
 
 int coreg_set_small_from_device(coreg_handle* h, const void* dev_img, int dtype, int32_t ny, int32_t nx) {
-    return set_small_direct(h, dev_img, dtype, ny, nx, SRC_DEVICE);
+    if (!h) return COREG_EINVAL;
+    if (!is_dtype(dtype)) return fail(h, COREG_EINVAL, "set_small: bad dtype");
+    return set_small_from(h, dev_img, PixFmt::native(dtype == COREG_F32), SRC_DEVICE, ny, nx);
 }
 
-// image to align as the FITS data unit stores it (host or page-locked memory): raw bytes up, decode on the GPU
-static int set_small_fits(coreg_handle* h, const coreg_fits_pixels* px, int32_t ny, int32_t nx, SrcKind kind) {
+// image to align as the FITS data unit stores it (host memory): raw bytes up, decode on the GPU
+int coreg_set_small_fits(coreg_handle* h, const coreg_fits_pixels* px, int32_t ny, int32_t nx) {
     if (!h) return COREG_EINVAL;
     PixFmt fmt;
     RETCHK(check_fits(h, px, &fmt));
-    if (ny < 1 || nx < 1 || too_many(ny, nx)) return fail(h, COREG_EINVAL, "set_small_fits: bad image size");
-    RETCHK(bind_device(h));
-    const size_t n = (size_t)ny * nx, eb = fmt.elem();
-    DevBuf& dst = fmt.swap_only() ? h->small : h->up_raw;
-    HIPCHK(dst.reserve(n * eb));
-    if (fmt.swap_only() && kind == SRC_HOST) {
-        // BITPIX = -32 from host memory (what an EUI level-2 file without tile compression holds): upload stream
-        hipStream_t s;
-        RETCHK(begin_small_upload(h, &s));
-        if (h->opt_async_upload && s != h->stream) {
-            h->small_f32 = true;
-            h->sW = nx;
-            h->sH = ny;
-            void* dev = dst.p;
-            const void* src = px->data;
-            post_upload(h, [h, dev, src, n, s] { return upload_small_worker(h, dev, src, n, true, s); });
-            h->small_pending = true;
-            return COREG_OK;
-        }
-        RETCHK(staged_upload(h, dst.p, px->data, n * eb, s));
-        const int nb = (int)std::min<size_t>((n + 255) / 256, 4096);
-        hipLaunchKernelGGL(k_fits_swap32, dim3(nb), dim3(256), 0, s, (unsigned int*)dst.p, (long long)n);
-        HIPCHK(hipGetLastError());
-        h->small_f32 = true;
-        h->sW = nx;
-        h->sH = ny;
-        RETCHK(device_mean<float>(h, h->small.as<float>(), (long long)n, h->pivots.as<double>() + 1, s));
-        return end_small_upload(h, s);
-    }
-    if (kind == SRC_PINNED) HIPCHK(hipMemcpyAsync(dst.p, px->data, n * eb, hipMemcpyHostToDevice, h->stream));
-    else if (kind == SRC_DEVICE) HIPCHK(hipMemcpyAsync(dst.p, px->data, n * eb, hipMemcpyDeviceToDevice, h->stream));
-    else RETCHK(staged_upload(h, dst.p, px->data, n * eb));
-    RETCHK(fits_decode(h, fmt, dst.p, n, h->small, &h->small_f32));
-    h->sW = nx;
-    h->sH = ny;
-    if (h->small_f32) return device_mean<float>(h, h->small.as<float>(), (long long)n, h->pivots.as<double>() + 1);
-    return device_mean<double>(h, h->small.as<double>(), (long long)n, h->pivots.as<double>() + 1);
-}
-
-int coreg_set_small_fits(coreg_handle* h, const coreg_fits_pixels* px, int32_t ny, int32_t nx) {
-    return set_small_fits(h, px, ny, nx, SRC_HOST);
+    return set_small_from(h, px->data, fmt, SRC_HOST, ny, nx);
 }
 
 int coreg_set_small_tiled(coreg_handle* h, const coreg_fits_tiled* t) {
     if (!h) return COREG_EINVAL;
-    RETCHK(bind_device(h));
-    RETCHK(decode_tiled_device(h, t, h->small, &h->small_f32));
-    h->sW = t->naxis1;
-    h->sH = t->naxis2;
-    const long long n = (long long)h->sW * h->sH;
-    if (h->small_f32) return device_mean<float>(h, h->small.as<float>(), n, h->pivots.as<double>() + 1);
-    return device_mean<double>(h, h->small.as<double>(), n, h->pivots.as<double>() + 1);
+    if (!t) return fail(h, COREG_EINVAL, "tiled image: null pointer");
+    return set_small_from(h, t, PixFmt(), SRC_TILED, t->naxis2, t->naxis1);
 }
 
 int coreg_decode_tiled_host(const coreg_fits_tiled* t, void* out, int dtype, int32_t* tile_status) {
     if (check_tiled(t) || !out || (dtype != COREG_F32 && dtype != COREG_F64)) return COREG_EINVAL;
     if (dtype == COREG_F32 && t->zbitpix != -32) return COREG_EINVAL;
-    static const std::vector<float> randoms = [] {
-        std::vector<float> r(coregrice::kNRandom);
-        coregrice::init_randoms(r.data());
-        return r;
-    }();
     coregrice::TileImage im;
     fill_tile_image(*t, &im);
     im.heap = (const unsigned char*)t->heap;
@@ -146,7 +111,7 @@ int coreg_decode_tiled_host(const coreg_fits_tiled* t, void* out, int dtype, int
     im.tile_nbytes = t->tile_nbytes;
     im.zscale = t->zscale;
     im.zzero = t->zzero;
-    im.randoms = randoms.data();
+    im.randoms = host_randoms();
     im.out = out;
     im.out_dtype = dtype == COREG_F32 ? coregrice::OUT_F32 : coregrice::OUT_F64;
     const int nt = t->n_tiles;
@@ -175,11 +140,6 @@ int coreg_encode_tiled_host(const void* pixels, int dtype, int ny, int nx, int t
     } else if (dtype != COREG_I32) {
         return COREG_EINVAL;  // integer images: the stored integers as int32, whatever BYTEPIX
     }
-    static const std::vector<float> randoms = [] {
-        std::vector<float> r(coregrice::kNRandom);
-        coregrice::init_randoms(r.data());
-        return r;
-    }();
     coregrice::TileImage t{};
     t.naxis1 = nx;
     t.naxis2 = ny;
@@ -195,9 +155,9 @@ int coreg_encode_tiled_host(const void* pixels, int dtype, int ny, int nx, int t
         if (is_float) {
             const int iseed = coregrice::dither_seed(t, n);
             const int e = dtype == COREG_F32
-                              ? coregrice::quantize_tile((const float*)pixels, nx, b, quantize, iseed, randoms.data(), scale,
+                              ? coregrice::quantize_tile((const float*)pixels, nx, b, quantize, iseed, host_randoms(), scale,
                                                          q.data(), &zzero[n])
-                              : coregrice::quantize_tile((const double*)pixels, nx, b, quantize, iseed, randoms.data(), scale,
+                              : coregrice::quantize_tile((const double*)pixels, nx, b, quantize, iseed, host_randoms(), scale,
                                                          q.data(), &zzero[n]);
             if (e) return COREG_EINVAL;  // (the tile's range does not fit 32-bit integers at this scale)
             zscale[n] = scale;
@@ -232,10 +192,7 @@ int coreg_threshold_small(coreg_handle* h, int has_min, double vmin, int has_max
         HIPCHK(hipGetLastError());
     }
     // pivot = mean of what is left (same value as uploading a host-thresholded image)
-    if (h->small_f32)
-        RETCHK(device_mean<float>(h, h->small.as<float>(), n, h->pivots.as<double>() + 1));
-    else
-        RETCHK(device_mean<double>(h, h->small.as<double>(), n, h->pivots.as<double>() + 1));
+    HIPCHK(buffer_mean(h, h->small.p, h->small_f32, n, h->pivots.as<double>() + 1, h->stream));
     if (n_finite) {
         long long cnt[256];
         HIPCHK(hipMemcpyAsync(cnt, h->red_cnt.p, sizeof(cnt), hipMemcpyDeviceToHost, h->stream));
@@ -248,14 +205,13 @@ int coreg_threshold_small(coreg_handle* h, int has_min, double vmin, int has_max
 }
 
 static int ref_pivot(coreg_handle* h) {
-    const long long n = (long long)h->gW * h->gH;
-    if (h->ref_dtype == COREG_F32) return device_mean<float>(h, h->ref.as<float>(), n, h->pivots.as<double>());
-    return device_mean<double>(h, h->ref.as<double>(), n, h->pivots.as<double>());
+    HIPCHK(buffer_mean(h, h->ref.p, h->ref_dtype == COREG_F32, (long long)h->gW * h->gH, h->pivots.as<double>(), h->stream));
+    return COREG_OK;
 }
 
 int coreg_set_reference_on_grid(coreg_handle* h, const void* ref, int dtype, int32_t gy, int32_t gx) {
     if (!h) return COREG_EINVAL;
-    if (!ref || gy < 1 || gx < 1 || (dtype != COREG_F32 && dtype != COREG_F64))
+    if (!ref || gy < 1 || gx < 1 || !is_dtype(dtype))
         return fail(h, COREG_EINVAL, "set_reference_on_grid: bad argument");
     RETCHK(bind_device(h));
     const size_t bytes = (size_t)gy * gx * (dtype == COREG_F32 ? 4 : 8);
@@ -322,83 +278,73 @@ static int reference_crop(coreg_handle* h, int mode, const ResampleArgs& a0, int
     return COREG_OK;
 }
 
-// rows y0 .. of a host image, columns x0 .., packed into pinned staging and sent to `dev` (contiguous, pitch = crop width)
-static int staged_upload_rect(coreg_handle* h, void* dev, const void* host, size_t elem, int W, const CropRect& c) {
-    const char* src = (const char*)host + ((size_t)c.y0 * W + c.x0) * elem;
-    if (c.w == W) return staged_upload(h, dev, src, (size_t)c.w * c.h * elem);  // whole rows: one contiguous range
-    const int k = h->pin_img_next;
-    h->pin_img_next ^= 1;
-    if (!h->ev_img[k]) HIPCHK(hipEventCreateWithFlags(&h->ev_img[k], hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(h->ev_img[k]));
-    const size_t bytes = (size_t)c.w * c.h * elem;
-    HIPCHK(h->pin_img[k].reserve(bytes));
-    parallel_copy_rows(h->pin_img[k].p, src, (size_t)c.h, (size_t)c.w * elem, (size_t)W * elem);
-    HIPCHK(hipMemcpyAsync(dev, h->pin_img[k].p, bytes, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(h->ev_img[k], h->stream));
-    return COREG_OK;
-}
-
-// the reference image's pixels: float64 from the caller (tested for float32-exactness on the GPU), the float32
-// pixels a BITPIX=-32 FITS file holds (half the PCIe bytes; the reference's float64 cast of them is exact), or the raw
-// big-endian elements of the FITS data unit (decoded on the GPU)
-// (src_on_device: the pixels are read where they are, by the resample kernel on the handle's stream -- no copy)
-static int upload_reference_source(coreg_handle* h, const void* large, size_t n, const PixFmt& fmt, bool* f32,
-                                   SrcKind kind, const void** img_dev, int W = 0, const CropRect* crop = nullptr) {
-    const bool src_f32 = fmt.f32;
+// The reference image's pixels where the resample kernel reads them (*img_dev) and whether they are float32 there.
+// Device memory is read where it is, by work enqueued on the handle's stream -- no copy.  From host memory only the
+// rectangle the resample can touch crosses PCIe (`crop`, pageable memory only), as the caller or the file stores it:
+// float32 pixels (half the PCIe bytes; the reference's float64 cast of them is exact), float64 pixels (tested for
+// float32-exactness on the GPU) or the raw big-endian elements of a FITS data unit (decoded on the GPU).
+static int upload_reference_source(coreg_handle* h, const void* large, int W, int H, const PixFmt& fmt, bool* f32,
+                                   SrcKind kind, const void** img_dev, const CropRect& crop) {
     if (kind == SRC_DEVICE) {
         if (fmt.raw()) return fail(h, COREG_ENOTIMPL, "raw FITS pixels must come from host memory");
-        *f32 = src_f32;
+        *f32 = fmt.f32;
         *img_dev = large;
         return COREG_OK;
     }
-    const bool cropped = crop && kind == SRC_HOST && (size_t)crop->w * crop->h < n;
-    const size_t nc = cropped ? (size_t)crop->w * crop->h : n;
-    if (fmt.raw()) {
-        // only the rectangle the resample can touch crosses PCIe, as stored in the file; decoded on the device
-        const size_t eb = fmt.elem();
-        DevBuf& dst = fmt.swap_only() ? h->tmp_img : h->up_raw;
-        HIPCHK(dst.reserve(nc * eb));
-        if (cropped) RETCHK(staged_upload_rect(h, dst.p, large, eb, W, *crop));
-        else if (kind == SRC_PINNED) HIPCHK(hipMemcpyAsync(dst.p, large, n * eb, hipMemcpyHostToDevice, h->stream));
-        else RETCHK(staged_upload(h, dst.p, large, n * eb));
-        RETCHK(fits_decode(h, fmt, dst.p, nc, h->tmp_img, f32));
-        *img_dev = h->tmp_img.p;
-        return COREG_OK;
-    }
-    if (cropped) {
-        // only the rectangle the resample can touch crosses PCIe
-        if (src_f32) {
-            HIPCHK(h->tmp_img.reserve(nc * sizeof(float)));
-            RETCHK(staged_upload_rect(h, h->tmp_img.p, large, sizeof(float), W, *crop));
-            *f32 = true;
-        } else {
-            HIPCHK(h->up_f64.reserve(nc * sizeof(double)));
-            RETCHK(staged_upload_rect(h, h->up_f64.p, large, sizeof(double), W, *crop));
-            RETCHK(upload_image(h, h->up_f64.as<double>(), nc, h->tmp_img, f32, SRC_DEVICE));
-        }
-        *img_dev = h->tmp_img.p;
-        return COREG_OK;
-    }
-    if (!src_f32) {
+    const size_t n = (size_t)crop.w * crop.h, eb = fmt.elem();
+    if (!fmt.raw() && !fmt.f32 && n == (size_t)W * H) {
+        // whole float64 image: upload_image stages it itself and, when the pixels are not float32-exact, makes its float64
+        // copy the image without another pass
         RETCHK(upload_image(h, (const double*)large, n, h->tmp_img, f32, kind));
-    } else {
-        HIPCHK(h->tmp_img.reserve(n * sizeof(float)));
-        if (kind == SRC_PINNED)
-            HIPCHK(hipMemcpyAsync(h->tmp_img.p, large, n * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        else
-            RETCHK(staged_upload(h, h->tmp_img.p, large, n * sizeof(float)));
-        *f32 = true;
+        *img_dev = h->tmp_img.p;
+        return COREG_OK;
     }
+    // which buffer, and how the stored elements get there: float32 pixels (after at most a byte swap) land where the
+    // resample reads them, float64 pixels and other FITS elements where their conversion expects them
+    DevBuf& dst = fmt.raw() ? (fmt.swap_only() ? h->tmp_img : h->up_raw) : (fmt.f32 ? h->tmp_img : h->up_f64);
+    HIPCHK(dst.reserve(n * eb));
+    const char* first = (const char*)large + ((size_t)crop.y0 * W + crop.x0) * eb;
+    if (kind == SRC_HOST)  // rows of the rectangle packed into pinned staging (whole rows: one contiguous range)
+        HIPCHK(stage_to_device(h, RING_CALLER, dst.p, first, (size_t)crop.h, (size_t)crop.w * eb, (size_t)W * eb, h->stream));
+    else
+        RETCHK(copy_in(h, dst.p, large, n * eb, kind));
+    // ... and what makes pixels of them
+    *f32 = true;
+    if (fmt.raw()) RETCHK(fits_decode(h, fmt, dst.p, n, h->tmp_img, f32));
+    else if (!fmt.f32) RETCHK(upload_image(h, h->up_f64.as<double>(), n, h->tmp_img, f32, SRC_DEVICE));
     *img_dev = h->tmp_img.p;
     return COREG_OK;
+}
+
+// The half every reference preparation shares, `a` holding the coordinate map of `mode` and the shapes: crop box ->
+// source pixels on the device -> once-only resample into h->ref (float32 or float64) -> pivot.
+static int prepare_reference(coreg_handle* h, const void* large, const PixFmt& fmt, SrcKind kind, int mode, int order,
+                             ResampleArgs& a, bool out_f32) {
+    CropRect crop = {0, 0, a.W, a.H};
+    if (kind == SRC_HOST) RETCHK(reference_crop(h, mode, a, order, &crop));
+    const bool carr = mode == MODE_TRANSLATE;
+    trace(carr ? "prepare_carrington: crop box known" : "prepare_helioprojective: crop box known");
+    bool f32;
+    RETCHK(upload_reference_source(h, large, a.W, a.H, fmt, &f32, kind, &a.img, crop));
+    if (crop.w != a.W || crop.h != a.H) a.crop = {crop.x0, crop.y0, crop.w};
+    HIPCHK(h->ref.reserve((size_t)a.gw * a.gh * (out_f32 ? sizeof(float) : sizeof(double))));
+    a.out = h->ref.p;
+    RETCHK(dispatch_resample(h, mode, order, f32, out_f32, a, 0));
+    h->gW = a.gw;
+    h->gH = a.gh;
+    h->ref_dtype = out_f32 ? COREG_F32 : COREG_F64;
+    RETCHK(ref_pivot(h));
+    trace(carr ? "prepare_carrington: issued" : "prepare_helioprojective: issued");
+    // no host sync: the pinned staging is guarded by stage_to_device's own wait, everything else is stream-ordered
+    return COREG_OK;  // tmp_img stays allocated: the next preparation re-uses it (hipFree would stall the device)
 }
 
 static int prepare_carrington(coreg_handle* h, const void* large, const PixFmt& fmt, int32_t ny, int32_t nx,
                               const coreg_wcs2d* hdr, const coreg_carr_grid* grid, double solar_r, int order,
                               SrcKind kind = SRC_HOST) {
     if (!h) return COREG_EINVAL;
-    if (!large || !hdr || !grid || ny < 1 || nx < 1 || too_many(ny, nx))
-        return fail(h, COREG_EINVAL, "prepare_reference: bad argument");
+    RETCHK(check_image(h, large, ny, nx, "prepare_reference"));
+    if (!hdr || !grid) return fail(h, COREG_EINVAL, "prepare_reference: null header or grid");
     RETCHK(check_order(h, order));
     RETCHK(check_wcs(h, hdr, true));
     RETCHK(check_grid(h, grid));
@@ -414,43 +360,15 @@ static int prepare_carrington(coreg_handle* h, const void* large, const PixFmt& 
     a.H = ny;
     a.gw = grid->n_lon;
     a.gh = grid->n_lat;
-    CropRect crop = {0, 0, nx, ny};
-    if (kind == SRC_HOST) RETCHK(reference_crop(h, MODE_TRANSLATE, a, order, &crop));
-    trace("prepare_carrington: crop box known");
-    bool f32;
-    const void* img_dev = nullptr;
-    RETCHK(upload_reference_source(h, large, (size_t)ny * nx, fmt, &f32, kind, &img_dev, nx, &crop));
-    a.img = img_dev;
-    if (crop.w != nx || crop.h != ny) a.crop = {crop.x0, crop.y0, crop.w};
-    HIPCHK(h->ref.reserve((size_t)a.gw * a.gh * sizeof(double)));
-    a.out = h->ref.p;
-    RETCHK(dispatch_resample(h, MODE_TRANSLATE, order, f32, false, a, 0));
-    h->gW = a.gw;
-    h->gH = a.gh;
-    h->ref_dtype = COREG_F64;
-    RETCHK(ref_pivot(h));
-    trace("prepare_carrington: issued");
-    // no host sync: the pinned staging is guarded by staged_upload's own wait, everything else is stream-ordered
-    return COREG_OK;  // tmp_img stays allocated: the next preparation re-uses it (hipFree would stall the device)
-}
-
-int coreg_prepare_reference_carrington(coreg_handle* h, const double* large, int32_t ny, int32_t nx,
-                                       const coreg_wcs2d* hdr, const coreg_carr_grid* grid, double solar_r, int order) {
-    return prepare_carrington(h, large, PixFmt::native(false), ny, nx, hdr, grid, solar_r, order);
-}
-
-int coreg_prepare_reference_carrington_f32(coreg_handle* h, const float* large, int32_t ny, int32_t nx,
-                                           const coreg_wcs2d* hdr, const coreg_carr_grid* grid, double solar_r,
-                                           int order) {
-    return prepare_carrington(h, large, PixFmt::native(true), ny, nx, hdr, grid, solar_r, order);
+    return prepare_reference(h, large, fmt, kind, MODE_TRANSLATE, order, a, false);
 }
 
 static int prepare_helioprojective(coreg_handle* h, const void* large, const PixFmt& fmt, int32_t ny, int32_t nx,
                                    const coreg_wcs2d* hdr_large, const coreg_wcs2d* hdr_small, int order,
                                    SrcKind kind = SRC_HOST) {
     if (!h) return COREG_EINVAL;
-    if (!large || !hdr_large || !hdr_small || ny < 1 || nx < 1 || too_many(ny, nx))
-        return fail(h, COREG_EINVAL, "prepare_reference: bad argument");
+    RETCHK(check_image(h, large, ny, nx, "prepare_reference"));
+    if (!hdr_large || !hdr_small) return fail(h, COREG_EINVAL, "prepare_reference: null header");
     if (hdr_small->naxis1 < 1 || hdr_small->naxis2 < 1 || too_many(hdr_small->naxis1, hdr_small->naxis2))
         return fail(h, COREG_EINVAL, "hdr_small: NAXIS1/2 missing (or more than 2^31 - 1 pixels)");
     if (hdr_large->proj != hdr_small->proj || (hdr_small->proj != COREG_PROJ_TAN && hdr_small->proj != COREG_PROJ_CAR))
@@ -473,19 +391,8 @@ static int prepare_helioprojective(coreg_handle* h, const void* large, const Pix
         const Mat3 m = mat_mul(mat_T(r_large), r_small);
         for (int i = 0; i < 3; ++i)
             for (int j = 0; j < 3; ++j) a.hom.h[3 * i + j] = (double)m.m[i][j];
-        const Affine2 fwd = car_pix_to_native(*hdr_small), inv = car_native_to_pix(*hdr_large);
-        a.car_fwd.m00 = fwd.m00;
-        a.car_fwd.m01 = fwd.m01;
-        a.car_fwd.m10 = fwd.m10;
-        a.car_fwd.m11 = fwd.m11;
-        a.car_fwd.b0 = fwd.b0;
-        a.car_fwd.b1 = fwd.b1;
-        a.car_inv.m00 = inv.m00;
-        a.car_inv.m01 = inv.m01;
-        a.car_inv.m10 = inv.m10;
-        a.car_inv.m11 = inv.m11;
-        a.car_inv.b0 = inv.b0;
-        a.car_inv.b1 = inv.b1;
+        set_affine(&a.car_fwd, car_pix_to_native(*hdr_small));
+        set_affine(&a.car_inv, car_native_to_pix(*hdr_large));
     } else {
         homography(*hdr_small, *hdr_large, a.hom.h);  // alignment.py:993: pixels of hdr_cut -> pixels of hdr_large
     }
@@ -493,21 +400,28 @@ static int prepare_helioprojective(coreg_handle* h, const void* large, const Pix
     a.H = ny;
     a.gw = hdr_small->naxis1;
     a.gh = hdr_small->naxis2;
-    CropRect crop = {0, 0, nx, ny};
-    if (kind == SRC_HOST) RETCHK(reference_crop(h, mode, a, order, &crop));
+    return prepare_reference(h, large, fmt, kind, mode, order, a, true);
+}
+
+// the compressed bytes of a tiled reference image cross PCIe, the pixels never do: decoded into h->dec_img, which the
+// preparation then reads as a device source
+static int decode_reference_tiled(coreg_handle* h, const coreg_fits_tiled* t, PixFmt* fmt) {
+    RETCHK(bind_device(h));
     bool f32;
-    const void* img_dev = nullptr;
-    RETCHK(upload_reference_source(h, large, (size_t)ny * nx, fmt, &f32, kind, &img_dev, nx, &crop));
-    a.img = img_dev;
-    if (crop.w != nx || crop.h != ny) a.crop = {crop.x0, crop.y0, crop.w};
-    HIPCHK(h->ref.reserve((size_t)a.gw * a.gh * sizeof(float)));
-    a.out = h->ref.p;
-    RETCHK(dispatch_resample(h, mode, order, f32, true, a, 0));
-    h->gW = a.gw;
-    h->gH = a.gh;
-    h->ref_dtype = COREG_F32;
-    RETCHK(ref_pivot(h));
+    RETCHK(decode_tiled_device(h, t, h->dec_img, &f32));
+    *fmt = PixFmt::native(f32);
     return COREG_OK;
+}
+
+int coreg_prepare_reference_carrington(coreg_handle* h, const double* large, int32_t ny, int32_t nx,
+                                       const coreg_wcs2d* hdr, const coreg_carr_grid* grid, double solar_r, int order) {
+    return prepare_carrington(h, large, PixFmt::native(false), ny, nx, hdr, grid, solar_r, order);
+}
+
+int coreg_prepare_reference_carrington_f32(coreg_handle* h, const float* large, int32_t ny, int32_t nx,
+                                           const coreg_wcs2d* hdr, const coreg_carr_grid* grid, double solar_r,
+                                           int order) {
+    return prepare_carrington(h, large, PixFmt::native(true), ny, nx, hdr, grid, solar_r, order);
 }
 
 int coreg_prepare_reference_helioprojective(coreg_handle* h, const double* large, int32_t ny, int32_t nx,
@@ -524,7 +438,7 @@ int coreg_prepare_reference_helioprojective_f32(coreg_handle* h, const float* la
 int coreg_prepare_reference_carrington_from_device(coreg_handle* h, const void* dev_large, int dtype, int32_t ny,
                                                    int32_t nx, const coreg_wcs2d* hdr_large,
                                                    const coreg_carr_grid* grid, double solar_r, int order) {
-    if (h && dtype != COREG_F32 && dtype != COREG_F64) return fail(h, COREG_EINVAL, "prepare_reference: bad dtype");
+    if (h && !is_dtype(dtype)) return fail(h, COREG_EINVAL, "prepare_reference: bad dtype");
     return prepare_carrington(h, dev_large, PixFmt::native(dtype == COREG_F32), ny, nx, hdr_large, grid, solar_r, order,
                               SRC_DEVICE);
 }
@@ -532,7 +446,7 @@ int coreg_prepare_reference_carrington_from_device(coreg_handle* h, const void* 
 int coreg_prepare_reference_helioprojective_from_device(coreg_handle* h, const void* dev_large, int dtype, int32_t ny,
                                                         int32_t nx, const coreg_wcs2d* hdr_large,
                                                         const coreg_wcs2d* hdr_small, int order) {
-    if (h && dtype != COREG_F32 && dtype != COREG_F64) return fail(h, COREG_EINVAL, "prepare_reference: bad dtype");
+    if (h && !is_dtype(dtype)) return fail(h, COREG_EINVAL, "prepare_reference: bad dtype");
     return prepare_helioprojective(h, dev_large, PixFmt::native(dtype == COREG_F32), ny, nx, hdr_large, hdr_small, order,
                                    SRC_DEVICE);
 }
@@ -557,21 +471,17 @@ int coreg_prepare_reference_helioprojective_fits(coreg_handle* h, const coreg_fi
 int coreg_prepare_reference_carrington_tiled(coreg_handle* h, const coreg_fits_tiled* t, const coreg_wcs2d* hdr_large,
                                              const coreg_carr_grid* grid, double solar_r, int order) {
     if (!h) return COREG_EINVAL;
-    RETCHK(bind_device(h));
-    bool f32;
-    RETCHK(decode_tiled_device(h, t, h->dec_img, &f32));  // the compressed bytes cross PCIe, the pixels never do
-    return prepare_carrington(h, h->dec_img.p, PixFmt::native(f32), t->naxis2, t->naxis1, hdr_large, grid, solar_r, order,
-                              SRC_DEVICE);
+    PixFmt fmt;
+    RETCHK(decode_reference_tiled(h, t, &fmt));
+    return prepare_carrington(h, h->dec_img.p, fmt, t->naxis2, t->naxis1, hdr_large, grid, solar_r, order, SRC_DEVICE);
 }
 
 int coreg_prepare_reference_helioprojective_tiled(coreg_handle* h, const coreg_fits_tiled* t, const coreg_wcs2d* hdr_large,
                                                   const coreg_wcs2d* hdr_small, int order) {
     if (!h) return COREG_EINVAL;
-    RETCHK(bind_device(h));
-    bool f32;
-    RETCHK(decode_tiled_device(h, t, h->dec_img, &f32));
-    return prepare_helioprojective(h, h->dec_img.p, PixFmt::native(f32), t->naxis2, t->naxis1, hdr_large, hdr_small, order,
-                                   SRC_DEVICE);
+    PixFmt fmt;
+    RETCHK(decode_reference_tiled(h, t, &fmt));
+    return prepare_helioprojective(h, h->dec_img.p, fmt, t->naxis2, t->naxis1, hdr_large, hdr_small, order, SRC_DEVICE);
 }
 
 int coreg_get_reference_on_grid(coreg_handle* h, void* out, int dtype) {

@@ -361,14 +361,8 @@ static int sweep_car(coreg_handle* h, const SweepCall& call, const coreg_wcs2d* 
         Launch L;
         L.slot_off = outidx.size();
         L.n_batches = slots.n_batches;
-        const Affine2 inv = car_native_to_pix(hc);
         std::memset(&L.inv, 0, sizeof(L.inv));
-        L.inv.m00 = inv.m00;
-        L.inv.m01 = inv.m01;
-        L.inv.m10 = inv.m10;
-        L.inv.m11 = inv.m11;
-        L.inv.b0 = inv.b0;
-        L.inv.b1 = inv.b1;
+        set_affine(&L.inv, car_native_to_pix(hc));
         L.inv.box_c = car_box_c(*hdr_target, hc, plan.tile_w);
         L.inv.pole_sep = 0.0;  // largest over the lags of this launch (below)
         L.identity = false;
@@ -443,13 +437,7 @@ static int sweep_car(coreg_handle* h, const SweepCall& call, const coreg_wcs2d* 
     PrecomputeArgs pa;
     int n_tiles;
     RETCHK(setup_precompute(h, plan, call.method, &pa, &n_tiles));
-    const Affine2 fwd = car_pix_to_native(*hdr_target);
-    pa.car_fwd.m00 = fwd.m00;
-    pa.car_fwd.m01 = fwd.m01;
-    pa.car_fwd.m10 = fwd.m10;
-    pa.car_fwd.m11 = fwd.m11;
-    pa.car_fwd.b0 = fwd.b0;
-    pa.car_fwd.b1 = fwd.b1;
+    set_affine(&pa.car_fwd, car_pix_to_native(*hdr_target));
     const double inf = std::numeric_limits<double>::infinity();
     pa.f0lo = pa.f1lo = -inf;  // no culling by position: only non-finite reference values drop out
     pa.f0hi = pa.f1hi = inf;

@@ -193,8 +193,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
     HIPCHK(c->mean.reserve(2 * sizeof(double)));
     if (!c->have_pivot) {
         const long long nf = (long long)c->n * c->W * c->H;
-        if (c->f32) RETCHK(device_mean<float>(h, c->frames.as<float>(), nf, c->mean.as<double>()));
-        else RETCHK(device_mean<double>(h, c->frames.as<double>(), nf, c->mean.as<double>()));
+        HIPCHK(buffer_mean(h, c->frames.p, c->f32, nf, c->mean.as<double>(), h->stream));
         HIPCHK(hipMemcpyAsync(&c->pivot, c->mean.p, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         if (!std::isfinite(c->pivot)) c->pivot = 0.0;

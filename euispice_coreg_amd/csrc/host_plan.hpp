@@ -92,7 +92,6 @@ static int check_wcs(coreg_handle* h, const coreg_wcs2d* w, bool carrington_tran
     return why ? fail(h, COREG_EINVAL, why) : COREG_OK;
 }
 // Pixel and grid-point counts are 32-bit in the kernels' lists (active points, border pixels, tiles): refuse what does not fit.
-static bool too_many(long long a, long long b) { return a * b > 2147483647ll; }
 static int check_grid(coreg_handle* h, const coreg_carr_grid* g) {
     if (g->n_lon >= 1 && g->n_lat >= 1 && too_many(g->n_lon, g->n_lat))
         return fail(h, COREG_EINVAL, "Carrington grid: more than 2^31 - 1 points");

@@ -57,6 +57,7 @@ enum SrcKind {
     SRC_HOST = 0,    // pageable host memory: staged through the handle's pinned buffers
     SRC_PINNED = 1,  // page-locked host memory every device can DMA from (coreg_multi's shared staging): one async copy
     SRC_DEVICE = 2,  // memory of the handle's GPU: read where it is
+    SRC_TILED = 3,   // a coreg_fits_tiled in host memory (the image to align): compressed bytes up, decoded on the GPU
 };
 
 // what the pixels of an upload are: native float32 / float64, or a FITS data unit's big-endian elements

@@ -8,6 +8,9 @@ int fail(coreg_handle* h, int code, const std::string& msg) {
     return code;
 }
 
+// images and grids are indexed with 32-bit integers on the device
+static bool too_many(long long a, long long b) { return a * b > 2147483647ll; }
+
 #define HIPCHK(expr)                                                                                  \
     do {                                                                                              \
         hipError_t _e = (expr);                                                                       \
@@ -121,19 +124,24 @@ EventPair* next_event(coreg_handle* h, std::vector<EventPair>& v, size_t& used) 
     return &v[used++];
 }
 
+// Mean of the finite values of `v` into `mean_dev`, enqueued on `s`.  Reports plain HIP codes and never writes h->err:
+// the handle's upload thread calls it too, and h->err belongs to the calling thread (callers there wrap it in HIPCHK).
 template <typename T>
-int device_mean(coreg_handle* h, const T* v, long long n, double* mean_dev, hipStream_t s = nullptr) {
+hipError_t device_mean(coreg_handle* h, const T* v, long long n, double* mean_dev, hipStream_t s) {
     const int nb = 256;
-    const bool up = s && s != h->stream;  // (the upload stream has scratch of its own)
-    if (!s) s = h->stream;
+    const bool up = s != h->stream;  // (the upload stream has scratch of its own)
     DevBuf& sum = up ? h->red_sum_up : h->red_sum;
     DevBuf& cnt = up ? h->red_cnt_up : h->red_cnt;
-    HIPCHK(sum.reserve(nb * sizeof(double)));
-    HIPCHK(cnt.reserve(nb * sizeof(long long)));
+    hipError_t e;
+    if ((e = sum.reserve(nb * sizeof(double))) != hipSuccess) return e;
+    if ((e = cnt.reserve(nb * sizeof(long long))) != hipSuccess) return e;
     hipLaunchKernelGGL((k_sum_finite<T>), dim3(nb), dim3(256), 0, s, v, n, sum.as<double>(), cnt.as<long long>());
     hipLaunchKernelGGL(k_mean_final, dim3(1), dim3(64), 0, s, sum.as<double>(), cnt.as<long long>(), nb, mean_dev);
-    HIPCHK(hipGetLastError());
-    return COREG_OK;
+    return hipGetLastError();
+}
+// the same for a buffer that holds float32 or float64 pixels
+hipError_t buffer_mean(coreg_handle* h, const void* v, bool f32, long long n, double* mean_dev, hipStream_t s) {
+    return f32 ? device_mean<float>(h, (const float*)v, n, mean_dev, s) : device_mean<double>(h, (const double*)v, n, mean_dev, s);
 }
 
 // host -> device through pinned staging: worker threads fill the staging buffer segment by segment while the DMA
@@ -294,62 +302,76 @@ void parallel_copy_rows(void* dst, const void* src, size_t rows, size_t row_byte
     CopyPool::get().copy_rows(dst, src, rows, row_bytes, src_pitch);
 }
 
-int staged_upload(coreg_handle* h, void* dev, const void* host, size_t bytes, hipStream_t stream = nullptr) {
-    if (!stream) stream = h->stream;
-    // two staging buffers used alternately, each guarded by an event recorded behind its last copy: filling the
-    // buffer for this upload overlaps the DMA (and whatever else the stream is doing) of the previous one
-    const int k = h->pin_img_next;
-    h->pin_img_next ^= 1;
-    if (!h->ev_img[k]) HIPCHK(hipEventCreateWithFlags(&h->ev_img[k], hipEventDisableTiming));
-    else HIPCHK(hipEventSynchronize(h->ev_img[k]));  // the upload that last used this buffer has left it
-    HIPCHK(h->pin_img[k].reserve(bytes));
-    char* pin = (char*)h->pin_img[k].p;
-    // segments: small at first so that the DMA engine starts early, then larger
+// The handle's two pinned staging rings.  They stay two: the upload thread's is touched from that thread and must not
+// share slots (or events) with the calling thread's.
+enum StageRing { RING_CALLER, RING_UPLOAD_THREAD };
+
+// `rows` rows of `row_bytes` bytes, `pitch` bytes apart in host memory, packed into a staging slot and sent to `dev` on
+// `stream`.  Each ring has two slots used alternately, each guarded by an event recorded behind its last copy: filling
+// the slot for this upload overlaps the DMA (and whatever else the stream is doing) of the previous one.  Plain HIP
+// codes, as device_mean (the upload thread runs this too).
+hipError_t stage_to_device(coreg_handle* h, StageRing ring, void* dev, const void* host, size_t rows, size_t row_bytes,
+                           size_t pitch, hipStream_t stream) {
+    const bool mine = ring == RING_CALLER;
+    const int k = mine ? h->pin_img_next : h->pin_small_next;
+    if (mine) h->pin_img_next ^= 1;
+    else h->pin_small_next ^= 1;
+    PinBuf& slot = mine ? h->pin_img[k] : h->pin_small[k];
+    hipEvent_t& ev = mine ? h->ev_img[k] : h->ev_pin_small[k];
+    hipError_t e = ev ? hipEventSynchronize(ev)  // the upload that last used this slot has left it
+                      : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (e != hipSuccess) return e;
+    const size_t bytes = rows * row_bytes;
+    if ((e = slot.reserve(bytes)) != hipSuccess) return e;
+    char* pin = (char*)slot.p;
+    if (pitch != row_bytes) {  // a rectangle of a wider image: packed row by row, one copy
+        parallel_copy_rows(pin, host, rows, row_bytes, pitch);
+        if ((e = hipMemcpyAsync(dev, pin, bytes, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
+        return hipEventRecord(ev, stream);
+    }
+    // one contiguous range, in segments: small at first so that the DMA engine starts early, then larger
     static const size_t seg_max = [] {
-        const char* e = std::getenv("COREG_UPLOAD_SEGMENT_MIB");
-        const int v = e ? std::atoi(e) : 0;
+        const char* env = std::getenv("COREG_UPLOAD_SEGMENT_MIB");
+        const int v = env ? std::atoi(env) : 0;
         return (size_t)(v > 0 ? v : 6) << 20;
     }();
     size_t seg = (size_t)2 << 20;
     for (size_t off = 0; off < bytes; off += seg, seg = std::min(seg * 2, seg_max)) {
         const size_t len = std::min(seg, bytes - off);
         parallel_memcpy(pin + off, (const char*)host + off, len);
-        HIPCHK(hipMemcpyAsync((char*)dev + off, pin + off, len, hipMemcpyHostToDevice, stream));
+        if ((e = hipMemcpyAsync((char*)dev + off, pin + off, len, hipMemcpyHostToDevice, stream)) != hipSuccess) return e;
     }
-    HIPCHK(hipEventRecord(h->ev_img[k], stream));
+    return hipEventRecord(ev, stream);
+}
+
+int staged_upload(coreg_handle* h, void* dev, const void* host, size_t bytes, hipStream_t stream = nullptr) {
+    HIPCHK(stage_to_device(h, RING_CALLER, dev, host, 1, bytes, bytes, stream ? stream : h->stream));
     return COREG_OK;
 }
 
-// the same on the handle's upload thread: staging and events of its own, plain HIP error codes (h->err belongs to the
+// `bytes` from a source of `kind` to `dev` on the handle's stream: pageable memory through the staging ring, page-locked
+// and device memory by one asynchronous copy
+int copy_in(coreg_handle* h, void* dev, const void* src, size_t bytes, SrcKind kind) {
+    if (kind == SRC_HOST) return staged_upload(h, dev, src, bytes);
+    HIPCHK(hipMemcpyAsync(dev, src, bytes, kind == SRC_DEVICE ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    return COREG_OK;
+}
+
+// BITPIX = -32 without scaling: the byte swap in place makes the float32 pixels
+void fits_swap32(void* dev, size_t n, hipStream_t s) {
+    const int nb = (int)std::min<size_t>((n + 255) / 256, 4096);
+    hipLaunchKernelGGL(k_fits_swap32, dim3(nb), dim3(256), 0, s, (unsigned int*)dev, (long long)n);
+}
+
+// the image to align on the handle's upload thread: staging ring of its own, plain HIP error codes (h->err belongs to the
 // calling thread), then the byte swap of a BITPIX = -32 data unit and the pivot of the image, all on stream `s`
 hipError_t upload_small_worker(coreg_handle* h, void* dev, const void* host, size_t n_elem, bool swap32, hipStream_t s) {
     trace("worker: upload begins");
     hipError_t e = hipSetDevice(h->device);
     if (e != hipSuccess) return e;
-    const size_t bytes = n_elem * 4;
-    const int k = h->pin_small_next;
-    h->pin_small_next ^= 1;
-    if (!h->ev_pin_small[k]) e = hipEventCreateWithFlags(&h->ev_pin_small[k], hipEventDisableTiming);
-    else e = hipEventSynchronize(h->ev_pin_small[k]);
-    if (e != hipSuccess) return e;
-    if ((e = h->pin_small[k].reserve(bytes)) != hipSuccess) return e;
-    char* pin = (char*)h->pin_small[k].p;
-    size_t seg = (size_t)2 << 20;
-    for (size_t off = 0; off < bytes; off += seg, seg = std::min(seg * 2, (size_t)6 << 20)) {
-        const size_t len = std::min(seg, bytes - off);
-        parallel_memcpy(pin + off, (const char*)host + off, len);
-        if ((e = hipMemcpyAsync((char*)dev + off, pin + off, len, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    }
-    if ((e = hipEventRecord(h->ev_pin_small[k], s)) != hipSuccess) return e;
-    const int nb = (int)std::min<size_t>((n_elem + 255) / 256, 4096);
-    if (swap32) hipLaunchKernelGGL(k_fits_swap32, dim3(nb), dim3(256), 0, s, (unsigned int*)dev, (long long)n_elem);
-    if ((e = h->red_sum_up.reserve(256 * sizeof(double))) != hipSuccess) return e;
-    if ((e = h->red_cnt_up.reserve(256 * sizeof(long long))) != hipSuccess) return e;
-    hipLaunchKernelGGL((k_sum_finite<float>), dim3(256), dim3(256), 0, s, (const float*)dev, (long long)n_elem,
-                       h->red_sum_up.as<double>(), h->red_cnt_up.as<long long>());
-    hipLaunchKernelGGL(k_mean_final, dim3(1), dim3(64), 0, s, h->red_sum_up.as<double>(), h->red_cnt_up.as<long long>(), 256,
-                       h->pivots.as<double>() + 1);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = stage_to_device(h, RING_UPLOAD_THREAD, dev, host, 1, n_elem * 4, n_elem * 4, s)) != hipSuccess) return e;
+    if (swap32) fits_swap32(dev, n_elem, s);
+    if ((e = buffer_mean(h, dev, true, (long long)n_elem, h->pivots.as<double>() + 1, s)) != hipSuccess) return e;
     e = hipEventRecord(h->ev_small, s);
     trace("worker: upload issued");
     return e;
@@ -364,10 +386,7 @@ int upload_image(coreg_handle* h, const double* img, size_t n, DevBuf& buf, bool
     const double* src = img;
     if (!src_on_device) {
         HIPCHK(h->up_f64.reserve(n * sizeof(double)));
-        if (kind == SRC_PINNED)
-            HIPCHK(hipMemcpyAsync(h->up_f64.p, img, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        else
-            RETCHK(staged_upload(h, h->up_f64.p, img, n * sizeof(double)));
+        RETCHK(copy_in(h, h->up_f64.p, img, n * sizeof(double), kind));
         src = h->up_f64.as<double>();
     }
     HIPCHK(hipMemsetAsync(h->up_flag.p, 0, sizeof(int), h->stream));
@@ -396,13 +415,13 @@ int upload_image(coreg_handle* h, const double* img, size_t n, DevBuf& buf, bool
 // byte swap runs in place and the image is float32.  Everything else: float64(stored) * bscale + bzero into up_f64, then
 // the same float32-exactness test and conversion a float64 upload gets (upload_image).
 int fits_decode(coreg_handle* h, const PixFmt& fmt, void* raw_dev, size_t n, DevBuf& buf, bool* is_f32) {
-    const int nb = (int)std::min<size_t>((n + 255) / 256, 4096);
     if (fmt.swap_only()) {
-        hipLaunchKernelGGL(k_fits_swap32, dim3(nb), dim3(256), 0, h->stream, (unsigned int*)raw_dev, (long long)n);
+        fits_swap32(raw_dev, n, h->stream);
         HIPCHK(hipGetLastError());
         *is_f32 = true;
         return COREG_OK;
     }
+    const int nb = (int)std::min<size_t>((n + 255) / 256, 4096);
     HIPCHK(h->up_f64.reserve(n * sizeof(double)));
     hipLaunchKernelGGL(k_fits_to_f64, dim3(nb), dim3(256), 0, h->stream, (const void*)raw_dev, fmt.bitpix,
                        fmt.scaled() ? 1 : 0, fmt.bscale, fmt.bzero, (long long)n, h->up_f64.as<double>());
@@ -493,6 +512,16 @@ const char* check_tiled(const coreg_fits_tiled* t) {
     return nullptr;
 }
 
+// cfitsio's random sequence of the subtractive dither, computed once per process
+const float* host_randoms() {
+    static const std::vector<float> r = [] {
+        std::vector<float> v(coregrice::kNRandom);
+        coregrice::init_randoms(v.data());
+        return v;
+    }();
+    return r.data();
+}
+
 void fill_tile_image(const coreg_fits_tiled& t, coregrice::TileImage* im) {
     std::memset(im, 0, sizeof(*im));
     im->naxis1 = t.naxis1;
@@ -519,6 +548,7 @@ void fill_tile_image(const coreg_fits_tiled& t, coregrice::TileImage* im) {
 // pixels go through the float32-exactness test of every float64 upload)
 int decode_tiled_device(coreg_handle* h, const coreg_fits_tiled* t, DevBuf& pix, bool* is_f32) {
     if (const char* why = check_tiled(t)) return fail(h, COREG_EINVAL, why);
+    if (too_many(t->naxis2, t->naxis1)) return fail(h, COREG_EINVAL, "tiled image: more than 2^31 - 1 pixels");
     if (!std::isfinite(t->bscale) || !std::isfinite(t->bzero)) return fail(h, COREG_EINVAL, "tiled image: BSCALE / BZERO");
     const size_t n = (size_t)t->naxis1 * t->naxis2, nt = (size_t)t->n_tiles;
     for (size_t k = 0; k < nt; ++k)
@@ -545,10 +575,8 @@ int decode_tiled_device(coreg_handle* h, const coreg_fits_tiled* t, DevBuf& pix,
     std::memcpy(tbl.data() + at, t->tile_nbytes, nt * 4);
     RETCHK(staged_upload(h, blob + heap_pad, tbl.data(), tbl_bytes));  // (copied into pinned staging before returning)
     if (!h->rice_rand.p) {
-        std::vector<float> r(coregrice::kNRandom);
-        coregrice::init_randoms(r.data());
-        HIPCHK(h->rice_rand.reserve(r.size() * sizeof(float)));
-        HIPCHK(hipMemcpy(h->rice_rand.p, r.data(), r.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIPCHK(h->rice_rand.reserve(coregrice::kNRandom * sizeof(float)));
+        HIPCHK(hipMemcpy(h->rice_rand.p, host_randoms(), coregrice::kNRandom * sizeof(float), hipMemcpyHostToDevice));
     }
     coregrice::TileImage im;
     fill_tile_image(*t, &im);
@@ -634,6 +662,16 @@ void set_carr_common(CarrDev* dev, const CarrCommon& c) {
     dev->sr = c.sr;
     dev->cdelt1 = c.cdelt1;
     dev->cdelt2 = c.cdelt2;
+}
+
+// the affine part of a launch's uniforms (MODE_CAR: pixel <-> native angles); the other members are left as they are
+void set_affine(LaunchU* u, const Affine2& a) {
+    u->m00 = a.m00;
+    u->m01 = a.m01;
+    u->m10 = a.m10;
+    u->m11 = a.m11;
+    u->b0 = a.b0;
+    u->b1 = a.b1;
 }
 
 // host mirror of kernels.hpp carr_term (tile-shape heuristics only)

@@ -696,8 +696,7 @@ int multi_sweep(coreg_multi* m, const coreg_lags* lags, double* corr_out, bool p
 // every GPU, and each device adopts (and, for raw FITS bytes, decodes) its copy.  The reference hands its workers the
 // image through ONE shared-memory copy (alignment.py:657-665).  Returns COREG_ENOTIMPL when RCCL is not in use or
 // fails (the caller then stages the whole image once in page-locked memory and every device copies it).
-int multi_set_small_shares(coreg_multi* m, const void* src, const PixFmt& fmt, const coreg_fits_pixels* px, int dtype,
-                           int32_t ny, int32_t nx) {
+int multi_set_small_shares(coreg_multi* m, const void* src, const PixFmt& fmt, int32_t ny, int32_t nx) {
     const int world = m->n;
     if (!m->use_rccl || m->comms.size() != (size_t)world) return COREG_ENOTIMPL;
     const size_t row_bytes = (size_t)nx * fmt.elem();
@@ -726,15 +725,8 @@ int multi_set_small_shares(coreg_multi* m, const void* src, const PixFmt& fmt, c
     }
     if (!multi_wait_group(m, "RCCL all-gather of the image")) return COREG_ENOTIMPL;  // (the caller stages the whole image)
     return multi_run(m, [&](int k) {
-        coreg_handle* h = m->h[k];
-        if (px) {
-            coreg_fits_pixels dev = *px;
-            dev.data = m->img[k].p;
-            RETCHK(set_small_fits(h, &dev, ny, nx, SRC_DEVICE));
-        } else {
-            RETCHK(set_small_direct(h, m->img[k].p, dtype, ny, nx, SRC_DEVICE));
-        }
-        return coreg_synchronize(h);  // the caller's host buffer and the share buffers are free again on return
+        RETCHK(set_small_from(m->h[k], m->img[k].p, fmt, SRC_DEVICE, ny, nx));
+        return coreg_synchronize(m->h[k]);  // the caller's host buffer and the share buffers are free again on return
     });
 }
 
@@ -816,6 +808,32 @@ void multi_rccl_selftest(coreg_multi* m) {
     m->comms.clear();
     m->use_rccl = false;
     m->rccl_error = why;
+}
+
+// run `fn` on device k's worker thread and translate its error into the multi-handle's
+template <typename F>
+int multi_on(coreg_multi* m, int k, F fn) {
+    int rc = COREG_OK;
+    m->w[k]->post([&] { rc = fn(m->h[k]); });
+    m->w[k]->wait();
+    return rc == COREG_OK ? rc : mfail(m, rc, coreg_last_error(m->h[k]));
+}
+
+// The image to align on every device, native pixels or a FITS data unit's raw bytes alike: shares over each device's own
+// link + one all-gather where RCCL is in use; one device: the single-device path (upload stream and all); else the whole
+// image once into the shared page-locked staging, from which every device copies it.
+int multi_set_small_from(coreg_multi* m, const void* src, const PixFmt& fmt, int32_t ny, int32_t nx) {
+    if (m->opt_image_shares) {
+        const int rc = multi_set_small_shares(m, src, fmt, ny, nx);
+        if (rc != COREG_ENOTIMPL) return rc;
+    }
+    if (m->n == 1)
+        return multi_on(m, 0, [&](coreg_handle* h) { return set_small_from(h, src, fmt, SRC_HOST, ny, nx); });
+    RETCHK(multi_stage(m, src, (size_t)ny * nx * fmt.elem()));
+    return multi_run(m, [&](int k) {
+        RETCHK(set_small_from(m->h[k], m->stage.p, fmt, SRC_PINNED, ny, nx));
+        return coreg_synchronize(m->h[k]);  // the shared staging is free again on return
+    });
 }
 
 }  // namespace
@@ -1021,26 +1039,9 @@ int coreg_multi_set_option(coreg_multi* m, const char* name, int64_t value) {
 
 int coreg_multi_set_small(coreg_multi* m, const void* img, int dtype, int32_t ny, int32_t nx) {
     if (!m) return COREG_EINVAL;
-    if (!img || ny < 1 || nx < 1 || (dtype != COREG_F32 && dtype != COREG_F64))
+    if (!img || ny < 1 || nx < 1 || too_many(ny, nx) || !is_dtype(dtype))
         return mfail(m, COREG_EINVAL, "multi_set_small: bad argument");
-    if (m->opt_image_shares) {
-        const int rc = multi_set_small_shares(m, img, PixFmt::native(dtype == COREG_F32), nullptr, dtype, ny, nx);
-        if (rc != COREG_ENOTIMPL) return rc;
-    }
-    if (m->n == 1) {
-        int rc;
-        m->w[0]->post([&] {
-            rc = dtype == COREG_F32 ? coreg_set_small_f32(m->h[0], (const float*)img, ny, nx)
-                                    : coreg_set_small(m->h[0], (const double*)img, ny, nx);
-        });
-        m->w[0]->wait();
-        return rc == COREG_OK ? rc : mfail(m, rc, coreg_last_error(m->h[0]));
-    }
-    RETCHK(multi_stage(m, img, (size_t)ny * nx * (dtype == COREG_F32 ? 4 : 8)));
-    return multi_run(m, [&](int k) {
-        RETCHK(set_small_direct(m->h[k], m->stage.p, dtype, ny, nx, SRC_PINNED));
-        return coreg_synchronize(m->h[k]);  // the shared staging is free again on return
-    });
+    return multi_set_small_from(m, img, PixFmt::native(dtype == COREG_F32), ny, nx);
 }
 
 int coreg_multi_threshold_small(coreg_multi* m, int has_min, double vmin, int has_max, double vmax, long long* n_finite) {
@@ -1059,7 +1060,7 @@ int coreg_multi_prepare_reference_carrington(coreg_multi* m, const void* large, 
                                              const coreg_wcs2d* hdr_large, const coreg_carr_grid* grid, double solar_r,
                                              int order) {
     if (!m) return COREG_EINVAL;
-    if (!large || ny < 1 || nx < 1 || (dtype != COREG_F32 && dtype != COREG_F64))
+    if (!large || ny < 1 || nx < 1 || too_many(ny, nx) || !is_dtype(dtype))
         return mfail(m, COREG_EINVAL, "multi_prepare_reference: bad argument");
     // every device sends its own copy of the rectangle the grid can touch (reference_crop: usually a few hundred KB;
     // when the grid covers most of the image, N whole uploads through the devices' own staging buffers)
@@ -1072,7 +1073,7 @@ int coreg_multi_prepare_reference_carrington(coreg_multi* m, const void* large, 
 int coreg_multi_prepare_reference_helioprojective(coreg_multi* m, const void* large, int dtype, int32_t ny, int32_t nx,
                                                   const coreg_wcs2d* hdr_large, const coreg_wcs2d* hdr_small, int order) {
     if (!m) return COREG_EINVAL;
-    if (!large || ny < 1 || nx < 1 || (dtype != COREG_F32 && dtype != COREG_F64))
+    if (!large || ny < 1 || nx < 1 || too_many(ny, nx) || !is_dtype(dtype))
         return mfail(m, COREG_EINVAL, "multi_prepare_reference: bad argument");
     return multi_run(m, [&](int k) {
         return prepare_helioprojective(m->h[k], large, PixFmt::native(dtype == COREG_F32), ny, nx, hdr_large, hdr_small,
@@ -1084,25 +1085,9 @@ int coreg_multi_prepare_reference_helioprojective(coreg_multi* m, const void* la
 int coreg_multi_set_small_fits(coreg_multi* m, const coreg_fits_pixels* px, int32_t ny, int32_t nx) {
     if (!m) return COREG_EINVAL;
     PixFmt fmt;
-    if (check_fits(nullptr, px, &fmt) != COREG_OK || ny < 1 || nx < 1)
+    if (check_fits(nullptr, px, &fmt) != COREG_OK || ny < 1 || nx < 1 || too_many(ny, nx))
         return mfail(m, COREG_EINVAL, "multi_set_small_fits: bad argument");
-    if (m->opt_image_shares) {
-        const int rc = multi_set_small_shares(m, px->data, fmt, px, 0, ny, nx);
-        if (rc != COREG_ENOTIMPL) return rc;
-    }
-    if (m->n == 1) {
-        int rc;
-        m->w[0]->post([&] { rc = coreg_set_small_fits(m->h[0], px, ny, nx); });
-        m->w[0]->wait();
-        return rc == COREG_OK ? rc : mfail(m, rc, coreg_last_error(m->h[0]));
-    }
-    RETCHK(multi_stage(m, px->data, (size_t)ny * nx * fmt.elem()));
-    coreg_fits_pixels staged = *px;
-    staged.data = m->stage.p;
-    return multi_run(m, [&](int k) {
-        RETCHK(set_small_fits(m->h[k], &staged, ny, nx, SRC_PINNED));
-        return coreg_synchronize(m->h[k]);  // the shared staging is free again on return
-    });
+    return multi_set_small_from(m, px->data, fmt, ny, nx);
 }
 
 int coreg_multi_prepare_reference_carrington_fits(coreg_multi* m, const coreg_fits_pixels* px, int32_t ny, int32_t nx,
@@ -1171,10 +1156,7 @@ int coreg_multi_sweep_helioprojective(coreg_multi* m, const coreg_wcs2d* hdr_tar
 
 int coreg_multi_last_stats(coreg_multi* m, int k, coreg_stats* out) {
     if (!m || k < 0 || k >= m->n || !out) return COREG_EINVAL;
-    int rc;
-    m->w[k]->post([&] { rc = coreg_last_stats(m->h[k], out); });
-    m->w[k]->wait();
-    return rc;
+    return multi_on(m, k, [&](coreg_handle* h) { return coreg_last_stats(h, out); });
 }
 
 }  // extern "C"
