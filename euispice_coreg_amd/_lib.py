@@ -54,6 +54,10 @@ class CarrGrid(C.Structure):
                 ("lat_cos", C.POINTER(C.c_float)), ("lat_sin", C.POINTER(C.c_float))]
 
 
+class DiffRot(C.Structure):
+    _fields_ = [("delta_t_days", C.c_double), ("c0", C.c_double), ("c1", C.c_double), ("c2", C.c_double)]
+
+
 class Stats(C.Structure):
     _fields_ = [("sweep_kernel_ms", C.c_double), ("precompute_ms", C.c_double), ("total_gpu_ms", C.c_double),
                 ("n_lags", C.c_int64), ("n_grid_points", C.c_int64), ("n_active_points", C.c_int64),
@@ -235,6 +239,8 @@ SYMBOLS = [
     ("coreg_resample_carrington", C.c_int, [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.c_int, _P]),
     ("coreg_resample_helioprojective", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
     ("coreg_resample_helioprojective_f64", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
+    ("coreg_set_reference_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
+    ("coreg_set_small_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_sweep_carrington", C.c_int,
      [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.POINTER(Lags), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P,
       C.c_int]),
@@ -255,6 +261,7 @@ SYMBOLS = [
     ("coreg_lag_homography", C.c_int,
      [_WP, _WP, C.POINTER(Lags), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_double)]),
     ("coreg_carrington_origin", C.c_int, [_WP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("coreg_diffrot_table", C.c_int, [C.POINTER(CarrGrid), C.POINTER(DiffRot), _P]),
     ("coreg_car_map", C.c_int, [_WP, _WP, C.c_int64, _P, _P, _P, _P]),
     ("coreg_wcslib_pixel_to_pixel", C.c_int, [_WP, _WP, C.c_int64, _P, _P, _P, _P, _P, _P]),
     ("coreg_car_tile_margin", C.c_int, [_WP, _WP, C.c_int32, C.c_double, C.POINTER(C.c_double)]),
@@ -297,6 +304,8 @@ SYMBOLS = [
     ("coreg_multi_prepare_reference_carrington", C.c_int,
      [_P, _P, C.c_int, C.c_int32, C.c_int32, _WP, C.POINTER(CarrGrid), C.c_double, C.c_int]),
     ("coreg_multi_prepare_reference_helioprojective", C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _WP, _WP, C.c_int]),
+    ("coreg_multi_set_reference_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
+    ("coreg_multi_set_small_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_multi_sweep_carrington", C.c_int,
      [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.POINTER(Lags), C.c_int, C.c_int, C.c_int, _P]),
     ("coreg_multi_sweep_helioprojective", C.c_int, [_P, _WP, _WP, C.POINTER(Lags), C.c_int, C.c_int, C.c_int, _P]),
@@ -468,6 +477,16 @@ class _ImageIntake:
         """The caller knows that the image has been read (a sweep has returned): let go of the pixel buffer held for the
         upload thread, so that it is freed where the caller frees it and not inside the next upload."""
         self._small_keepalive = None
+
+    def set_rotation(self, role, rot):
+        """Differential rotation of the Carrington resamples of one role: "reference" (every
+        `prepare_reference_carrington` that follows) or "small" (`sweep_carrington`, `resample_carrington`).
+        `rot`: (delta_t_days, c0, c1, c2), or None for none (the default).  It stays until set again."""
+        if role not in ("reference", "small"):
+            raise ValueError("role must be 'reference' or 'small'")
+        fn = getattr(self._lib, f"{self._prefix}set_{role}_rotation")
+        arg = None if rot is None else C.byref(DiffRot(*(float(v) for v in rot)))
+        self._chk(fn(getattr(self, self._ptr), arg))
 
     def prepare_reference_carrington(self, large, hdr_large, grid: Grid, solar_r, order=2):
         w = wcs_from_header(hdr_large, carrington=True)
@@ -1073,6 +1092,17 @@ def fit_gaussian2d(x, y, z, p0, lb, ub, jac="2-point", ftol=1e-8, xtol=1e-8, gto
     if rc != COREG_OK:
         raise CoregError(rc, "coreg_fit_gaussian2d: bad arguments (sizes, bounds, or p0 outside the bounds)")
     return popt, int(status.value), int(nfev.value)
+
+
+def diffrot_table(grid: Grid, rot):
+    """The longitude shift [degrees] that the differential rotation `rot` = (delta_t_days, c0, c1, c2) gives every row of
+    `grid` (host only): dx of utils/rectify.py:304-311."""
+    out = np.empty(grid.n_lat, dtype=np.float64)
+    r = DiffRot(*(float(v) for v in rot))
+    rc = load_library().coreg_diffrot_table(C.byref(grid.c), C.byref(r), out.ctypes.data)
+    if rc != COREG_OK:
+        raise CoregError(rc, "coreg_diffrot_table: bad grid, or a non-finite delta_t / coefficient")
+    return out
 
 
 def carrington_origin(hdr):

@@ -111,6 +111,16 @@ int coreg_carrington_origin(const coreg_wcs2d* hdr, double* x0, double* y0) {
     return COREG_OK;
 }
 
+int coreg_diffrot_table(const coreg_carr_grid* grid, const coreg_diffrot* rot, double* dx) {
+    if (!grid || !rot || !dx || grid->n_lon < 1 || grid->n_lat < 1 || !diffrot_valid(*rot)) return COREG_EINVAL;
+    CarrTables t;
+    carr_tables(*grid, 0.0, t);
+    std::vector<double> v;
+    diffrot_dx(t.sin_lat.data(), grid->n_lat, *rot, v);
+    std::copy(v.begin(), v.end(), dx);
+    return COREG_OK;
+}
+
 int coreg_nansum_planes_be(const void* cube, int32_t bitpix, int64_t n_pixels, const int64_t* plane_index, int32_t n_sel,
                            double* out) {
     if (!cube || !out || n_pixels < 0 || n_sel < 0 || (n_sel > 0 && !plane_index) || (bitpix != -32 && bitpix != -64))

@@ -353,7 +353,7 @@ static int prepare_carrington(coreg_handle* h, const void* large, const PixFmt& 
     RETCHK(bind_device_nowait(h));  // (touches neither the image to align nor its pivot: no join with the upload stream)
     ResampleArgs a;
     std::memset(&a, 0, sizeof(a));
-    RETCHK(upload_carr_tables(h, *grid, *hdr, &a.carr));
+    RETCHK(upload_carr_tables(h, *grid, *hdr, &a.carr, h->has_rot_ref ? &h->rot_ref : nullptr));
     set_carr_common(&a.carr, carr_common(*hdr, solar_r));
     carr_origin(*hdr, &a.x0, &a.y0);
     a.W = nx;
@@ -484,6 +484,20 @@ int coreg_prepare_reference_helioprojective_tiled(coreg_handle* h, const coreg_f
     return prepare_helioprojective(h, h->dec_img.p, fmt, t->naxis2, t->naxis1, hdr_large, hdr_small, order, SRC_DEVICE);
 }
 
+static int set_rotation(coreg_handle* h, const coreg_diffrot* rot, coreg_diffrot* dst, bool* has) {
+    if (!h) return COREG_EINVAL;
+    if (rot && !diffrot_valid(*rot)) return fail(h, COREG_EINVAL, "differential rotation: non-finite delta_t or coefficient");
+    *has = rot != nullptr;
+    if (rot) *dst = *rot;
+    return COREG_OK;
+}
+int coreg_set_reference_rotation(coreg_handle* h, const coreg_diffrot* rot) {
+    return h ? set_rotation(h, rot, &h->rot_ref, &h->has_rot_ref) : COREG_EINVAL;
+}
+int coreg_set_small_rotation(coreg_handle* h, const coreg_diffrot* rot) {
+    return h ? set_rotation(h, rot, &h->rot_small, &h->has_rot_small) : COREG_EINVAL;
+}
+
 int coreg_get_reference_on_grid(coreg_handle* h, void* out, int dtype) {
     if (!h) return COREG_EINVAL;
     if (!h->ref.p) return fail(h, COREG_ESTATE, "no reference image on the target grid");
@@ -507,7 +521,7 @@ int coreg_resample_carrington(coreg_handle* h, const coreg_wcs2d* hdr, const cor
     RETCHK(bind_device(h));
     ResampleArgs a;
     std::memset(&a, 0, sizeof(a));
-    RETCHK(upload_carr_tables(h, *grid, *hdr, &a.carr));
+    RETCHK(upload_carr_tables(h, *grid, *hdr, &a.carr, h->has_rot_small ? &h->rot_small : nullptr));
     set_carr_common(&a.carr, carr_common(*hdr, solar_r));
     carr_origin(*hdr, &a.x0, &a.y0);
     a.img = h->small.p;

@@ -159,7 +159,13 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
 
     CarrDev cd;
     std::memset(&cd, 0, sizeof(cd));
-    RETCHK(upload_carr_tables(h, *grid, *hdr_small, &cd));
+    RETCHK(upload_carr_tables(h, *grid, *hdr_small, &cd, h->has_rot_small ? &h->rot_small : nullptr));
+    // differential rotation: neighbouring rows slide against each other by up to this many radians of longitude, which
+    // the whole-tile bound below adds to the per-row step
+    double row_slip = 0.0;
+    for (size_t j = 1; j < h->tabs.dx.size(); ++j)
+        row_slip = std::max(row_slip, std::fabs(h->tabs.dx[j] - h->tabs.dx[j - 1]));
+    row_slip *= kDeg2Rad * (1.0 + 1e-9);
 
     // ---- plan: local geometry (heuristic inputs only) -> tile shape + lag patch
     Geometry geo;
@@ -262,6 +268,7 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
             // float32 linspace grid: the spacing is uniform to ~1e-7 relative of the coordinate
             pa.dlon = grid->n_lon > 1 ? (std::fabs(grid->lon1 - grid->lon0) / (grid->n_lon - 1) * 1.001 + 1e-4) * kDeg2Rad : 0.0;
             pa.dlat = grid->n_lat > 1 ? (std::fabs(grid->lat1 - grid->lat0) / (grid->n_lat - 1) * 1.001 + 1e-4) * kDeg2Rad : 0.0;
+            pa.dlat += row_slip;
         }
         RETCHK(precompute<MODE_TRANSLATE>(h, pa, n_tiles, pick_groups(h, L.n_batches, n_tiles), L.n_batches));
         // SoA block of this launch starts at 2 * slot_off doubles (every earlier launch contributed 2 per slot)

@@ -934,12 +934,19 @@ inline void linspace_f32(double lo, double hi, int n, std::vector<float>& out) {
 struct CarrTables {
     std::vector<double> sin_lon, cos_lon;  // [n_lon]
     std::vector<float> cos_lat, sin_lat;   // [n_lat]
+    // differential rotation (diffrot_dx): float64(lon32) [n_lon] and the per-row longitude shift [n_lat], both in degrees;
+    // dx is empty when no rotation applies (none asked for, or every entry zero)
+    std::vector<double> lon_deg, dx;
+    double l0 = 0.0;  // radians(CRLN_OBS)
 };
 inline void carr_tables(const coreg_carr_grid& g, double crln_obs, CarrTables& t) {
     std::vector<float> lon32, lat32;
     linspace_f32(g.lon0, g.lon1, g.n_lon, lon32);
     linspace_f32(g.lat0, g.lat1, g.n_lat, lat32);
     const double l0 = crln_obs * kDeg2Rad;
+    t.l0 = l0;
+    t.lon_deg.assign(lon32.begin(), lon32.end());
+    t.dx.clear();
     t.sin_lon.resize(g.n_lon);
     t.cos_lon.resize(g.n_lon);
     for (int i = 0; i < g.n_lon; ++i) {
@@ -955,6 +962,27 @@ inline void carr_tables(const coreg_carr_grid& g, double crln_obs, CarrTables& t
         t.cos_lat[j] = g.lat_cos ? g.lat_cos[j] : (float)std::cos((double)latr);
         t.sin_lat[j] = g.lat_sin ? g.lat_sin[j] : (float)std::sin((double)latr);
     }
+}
+// utils/rectify.py:304-311 (DifferentialRotationTransform.forward) for one grid row: the longitude shift in degrees that
+// the transform subtracts from every point of the row.  The reference evaluates the rate polynomial on the float32
+// latitude sines of the grid with Python-float coefficients (weak scalars: float32 arithmetic, one rounding per
+// operation, no fused multiply-add), and only the product with the float64 delta_t is float64.
+constexpr double kCarringtonRate = 14.18;  // degrees / day, rectify.py:292
+inline void diffrot_dx(const float* sin_lat, int n_lat, const coreg_diffrot& r, std::vector<double>& dx) {
+    dx.resize(n_lat);
+    const float c0 = (float)r.c0, c1 = (float)r.c1, c2 = (float)r.c2, rate = (float)kCarringtonRate;
+    for (int j = 0; j < n_lat; ++j) {
+        volatile float s2 = sin_lat[j] * sin_lat[j];
+        volatile float a = c2 * s2;
+        volatile float b = c1 + a;
+        volatile float m = s2 * b;
+        volatile float e = c0 + m;
+        volatile float chain = e - rate;
+        dx[j] = r.delta_t_days * (double)chain;
+    }
+}
+inline bool diffrot_valid(const coreg_diffrot& r) {
+    return std::isfinite(r.delta_t_days) && std::isfinite(r.c0) && std::isfinite(r.c1) && std::isfinite(r.c2);
 }
 
 // ---- iterative-context sweep (AlignementSpiceIterativeContextRaster, alignment_spice.py:357-469) ------------------

@@ -128,7 +128,10 @@ struct coreg_handle {
     // pivots[0] = mean(reference), pivots[1] = mean(small)
     DevBuf pivots, red_sum, red_cnt;
     // geometry tables (+ the host copy they were built from: re-uploaded only when the grid changes)
-    DevBuf t_sin_lon, t_cos_lon, t_cos_lat, t_sin_lat;
+    DevBuf t_sin_lon, t_cos_lon, t_cos_lat, t_sin_lat, t_lon_deg, t_dx;
+    // differential rotation per role (coreg_set_reference_rotation / coreg_set_small_rotation); has_* false: off
+    coreg_diffrot rot_ref = {}, rot_small = {};
+    bool has_rot_ref = false, has_rot_small = false;
     CarrTables tabs;
     std::vector<double> tabs_key;
     PinBuf pin_img[2];

@@ -622,26 +622,42 @@ int decode_tiled_device(coreg_handle* h, const coreg_fits_tiled* t, DevBuf& pix,
     return upload_image(h, h->up_f64.as<double>(), n, pix, is_f32, SRC_DEVICE);
 }
 
-int upload_carr_tables(coreg_handle* h, const coreg_carr_grid& g, const coreg_wcs2d& hdr, CarrDev* dev) {
+// rot: differential rotation of the image this resample is for (null: none)
+int upload_carr_tables(coreg_handle* h, const coreg_carr_grid& g, const coreg_wcs2d& hdr, CarrDev* dev,
+                       const coreg_diffrot* rot = nullptr) {
     if (g.n_lon < 1 || g.n_lat < 1) return fail(h, COREG_EINVAL, "carrington grid: n_lon/n_lat must be >= 1");
     // key: everything the tables depend on (caller-supplied latitude trig by value)
     std::vector<double> key = {g.lon0, g.lon1, (double)g.n_lon, g.lat0, g.lat1, (double)g.n_lat, hdr.crln_obs,
-                               g.lat_cos ? 1.0 : 0.0, g.lat_sin ? 1.0 : 0.0};
+                               g.lat_cos ? 1.0 : 0.0, g.lat_sin ? 1.0 : 0.0, rot ? 1.0 : 0.0};
+    if (rot) key.insert(key.end(), {rot->delta_t_days, rot->c0, rot->c1, rot->c2});
     if (g.lat_cos) key.insert(key.end(), g.lat_cos, g.lat_cos + g.n_lat);
     if (g.lat_sin) key.insert(key.end(), g.lat_sin, g.lat_sin + g.n_lat);
     if (key != h->tabs_key || !h->t_sin_lon.p) {
         CarrTables& t = h->tabs;
         carr_tables(g, hdr.crln_obs, t);
+        if (rot) {
+            diffrot_dx(t.sin_lat.data(), g.n_lat, *rot, t.dx);
+            // nothing to rotate: the per-column tables serve, as without a rotation
+            if (std::all_of(t.dx.begin(), t.dx.end(), [](double v) { return v == 0.0; })) t.dx.clear();
+        }
         HIPCHK(h->t_sin_lon.reserve(g.n_lon * sizeof(double)));
         HIPCHK(h->t_cos_lon.reserve(g.n_lon * sizeof(double)));
         HIPCHK(h->t_cos_lat.reserve(g.n_lat * sizeof(float)));
         HIPCHK(h->t_sin_lat.reserve(g.n_lat * sizeof(float)));
+        if (!t.dx.empty()) {
+            HIPCHK(h->t_lon_deg.reserve(g.n_lon * sizeof(double)));
+            HIPCHK(h->t_dx.reserve(g.n_lat * sizeof(double)));
+        }
         // h->tabs outlives the copies (it is only rebuilt after the next key mismatch, behind this same stream)
         HIPCHK(hipStreamSynchronize(h->stream));
         HIPCHK(hipMemcpyAsync(h->t_sin_lon.p, t.sin_lon.data(), g.n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->t_cos_lon.p, t.cos_lon.data(), g.n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->t_cos_lat.p, t.cos_lat.data(), g.n_lat * sizeof(float), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->t_sin_lat.p, t.sin_lat.data(), g.n_lat * sizeof(float), hipMemcpyHostToDevice, h->stream));
+        if (!t.dx.empty()) {
+            HIPCHK(hipMemcpyAsync(h->t_lon_deg.p, t.lon_deg.data(), g.n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
+            HIPCHK(hipMemcpyAsync(h->t_dx.p, t.dx.data(), g.n_lat * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        }
         HIPCHK(hipStreamSynchronize(h->stream));
         h->tabs_key.swap(key);
     }
@@ -651,6 +667,10 @@ int upload_carr_tables(coreg_handle* h, const coreg_carr_grid& g, const coreg_wc
     dev->sin_lat = h->t_sin_lat.as<float>();
     dev->n_lon = g.n_lon;
     dev->n_lat = g.n_lat;
+    const bool rotated = !h->tabs.dx.empty();
+    dev->dx = rotated ? h->t_dx.as<double>() : nullptr;
+    dev->lon_deg = rotated ? h->t_lon_deg.as<double>() : nullptr;
+    dev->l0 = h->tabs.l0;
     return COREG_OK;
 }
 

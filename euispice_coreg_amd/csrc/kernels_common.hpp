@@ -59,6 +59,10 @@ struct CarrDev {
     const float* sin_lat;   // [n_lat] float32 sin(lat)
     int n_lon, n_lat;
     double dist, cb, sb, cr, sr, cdelt1, cdelt2;
+    // differential rotation (utils/rectify.py:304-311); dx == nullptr: none, the two longitude tables above serve
+    const double* dx;       // [n_lat] longitude shift of grid row j, degrees
+    const double* lon_deg;  // [n_lon] float64(lon32), degrees
+    double l0;              // radians(CRLN_OBS)
 };
 
 struct H9 {
@@ -68,12 +72,13 @@ struct H9 {
 // ---- utils/rectify.py:340-363: the lag-independent part of SphericalTransform.forward for grid point (i, j):
 // t0 = degrees(atan(x''/z)) * 3600 / cdelt1, t1 likewise; pixel = (X0 + t0, Y0 + t1).  Operation order follows the
 // reference (no fused multiply-add) so that float64 results track NumPy's.
-__device__ __forceinline__ bool carr_term(const CarrDev& c, int i, int j, double& t0, double& t1) {
+// (sn, cs) = sin, cos of the point's longitude relative to the observer's
+__device__ __forceinline__ bool carr_project(const CarrDev& c, int j, double sn, double cs, double& t0, double& t1) {
 #pragma clang fp contract(off)
     const double cl = (double)c.cos_lat[j];
     const double y = (double)c.sin_lat[j];
-    const double x = cl * c.sin_lon[i];
-    const double z = cl * c.cos_lon[i];
+    const double x = cl * sn;
+    const double z = cl * cs;
     const double zz = z * c.cb + y * c.sb;
     const double yy = y * c.cb - z * c.sb;
     const bool vis = zz >= 0.0;  // zclip = 0
@@ -83,6 +88,19 @@ __device__ __forceinline__ bool carr_term(const CarrDev& c, int i, int j, double
     t0 = atan(xr / zd) * (180.0 / 3.14159265358979323846) * 3600.0 / c.cdelt1;
     t1 = atan(yr / zd) * (180.0 / 3.14159265358979323846) * 3600.0 / c.cdelt2;
     return vis;
+}
+// Without differential rotation the longitude depends on the column alone: per-column tables the host fills with its own
+// sin / cos.  With it, lon' = radians(float64(lon32[i]) - dx[j]) - radians(CRLN_OBS) (rectify.py:311, :342) differs from
+// point to point and its sine and cosine are taken here.  The choice is uniform over a launch.
+__device__ __forceinline__ bool carr_term(const CarrDev& c, int i, int j, double& t0, double& t1) {
+    if (!c.dx) return carr_project(c, j, c.sin_lon[i], c.cos_lon[i], t0, t1);
+    double sn, cs;
+    {
+#pragma clang fp contract(off)
+        const double lon = (c.lon_deg[i] - c.dx[j]) * (3.14159265358979323846 / 180.0) - c.l0;
+        sincos(lon, &sn, &cs);
+    }
+    return carr_project(c, j, sn, cs, t0, t1);
 }
 
 __device__ __forceinline__ void apply_h(const H9& m, double x, double y, double& ox, double& oy) {

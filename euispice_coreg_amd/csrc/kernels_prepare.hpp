@@ -245,7 +245,8 @@ __global__ void __launch_bounds__(256) k_precompute(const PrecomputeArgs a) {
         // (x'', y'', zz) components of a rotated unit vector and zd = dist - zz >= dist - 1 > 0, so moving the grid
         // point by an angle d (radians, <= |d lon| + |d lat|) moves x''/zd by at most d (1/(dist-1) + 1/(dist-1)^2) and
         // atan is 1-Lipschitz: |t - t_centre| <= lip * (|di| dlon + |dj| dlat) for every point of the tile, visible or
-        // not (host: lip_x/lip_y, dlon/dlat with their rounding margins; tile_skip = 0 when dist <= 1).
+        // not (host: lip_x/lip_y, dlon/dlat with their rounding margins; tile_skip = 0 when dist <= 1).  Under
+        // differential rotation row j's longitudes are shifted by dx[j]: dlat then includes max_j |dx[j+1] - dx[j]|.
         __shared__ int s_skip;
         const int i0 = tx * a.tile_w, j0 = ty * a.tile_h;
         const int i1 = min(i0 + a.tile_w, a.gw) - 1, j1 = min(j0 + a.tile_h, a.gh) - 1;

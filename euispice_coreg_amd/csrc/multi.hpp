@@ -1037,6 +1037,15 @@ int coreg_multi_set_option(coreg_multi* m, const char* name, int64_t value) {
     return multi_run(m, [&](int k) { return coreg_set_option(m->h[k], name, value); });
 }
 
+int coreg_multi_set_reference_rotation(coreg_multi* m, const coreg_diffrot* rot) {
+    if (!m) return COREG_EINVAL;
+    return multi_run(m, [&](int k) { return coreg_set_reference_rotation(m->h[k], rot); });
+}
+int coreg_multi_set_small_rotation(coreg_multi* m, const coreg_diffrot* rot) {
+    if (!m) return COREG_EINVAL;
+    return multi_run(m, [&](int k) { return coreg_set_small_rotation(m->h[k], rot); });
+}
+
 int coreg_multi_set_small(coreg_multi* m, const void* img, int dtype, int32_t ny, int32_t nx) {
     if (!m) return COREG_EINVAL;
     if (!img || ny < 1 || nx < 1 || too_many(ny, nx) || !is_dtype(dtype))

@@ -12,6 +12,8 @@ surface.  Differences, all deliberate and listed in DESIGN.md:
   * `counts_cpu_max`, `display_progress_bar`, `path_save_figure` are accepted and ignored.
   * CDELT lags follow the intended semantics of utils/Util.py:199-215 (quirk Q2) unless
     `cdelt_semantics="reference"`.
+  * `differential_rotation="intended"` rotates both Carrington resamples to `reference_date` (utils/diffrot.py); the
+    default "reference" ignores the date, as the reference's failed band lookup makes it do (quirk Q5).
   * inputs may be FITS paths or (data, header) pairs; astropy is optional.
   * with torch.distributed initialised (one process per GPU) the lag grid is sharded and all-gathered
     (euispice_coreg_amd/parallel.py); without it, `parallelism=True` drives every visible GPU from this one process
@@ -27,7 +29,7 @@ import warnings
 import numpy as np
 
 from .. import _lib, parallel
-from ..utils import fits_io, header as hdrutil, wcs_tan
+from ..utils import diffrot, fits_io, header as hdrutil, wcs_tan
 from .alignment_results import AlignmentResults
 
 
@@ -37,7 +39,7 @@ class Alignment:
                  lag_crota, lag_solar_r=None, small_fov_value_min=None, parallelism=False, display_progress_bar=False,
                  small_fov_value_max=None, counts_cpu_max=40, large_fov_window=-1, small_fov_window=-1,
                  path_save_figure=None, reprojection_order=2, force_crota_0=False, unit_lag="arcsec",
-                 cdelt_semantics="intended", device=None):
+                 cdelt_semantics="intended", device=None, differential_rotation="reference"):
         self.large_fov_known_pointing = large_fov_known_pointing
         self.small_fov_to_correct = small_fov_to_correct
         self.lag_crval1 = lag_crval1
@@ -68,6 +70,9 @@ class Alignment:
         if cdelt_semantics not in ("intended", "reference"):
             raise ValueError("cdelt_semantics must be 'intended' or 'reference'")
         self.cdelt_semantics = cdelt_semantics
+        if differential_rotation not in ("intended", "reference"):
+            raise ValueError("differential_rotation must be 'intended' or 'reference'")
+        self.differential_rotation = differential_rotation
         self.device = device
         # plain image HDUs of local files go to the GPU as the file stores them (COREG_RAW_FITS=0: decode on the host)
         self.raw_fits_upload = os.environ.get("COREG_RAW_FITS", "1") != "0"
@@ -126,6 +131,19 @@ class Alignment:
             return tuple(np.asarray(v, dtype=np.float64).ravel().tolist())
         return (ident, frame, bool(self.force_crota_0), int(self.order)) + tuple(flat(w) for w in what)
 
+    def _carrington_tag(self, solar_r, rot_large):
+        """Identity of the reference image on the Carrington grid: a resident one prepared for another rotation (another
+        `reference_date`, another band) is not this one."""
+        return self._reference_tag("carrington", self.lonlims, self.latlims, self.shape, solar_r, rot_large or ())
+
+    def _rotations(self):
+        """(rotation of the reference image, rotation of the image to align) of the Carrington frame, each
+        (delta_t_days, c0, c1, c2) or None (utils/diffrot.py): None, None unless differential_rotation="intended"."""
+        if self.differential_rotation != "intended" or self.coordinate_frame != "final_carrington":
+            return None, None
+        return (diffrot.rotation(self.hdr_large, self.hdr_large, self.reference_date),
+                diffrot.rotation(self.hdr_small, self.hdr_large, self.reference_date))
+
     def _set_initial_header_values(self, ang2pipi=True):
         """alignment.py:799-842."""
         h = self.hdr_small
@@ -160,7 +178,9 @@ class Alignment:
     def align_using_carrington(self, lonlims=None, latlims=None, size_deg_carrington=None, shape=None,
                                reference_date=None, method="correlation", method_carrington_reprojection="fa",
                                return_type="AlignmentResults"):
-        """alignment.py:144-261."""
+        """alignment.py:144-261.  `reference_date` (default: DATE-AVG of the reference image) acts only with
+        `differential_rotation="intended"`: each image is then rotated over (its DATE-OBS - reference_date), leap seconds
+        inside that interval ignored, at the rate of the band the reference image's WAVELNTH selects (utils/diffrot.py)."""
         self.method = method
         self.coordinate_frame = "final_carrington"
         if method_carrington_reprojection == "sunpy":
@@ -175,7 +195,8 @@ class Alignment:
                                  "DATE-AVG keyword.")
             self.reference_date = self.hdr_large["DATE-AVG"]
         else:
-            self.reference_date = reference_date  # no numerical effect on the 'fa' path (quirk Q5)
+            # no numerical effect on the 'fa' path (quirk Q5) unless differential_rotation="intended"
+            self.reference_date = reference_date
         if (lonlims is None) and (latlims is None) and (size_deg_carrington is not None):
             crln, crlt = self.hdr_small["CRLN_OBS"], self.hdr_small["CRLT_OBS"]
             self.lonlims = [crln - 0.5 * size_deg_carrington[0], crln + 0.5 * size_deg_carrington[0]]
@@ -328,6 +349,11 @@ class Alignment:
                 h.set_small_from_device(t.data_ptr(), t.shape, np.float32 if t.element_size() == 4 else np.float64)
                 h.synchronize()  # `t` may go once the copy has run
 
+        # the handle is long-lived and keeps its rotations: set on every call, None included
+        rot_large, rot_small = self._rotations()
+        if self.coordinate_frame == "final_carrington":
+            h.set_rotation("reference", rot_large)
+            h.set_rotation("small", rot_small)
         # alignment.py:844-861: thresholds, then the box to remove, then the sub-FOV re-grid
         on_device = (remove_fov_limits is None) and (fov_limits is None)
         n_finite = None
@@ -343,7 +369,7 @@ class Alignment:
             will_prepare = True
             if self.coordinate_frame == "final_carrington":
                 sr0 = 1.004 if self.lag_solar_r is None else float(np.atleast_1d(self.lag_solar_r)[0])
-                tag0 = self._reference_tag("carrington", self.lonlims, self.latlims, self.shape, sr0)
+                tag0 = self._carrington_tag(sr0, rot_large)
                 will_prepare = tag0 is None or tag0 != getattr(h, "reference_tag", None)
             use_async = (will_prepare and not use_all and not spread
                          and os.environ.get("COREG_ASYNC_UPLOAD", "0") == "1")
@@ -416,7 +442,7 @@ class Alignment:
         for kk, solar_r in enumerate(solar_rs):
             if self.coordinate_frame == "final_carrington":
                 grid = _lib.Grid(self.lonlims, self.latlims, self.shape, numpy_lat_trig=True)
-                tag = self._reference_tag("carrington", self.lonlims, self.latlims, self.shape, solar_r)
+                tag = self._carrington_tag(solar_r, rot_large)
                 if tag is None or tag != h.reference_tag:
                     prepare("carrington", self.hdr_large, grid, solar_r, self.order)
                     h.reference_tag = tag

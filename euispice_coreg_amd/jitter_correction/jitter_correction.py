@@ -20,6 +20,8 @@ Same arguments and same outputs as the reference.  What changes is how the work 
   * with torch.distributed initialised (one process per GPU) the images of a sublist are dealt round-robin to the
     ranks instead, each rank on its own device; ranks meet at a barrier between sublists.  No data-path collective.
 `parallelism`, `cpu_count` are accepted and ignored (they size the reference's process pool).
+`differential_rotation="intended"` (default "reference", as `hdrshift.Alignment`): every image, and the sublist's
+reference image, is rotated to the DATE-AVG of that reference image (each has its own time difference).
 """
 from __future__ import annotations
 
@@ -60,7 +62,7 @@ def jitter_correction_imagers(list_files_input, path_files_output, lonlims=None,
                               method_carrington_reprojection="fa", unit_lag="arcsec", path_figures=None,
                               plot_all_figures=False, parallelism=True, cpu_count=None, small_fov_value_max=None,
                               small_fov_value_min=None, alignement_method="carrington", device=None, prefetch=2,
-                              pipeline_depth=2):
+                              pipeline_depth=2, differential_rotation="reference"):
     """See the module docstring.  Returns the list of (index_to_align, index_ref, AlignmentResults) this rank
     produced, in processing order (the reference returns None; the corrected files are the product)."""
     if overlap == 0:
@@ -103,7 +105,7 @@ def jitter_correction_imagers(list_files_input, path_files_output, lonlims=None,
             method_carrington_reprojection=method_carrington_reprojection, reference_date=dates[index_ref],
             parallelism=parallelism, alignement_method=alignement_method, small_fov_value_max=small_fov_value_max,
             small_fov_value_min=small_fov_value_min, unit_lag=unit_lag, device=dev,
-            _preloaded_small=fut_image.result(), _return_corr=True, _handle_slot=slot0 + slots.id, **kwargs_carrington)
+            differential_rotation=differential_rotation, _preloaded_small=fut_image.result(), _return_corr=True, _handle_slot=slot0 + slots.id, **kwargs_carrington)
         out_path = os.path.join(path_files_output, os.path.basename(list_files_input[index_to_align]))
         # sub-lag Gaussian fit + corrected FITS in a writer thread: the GPU is already on the next image
         figure_path = None
@@ -180,14 +182,15 @@ def _align_hrieuv_with_hrieuv(large_fov_fits_path, large_fov_window, small_fov_p
                               lonlims=None, latlims=None, shape=None, unit_lag="arcsec", reference_date=None,
                               small_fov_value_max=None, small_fov_value_min=None, method_carrington_reprojection="fa",
                               alignement_method="carrington", path_output_figures=None, fov_limits=None, device=None,
-                              _preloaded_small=None, _return_corr=False, _handle_slot=0):
+                              _preloaded_small=None, _return_corr=False, _handle_slot=0,
+                              differential_rotation="reference"):
     """jitter_correction.py:177-256: one image against the sublist's reference.  `_return_corr`: hand back
     (Alignment, raw correlation array) so that the caller can build the AlignmentResults off the critical path."""
     A = Alignment(large_fov_known_pointing=large_fov_fits_path, large_fov_window=large_fov_window,
                   small_fov_to_correct=small_fov_path, small_fov_window=window_to_align, display_progress_bar=False,
                   small_fov_value_max=small_fov_value_max, small_fov_value_min=small_fov_value_min,
                   parallelism=parallelism, counts_cpu_max=cpu_count, unit_lag=unit_lag, device=device,
-                  **parameter_alignment)
+                  differential_rotation=differential_rotation, **parameter_alignment)
     A.shard_lags = False
     A._preloaded_small = _preloaded_small
     A._handle_slot = _handle_slot

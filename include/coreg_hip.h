@@ -90,6 +90,16 @@ typedef struct coreg_carr_grid {
     const float* lat_sin; /* [n_lat] or NULL */
 } coreg_carr_grid;
 
+/* Differential rotation of a Carrington resample (utils/rectify.py:282-311, DifferentialRotationTransform): grid row j is
+ * shifted in longitude by dx[j] = delta_t_days * float64(c0 + s2 (c1 + c2 s2) - 14.18) degrees, s2 = sin(lat_j)^2 and
+ * the polynomial in float32 on the grid's float32 latitude sines, before the sphere -> detector map.
+ * delta_t_days = DATE-OBS of the image being resampled - reference date; (c0, c1, c2) = the band's rotation rate
+ * in degrees / day. */
+typedef struct coreg_diffrot {
+    double delta_t_days;
+    double c0, c1, c2;
+} coreg_diffrot;
+
 typedef struct coreg_stats {
     double sweep_kernel_ms;    /* sum of HIP-event durations of the sweep kernel launches of the last sweep   */
     double precompute_ms;      /* grid-coordinate / compaction kernels of the last sweep                      */
@@ -260,6 +270,15 @@ int coreg_resample_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_targe
 int coreg_resample_helioprojective_f64(coreg_handle* h, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr,
                                        int order, double* out);
 
+/* Differential rotation, one setting per role; it stays until set again.  NULL = off (the default): the reference's
+ * behaviour, whose rate lookup never matches and whose coefficients cancel (quirk Q5).  A rotation whose every dx[j] is
+ * zero (delta_t_days 0, or coefficients (14.18, 0, 0)) runs the same code as off.
+ *   coreg_set_reference_rotation   the reference image: every coreg_prepare_reference_carrington* call that follows
+ *   coreg_set_small_rotation       the image to align: coreg_sweep_carrington and coreg_resample_carrington
+ * COREG_EINVAL for a non-finite member. */
+int coreg_set_reference_rotation(coreg_handle* h, const coreg_diffrot* rot);
+int coreg_set_small_rotation(coreg_handle* h, const coreg_diffrot* rot);
+
 /* The sweep: replaces the per-lag loop alignment.py:470-578 + :613-797 for one lag_solar_r value.
  * hdr_small is the UNSHIFTED header of the image to align; its CRVAL/CDELT/CROTA are the *_ref values of
  * alignment.py:799-814 and each lag-point applies _shift_header (alignment.py:401-468) to it.
@@ -424,6 +443,9 @@ int coreg_lag_homography(const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_s
 int coreg_wcslib_pixel_to_pixel(const coreg_wcs2d* from, const coreg_wcs2d* to, int64_t n, const double* px,
                                 const double* py, double* ox, double* oy, double* lng, double* lat);
 int coreg_carrington_origin(const coreg_wcs2d* hdr, double* x0, double* y0);
+/* The longitude shift dx[j] (degrees, [grid->n_lat]) that `rot` gives the rows of `grid` -- what utils/rectify.py:304-311
+ * subtracts from the longitudes, on the latitude sines the resample kernels use (grid->lat_sin when given). */
+int coreg_diffrot_table(const coreg_carr_grid* grid, const coreg_diffrot* rot, double* dx);
 /* CAR -> CAR map of one lag-point on the host: 0-based pixels of `from` -> 0-based pixels of `to` through the common
  * sphere, WCS(to).world_to_pixel(WCS(from).pixel_to_world(p)) for CRLN-CAR / CRLT-CAR headers (alignment.py:1038-1069
  * on the align_using_initial_carrington path).  Returns 1 when either header has no valid native pole (astropy raises
@@ -559,6 +581,9 @@ int coreg_multi_prepare_reference_carrington(coreg_multi* m, const void* large, 
                                              int order);
 int coreg_multi_prepare_reference_helioprojective(coreg_multi* m, const void* large, int dtype, int32_t ny, int32_t nx,
                                                   const coreg_wcs2d* hdr_large, const coreg_wcs2d* hdr_small, int order);
+/* coreg_set_reference_rotation / coreg_set_small_rotation on every device's context */
+int coreg_multi_set_reference_rotation(coreg_multi* m, const coreg_diffrot* rot);
+int coreg_multi_set_small_rotation(coreg_multi* m, const coreg_diffrot* rot);
 int coreg_multi_sweep_carrington(coreg_multi* m, const coreg_wcs2d* hdr_small, const coreg_carr_grid* grid, double solar_r,
                                  const coreg_lags* lags, int order, int method, int cdelt_semantics, double* corr_out);
 int coreg_multi_sweep_helioprojective(coreg_multi* m, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small,
