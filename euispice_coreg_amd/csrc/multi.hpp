@@ -12,6 +12,12 @@
 // onto the GPUs present so that this file can be exercised on a one-GPU box -- the blocks go to the host by one
 // asynchronous copy per device instead (RCCL refuses two ranks on one device).
 //
+// Map of the file:  RcclApi (dlopen), wait_limit, give_up_comms  ->  DeviceWorker (one host thread per device)
+//   ->  the partition (mirror of parallel.py: multi_lag_plan, forced_plan, multi_grid_share)  ->  struct coreg_multi,
+//   multi_run / multi_on  ->  the group helper (k_test_stall, poll_stream, multi_group: the ONE place a grouped
+//   collective is issued, waited for and given up)  ->  the sweep modes (sweep_points, sweep_sharded + scatter_chunks,
+//   multi_sweep), the image shares, the creation self-test  ->  the C ABI (coreg_multi_*).
+//
 // This file is included by coreg_hip.hip (same translation unit: it uses the handle's stream and staging internals).
 #pragma once
 
@@ -84,6 +90,25 @@ struct RcclApi {
         return api;
     }
 };
+
+// the limit of a bounded wait on RCCL, in seconds: the named environment variable when it is positive, else 20
+inline double wait_limit(const char* env_name) {
+    const char* env = std::getenv(env_name);
+    return env && std::atof(env) > 0 ? std::atof(env) : 20.0;
+}
+
+// Communicators nobody will use again.  `abort`: ncclCommAbort where the library has it (it releases the kernels a group
+// holds on a stream, and does not wait for them); else, and for communicators with nothing queued, ncclCommDestroy.
+void give_up_comms(std::vector<ncclComm_t>& comms, bool abort) {
+    if (comms.empty()) return;  // (RCCL was never set up: it is not looked up for this either)
+    RcclApi& api = RcclApi::get();
+    for (ncclComm_t c : comms)
+        if (c) {
+            if (abort && api.CommAbort) (void)api.CommAbort(c);
+            else (void)api.CommDestroy(c);
+        }
+    comms.clear();
+}
 
 // ---- one host thread per device -----------------------------------------------------------------------------------
 class DeviceWorker {
@@ -169,6 +194,15 @@ void multi_block_bounds(int n1, int n2, int world, int rank, int b[4]) {
     b[2] = std::min(r2 * b2, n2);
     b[3] = std::min((r2 + 1) * b2, n2);
 }
+// every one of the gb blocks of the plane holds at least one lag
+bool blocks_all_nonempty(int n1, int n2, int gb) {
+    for (int r = 0; r < gb; ++r) {
+        int b[4];
+        multi_block_bounds(n1, n2, gb, r, b);
+        if (b[1] <= b[0] || b[3] <= b[2]) return false;
+    }
+    return true;
+}
 // mirror of parallel.lag_batches / combo_bounds / lag_plan (checked against them on the CPU, tests/test_host_abi.py)
 constexpr double kLaunchOverheadBatches = 0.75;  // parallel.LAUNCH_OVERHEAD_BATCHES
 long long multi_lag_batches(int b1, int b2) {
@@ -201,13 +235,7 @@ MultiPlan multi_lag_plan(int n1, int n2, long long inner, int world, bool per_co
     for (int gc = 1; gc <= world; ++gc) {
         if (world % gc || gc > inner) continue;
         const int gb = world / gc;
-        bool full = true;
-        for (int r = 0; r < gb && full; ++r) {
-            int b[4];
-            multi_block_bounds(n1, n2, gb, r, b);
-            full = b[1] > b[0] && b[3] > b[2];
-        }
-        if (!full) continue;
+        if (!blocks_all_nonempty(n1, n2, gb)) continue;
         int g1, g2;
         multi_block_grid(n1, n2, gb, &g1, &g2);
         const double n_c = (double)((inner + gc - 1) / gc);
@@ -227,6 +255,18 @@ MultiPlan multi_lag_plan(int n1, int n2, long long inner, int world, bool per_co
     }
     p.mode = p.g_combo > 1 ? MULTI_COMBOS : MULTI_BLOCKS;
     return p;
+}
+// coreg_multi_set_option "force_mode" (tests of one partition on any lag set) over the planner's `plan`: 2 = slices;
+// 1 = blocks, 4 = combos over the whole plane -- unless a rank's block of the plane would be empty: the plan then stays
+MultiPlan forced_plan(MultiPlan plan, int force_mode, int n1, int n2, long long inner, int world) {
+    if (force_mode == MULTI_SLICES) plan.mode = MULTI_SLICES;
+    if (force_mode != MULTI_BLOCKS && force_mode != MULTI_COMBOS) return plan;
+    MultiPlan f;
+    f.mode = force_mode;
+    f.g_combo = force_mode == MULTI_COMBOS ? (int)std::min<long long>(world, inner) : 1;
+    while (world % f.g_combo) --f.g_combo;
+    multi_block_grid(n1, n2, world / f.g_combo, &f.g1, &f.g2);
+    return blocks_all_nonempty(n1, n2, f.g1 * f.g2) ? f : plan;
 }
 // device k's share under a blocks / combos plan: block b[4] of the plane, combinations [c_lo, c_hi)
 void multi_grid_share(const MultiPlan& p, int n1, int n2, long long inner, int k, int b[4], long long* c_lo, long long* c_hi) {
@@ -268,16 +308,34 @@ int mfail(coreg_multi* m, int code, const std::string& msg) {
     return code;
 }
 
-// run fn(k) on every device's own thread; first failure wins (its handle's message is kept)
-int multi_run(coreg_multi* m, const std::function<int(int)>& fn) {
+// run fn(k) on every device's own thread; first failure wins: its code is returned, its device goes to *k_bad.  No handle
+// is looked at here: coreg_multi_create makes them through this loop.
+int multi_each(coreg_multi* m, const std::function<int(int)>& fn, int* k_bad = nullptr) {
     std::vector<int> rc(m->n, COREG_OK);
     for (int k = 0; k < m->n; ++k) m->w[k]->post([&, k] { rc[k] = fn(k); });
     for (int k = 0; k < m->n; ++k) m->w[k]->wait();
     for (int k = 0; k < m->n; ++k)
-        if (rc[k] != COREG_OK)
-            return mfail(m, rc[k], "device " + std::to_string(m->devices[k]) + " (logical " + std::to_string(k) +
-                                       "): " + coreg_last_error(m->h[k]));
+        if (rc[k] != COREG_OK) {
+            if (k_bad) *k_bad = k;
+            return rc[k];
+        }
     return COREG_OK;
+}
+// ... with the failing handle's message kept
+int multi_run(coreg_multi* m, const std::function<int(int)>& fn) {
+    int k = 0;
+    const int rc = multi_each(m, fn, &k);
+    if (rc == COREG_OK) return rc;
+    return mfail(m, rc, "device " + std::to_string(m->devices[k]) + " (logical " + std::to_string(k) +
+                            "): " + coreg_last_error(m->h[k]));
+}
+// run `fn` on device k's worker thread and translate its error into the multi-handle's
+template <typename F>
+int multi_on(coreg_multi* m, int k, F fn) {
+    int rc = COREG_OK;
+    m->w[k]->post([&] { rc = fn(m->h[k]); });
+    m->w[k]->wait();
+    return rc == COREG_OK ? rc : mfail(m, rc, coreg_last_error(m->h[k]));
 }
 
 // host image -> the shared pinned staging (one parallel copy), page-locked so that every device DMAs from it
@@ -301,9 +359,16 @@ int multi_sync_pivots(coreg_multi* m) {
     return multi_run(m, [&](int k) { return k == 0 ? COREG_OK : coreg_set_pivots(m->h[k], piv); });
 }
 
+// ---- the group helper: ONE path for a grouped RCCL collective, every wait bounded -------------
+// A grouped collective is enqueued on the handles' own streams; what can fail to come back is the streams.  After each
+// group the streams are polled (hipStreamQuery) for at most the caller's limit (COREG_RCCL_WAIT_SECONDS for a sweep's
+// and the image's collective, COREG_RCCL_SELFTEST_SECONDS at creation; default 20 s); on expiry the communicators are
+// aborted (ncclCommAbort releases the kernels a group holds on a stream), RCCL is dropped for this handle, and the
+// caller hands the intact per-device results over through the host.
+
 // RCCL has failed (or never worked) on this multi-handle: from now on the blocks reach the host by one copy per device.
 // The streams are drained first so that nothing of the failed group is still queued behind the sweeps.
-void multi_drop_rccl(coreg_multi* m, const char* why) {
+void multi_drop_rccl(coreg_multi* m, const std::string& why) {
     m->use_rccl = false;
     m->rccl_error = why;
     const auto t0 = std::chrono::steady_clock::now();
@@ -311,7 +376,7 @@ void multi_drop_rccl(coreg_multi* m, const char* why) {
     m->phase_s[2] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// the stream position "just before the group": call on every device after its sweep is enqueued, before GroupStart
+// the stream position "just before the group": on every device after its sweep is enqueued, before the group is issued
 int multi_mark_pre_group(coreg_multi* m) {
     if (m->pre.size() != (size_t)m->n) m->pre.assign(m->n, nullptr);
     return multi_run(m, [&](int k) {
@@ -323,42 +388,23 @@ int multi_mark_pre_group(coreg_multi* m) {
     });
 }
 
-// ---- every wait on RCCL is bounded ------------------------------------------------------------
-// A grouped collective is enqueued on the handles' own streams; what can fail to come back is the streams.  After each
-// group the streams are polled (hipStreamQuery) for at most COREG_RCCL_WAIT_SECONDS (default 20, as the creation-time
-// self-test); on expiry the communicators are aborted (ncclCommAbort releases the kernels a group holds on a stream),
-// RCCL is dropped for this handle, and the caller hands the intact per-device results over through the host.
-inline double multi_rccl_wait_limit() {
-    const char* env = std::getenv("COREG_RCCL_WAIT_SECONDS");
-    return env && std::atof(env) > 0 ? std::atof(env) : 20.0;
-}
-
-// Fault injection for the tests (COREG_RCCL_TEST_STALL=1): instead of the group's collective, every stream gets a kernel
+// Fault injection for the tests (COREG_RCCL_TEST_STALL=1): instead of a sweep's collective, every stream gets a kernel
 // that spins on a flag in page-locked host memory -- a collective that never completes, as far as the stream can tell.
 // The abort path sets the flag; the kernel also leaves by itself after ~12 s of GPU clock, so that a bug in the recovery
 // cannot hold the device -- far enough above every wait limit the tests use (0.4 s) that a recovery released by this
 // self-limit cannot pass for one released by the abort path.  The flag is COHERENT (fine-grained)
 // page-locked memory, re-read with a system-scope atomic load on every turn: a host store reaches the spinning wave.
-__global__ void k_test_stall(int* release, int legacy) {
+__global__ void k_test_stall(int* release) {
     const long long t0 = wall_clock64();
-    if (legacy) {  // (round 5's form, kept for the A/B of DESIGN 6: a plain volatile load of plain page-locked memory)
-        volatile int* r = release;
-        while (*r == 0 && wall_clock64() - t0 < 1200000000LL) __builtin_amdgcn_s_sleep(64);
-        return;
-    }
     while (__hip_atomic_load(release, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0 &&
            wall_clock64() - t0 < 1200000000LL)  // 100 MHz counter: 12 s
         __builtin_amdgcn_s_sleep(64);
 }
-inline int multi_test_stall_legacy() {
-    const char* env = std::getenv("COREG_RCCL_TEST_STALL_LEGACY");
-    return env && std::atoi(env) == 1 ? 1 : 0;
-}
 struct StallFlag {
     int* p = nullptr;
-    StallFlag() {
-        const unsigned flags = multi_test_stall_legacy() ? hipHostMallocPortable : (hipHostMallocPortable | hipHostMallocCoherent);
-        if (hipHostMalloc((void**)&p, sizeof(int), flags) != hipSuccess) p = nullptr;
+    explicit StallFlag(bool wanted) {
+        if (!wanted) return;
+        if (hipHostMalloc((void**)&p, sizeof(int), hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess) p = nullptr;
         if (p) __atomic_store_n(p, 0, __ATOMIC_SEQ_CST);
     }
     ~StallFlag() {
@@ -370,70 +416,82 @@ inline bool multi_test_stall() {
     return env && std::atoi(env) == 1;
 }
 
-// true: every stream has drained.  false: at least one did not within the limit (or reported an error) -- the
-// communicators are aborted and RCCL is given up for this handle; the streams are usable again on return.
-bool multi_wait_group(coreg_multi* m, const char* what, StallFlag* stall = nullptr) {
-    const double limit = multi_rccl_wait_limit();
-    std::vector<int> state(m->n, 0);  // 1 = drained, 2 = error, 3 = timed out
-    const bool have_pre = m->pre.size() == (size_t)m->n;
+// Poll a stream for at most `limit` seconds: 1 = drained, 2 = error, 3 = timed out.  With `pre` (an event recorded on
+// the stream) the clock of the limit starts when the work queued BEFORE it (this device's sweep) has left the stream
+// (a long sweep is not a hung collective); that part is waited for without a limit, as every stream-ordered
+// call of the library waits for its own kernels.
+int poll_stream(hipStream_t stream, hipEvent_t pre, double limit) {
+    bool started = !pre;
+    auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        if (!started) {
+            const hipError_t qe = hipEventQuery(pre);
+            if (qe == hipSuccess) {
+                started = true;
+                t0 = std::chrono::steady_clock::now();
+            } else if (qe != hipErrorNotReady) {
+                return 2;
+            }
+        }
+        const hipError_t q = hipStreamQuery(stream);
+        if (q == hipSuccess) return 1;
+        if (q != hipErrorNotReady) return 2;
+        const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        if (started && dt > limit) return 3;
+        if (dt < 0.005) std::this_thread::yield();  // a sweep's collective takes microseconds to milliseconds
+        else std::this_thread::sleep_for(std::chrono::microseconds(200));
+    }
+}
+
+// One grouped collective on the handles' own streams: `issue(k)` = device k's one RCCL call (`what` names it in the
+// status).  true: every stream has drained.  false: a call failed, or a stream did not drain within `limit` seconds (or
+// reported an error) and the communicators were aborted -- either way RCCL is given up for this handle
+// (coreg_multi_rccl_status says why and where the time of the recovery went) and the streams are usable again.
+// `test_stall`: this group honours COREG_RCCL_TEST_STALL (a sweep's collective), and is then never reported as done.
+bool multi_group(coreg_multi* m, const char* what, double limit, const std::function<ncclResult_t(int)>& issue,
+                 bool test_stall = false) {
+    RcclApi& api = RcclApi::get();
+    const bool stalling = test_stall && multi_test_stall();
+    StallFlag stall(stalling);
+    ncclResult_t e = ncclSuccess, e2 = ncclSuccess;
+    if (multi_mark_pre_group(m) != COREG_OK) {
+        e = ncclUnhandledCudaError;
+    } else if (stall.p) {
+        (void)multi_run(m, [&](int k) {
+            RETCHK(bind_device(m->h[k]));
+            hipLaunchKernelGGL(k_test_stall, dim3(1), dim3(1), 0, m->h[k]->stream, stall.p);
+            return COREG_OK;
+        });
+    } else {
+        e = api.GroupStart();
+        for (int k = 0; k < m->n && e == ncclSuccess; ++k) e = issue(k);
+        e2 = api.GroupEnd();
+    }
+    if (e != ncclSuccess || e2 != ncclSuccess) {
+        multi_drop_rccl(m, std::string(what) + " failed");
+        return false;
+    }
+    std::vector<int> state(m->n, 0);
     const auto t_poll = std::chrono::steady_clock::now();
     (void)multi_run(m, [&](int k) {
-        coreg_handle* h = m->h[k];
-        RETCHK(bind_device(h));
-        // the clock of the limit starts when the work queued BEFORE the group (this device's sweep) has left the stream
-        // (a long sweep is not a hung collective); that part is waited for without a limit, as every
-        // stream-ordered call of the library waits for its own kernels
-        bool started = !(have_pre && m->pre[k]);
-        auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            if (!started) {
-                const hipError_t qe = hipEventQuery(m->pre[k]);
-                if (qe == hipSuccess) {
-                    started = true;
-                    t0 = std::chrono::steady_clock::now();
-                } else if (qe != hipErrorNotReady) {
-                    state[k] = 2;
-                    return COREG_OK;
-                }
-            }
-            const hipError_t q = hipStreamQuery(h->stream);
-            if (q == hipSuccess) {
-                state[k] = 1;
-                return COREG_OK;
-            }
-            if (q != hipErrorNotReady) {
-                state[k] = 2;
-                return COREG_OK;
-            }
-            const double dt = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            if (started && dt > limit) {
-                state[k] = 3;
-                return COREG_OK;
-            }
-            if (dt < 0.005) std::this_thread::yield();  // a sweep's collective takes microseconds to milliseconds
-            else std::this_thread::sleep_for(std::chrono::microseconds(200));
-        }
+        RETCHK(bind_device(m->h[k]));
+        state[k] = poll_stream(m->h[k]->stream, m->pre[k], limit);
+        return COREG_OK;
     });
     bool ok = true, timed_out = false;
     for (int k = 0; k < m->n; ++k) {
         ok = ok && state[k] == 1;
         timed_out = timed_out || state[k] == 3;
     }
-    if (ok) return true;
+    if (ok) return !stalling;
     m->phase_s[0] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_poll).count();
     // (test: the injected "collective" is what the abort releases -- before ncclCommAbort, which waits for the
     // communicator's stream work)
-    if (stall && stall->p) __atomic_store_n(stall->p, 1, __ATOMIC_SEQ_CST);
+    if (stall.p) __atomic_store_n(stall.p, 1, __ATOMIC_SEQ_CST);
     const auto t_abort = std::chrono::steady_clock::now();
-    RcclApi& api = RcclApi::get();
-    for (ncclComm_t c : m->comms)
-        if (c) {
-            if (api.CommAbort) (void)api.CommAbort(c);
-            else (void)api.CommDestroy(c);
-        }
-    m->comms.clear();
+    give_up_comms(m->comms, true);
     m->phase_s[1] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_abort).count();
-    multi_drop_rccl(m, (std::string(what) + (timed_out ? " did not complete in time" : " failed on a stream")).c_str());
+    multi_drop_rccl(m, std::string(what) + (timed_out ? " did not complete in time" : " failed on a stream"));
     // where the time of the recovery went, for whoever reads the status (coreg_multi_rccl_status)
     char buf[160];
     std::snprintf(buf, sizeof buf, " [waited %.3f s on the streams (limit %.3g s), ncclCommAbort %.3f s, stream drain %.3f s]",
@@ -442,147 +500,109 @@ bool multi_wait_group(coreg_multi* m, const char* what, StallFlag* stall = nullp
     return false;
 }
 
-// one sweep on every device + the collective; `launch(k, lags_k, begin, end, out_dev)` = the per-device sweep call
-int multi_sweep(coreg_multi* m, const coreg_lags* lags, double* corr_out, bool per_combo_launch,
-                const std::function<int(int, const coreg_lags*, int64_t, int64_t, double*)>& launch) {
-    if (!m) return COREG_EINVAL;
-    if (!lags || !lags->crval1 || !lags->crval2 || !lags->cdelt1 || !lags->cdelt2 || !lags->crota || lags->n_crval1 < 1 ||
-        lags->n_crval2 < 1 || lags->n_cdelt1 < 1 || lags->n_cdelt2 < 1 || lags->n_crota < 1)
-        return mfail(m, COREG_EINVAL, "lags: null array or empty axis");
-    const int n1 = lags->n_crval1, n2 = lags->n_crval2, world = m->n;
-    const long long inner = (long long)lags->n_cdelt1 * lags->n_cdelt2 * lags->n_crota;
-    const long long n_lags = (long long)n1 * n2 * inner;
-    if (!corr_out && n_lags > 0) return mfail(m, COREG_EINVAL, "corr_out is null");
-    MultiPlan plan = multi_lag_plan(n1, n2, inner, world, per_combo_launch);
-    if (m->force_mode >= 0 && world > 1) {  // tests: "force_mode" 1 = blocks, 2 = slices, 4 = combos over the whole plane
-        if (m->force_mode == MULTI_SLICES) plan.mode = MULTI_SLICES;
-        if (m->force_mode == MULTI_BLOCKS || m->force_mode == MULTI_COMBOS) {
-            MultiPlan f;
-            f.mode = m->force_mode;
-            f.g_combo = m->force_mode == MULTI_COMBOS ? (int)std::min<long long>(world, inner) : 1;
-            while (world % f.g_combo) --f.g_combo;
-            multi_block_grid(n1, n2, world / f.g_combo, &f.g1, &f.g2);
-            bool full = true;
-            for (int r = 0; r < f.g1 * f.g2 && full; ++r) {
-                int bb[4];
-                multi_block_bounds(n1, n2, f.g1 * f.g2, r, bb);
-                full = bb[1] > bb[0] && bb[3] > bb[2];
-            }
-            if (full) plan = f;
-        }
-    }
-    int mode = plan.mode;
-    if (mode == MULTI_NONE && m->force_collective) mode = MULTI_SLICES;  // one slice, one-rank all-gather
-    m->last_mode = mode;
-    if (mode == MULTI_NONE) {
-        m->collective = "none";
-        int rc = COREG_OK;
-        m->w[0]->post([&] { rc = launch(0, lags, 0, n_lags, nullptr); });
-        m->w[0]->wait();
-        if (rc != COREG_OK) return mfail(m, rc, coreg_last_error(m->h[0]));
-        return COREG_OK;
-    }
-    bool rccl = m->use_rccl;
-    m->collective = rccl ? "rccl" : "host-copy";
+// ---- the sweep modes ----------------------------------------------------------------------------------------------
+// `launch(k, lags_k, begin, end, out_dev)` = the per-device sweep call
+using SweepLaunch = std::function<int(int, const coreg_lags*, int64_t, int64_t, double*)>;
 
-    if (mode == MULTI_POINTS) {
-        // every device sweeps ALL lag-points over its share of the grid; the six sums per lag slot are added over the
-        // devices (all-reduce), device 0 evaluates the coefficients.  Whatever happens in between, every context is
-        // back to "unsharded" and drained when this branch is left (a later sweep on the same contexts must not run as
-        // a grid share).
-        struct Unshard {
-            coreg_multi* m;
-            ~Unshard() {
-                (void)multi_run(m, [&](int k) {
-                    (void)coreg_set_option(m->h[k], "shard_world", 1);
-                    return coreg_synchronize(m->h[k]);
-                });
-            }
-        } unshard{m};
-        RETCHK(multi_sync_pivots(m));
+// a sweep's collective: the sweep's limit, the tests' stall injection honoured.  false: the per-device results are intact
+// and go through the host instead, this sweep and (RCCL being gone for the handle) every later one
+bool sweep_group(coreg_multi* m, const char* what, const std::function<ncclResult_t(int)>& issue) {
+    if (multi_group(m, what, wait_limit("COREG_RCCL_WAIT_SECONDS"), issue, true)) return true;
+    m->collective = std::string("host-copy (") + what + " did not complete)";
+    return false;
+}
+
+// Grid shares: every device sweeps ALL lag-points over its share of the grid; the six sums per lag slot are added over
+// the devices (all-reduce), device 0 evaluates the coefficients.
+int sweep_points(coreg_multi* m, const coreg_lags* lags, long long n_lags, double* corr_out, const SweepLaunch& launch) {
+    const int world = m->n;
+    // Whatever happens in between, every context is back to "unsharded" and drained when this function is left (a later
+    // sweep on the same contexts must not run as a grid share; the caller's buffers go after the streams have drained).
+    struct Unshard {
+        coreg_multi* m;
+        ~Unshard() {
+            (void)multi_run(m, [&](int k) {
+                (void)coreg_set_option(m->h[k], "shard_world", 1);
+                return coreg_synchronize(m->h[k]);
+            });
+        }
+    } unshard{m};
+    RETCHK(multi_sync_pivots(m));
+    RETCHK(multi_run(m, [&](int k) {
+        coreg_handle* h = m->h[k];
+        RETCHK(bind_device(h));
+        RETCHK(coreg_set_option(h, "shard_world", world));
+        RETCHK(coreg_set_option(h, "shard_rank", k));
+        HIPCHK(m->blk[k].reserve((size_t)std::max<long long>(n_lags, 1) * sizeof(double)));
+        return launch(k, lags, 0, n_lags, m->blk[k].as<double>());
+    }));
+    int64_t n6 = 0;
+    coreg_sums_size(m->h[0], &n6);
+    if (n6 <= 0)  // no launch happened anywhere (every lag-point invalid): the NaN-filled output of device 0
+        return multi_on(m, 0, [&](coreg_handle* h) {
+            RETCHK(bind_device(h));
+            HIPCHK(hipMemcpyAsync(corr_out, m->blk[0].p, (size_t)n_lags * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            return COREG_OK;
+        });
+    if (m->use_rccl) {
+        // OUT of place (into gat[k]): whatever happens to the collective, every device's own sums stay intact and the
+        // host path below can still add them
         RETCHK(multi_run(m, [&](int k) {
             coreg_handle* h = m->h[k];
             RETCHK(bind_device(h));
-            RETCHK(coreg_set_option(h, "shard_world", world));
-            RETCHK(coreg_set_option(h, "shard_rank", k));
-            HIPCHK(m->blk[k].reserve((size_t)std::max<long long>(n_lags, 1) * sizeof(double)));
-            return launch(k, lags, 0, n_lags, m->blk[k].as<double>());
+            HIPCHK(m->gat[k].reserve((size_t)n6 * sizeof(double)));
+            return COREG_OK;
         }));
-        int rc = COREG_OK;
-        int64_t n6 = 0;
-        coreg_sums_size(m->h[0], &n6);
-        bool reduced_on_device = false;
-        if (rccl && n6 > 0) {
-            // OUT of place (into gat[k]): whatever happens to the collective, every device's own sums stay intact and
-            // the host path below can still add them
-            RETCHK(multi_run(m, [&](int k) {
-                coreg_handle* h = m->h[k];
-                RETCHK(bind_device(h));
-                HIPCHK(m->gat[k].reserve((size_t)n6 * sizeof(double)));
-                return COREG_OK;
-            }));
-            StallFlag stall;
-            ncclResult_t e = ncclSuccess, e2 = ncclSuccess;
-            RETCHK(multi_mark_pre_group(m));
-            if (multi_test_stall() && stall.p) {
-                (void)multi_run(m, [&](int k) {
-                    RETCHK(bind_device(m->h[k]));
-                    hipLaunchKernelGGL(k_test_stall, dim3(1), dim3(1), 0, m->h[k]->stream, stall.p, multi_test_stall_legacy());
-                    return COREG_OK;
-                });
-            } else {
-                e = RcclApi::get().GroupStart();
-                for (int k = 0; k < world && e == ncclSuccess; ++k)
-                    e = RcclApi::get().AllReduce(m->h[k]->sums.p, m->gat[k].p, (size_t)n6, ncclDouble, ncclSum, m->comms[k],
-                                                 m->h[k]->stream);
-                e2 = RcclApi::get().GroupEnd();
-            }
-            if (e != ncclSuccess || e2 != ncclSuccess) {
-                multi_drop_rccl(m, "RCCL all-reduce failed");
-                m->collective = "host-copy (RCCL all-reduce failed)";
-            } else if (!multi_wait_group(m, "RCCL all-reduce", &stall) || multi_test_stall()) {
-                m->collective = "host-copy (RCCL all-reduce did not complete)";
-            } else {
-                reduced_on_device = true;
-            }
-        }
-        if (reduced_on_device) {
-            m->w[0]->post([&] { rc = coreg_finalize_sums(m->h[0], m->gat[0].as<double>(), 1, corr_out, 0); });
-            m->w[0]->wait();
-            if (rc != COREG_OK) mfail(m, rc, coreg_last_error(m->h[0]));
-        } else if (n6 > 0) {
-            std::vector<std::vector<double>> part(world, std::vector<double>((size_t)n6));
-            rc = multi_run(m, [&](int k) { return coreg_copy_sums(m->h[k], part[k].data(), 0); });
-            if (rc == COREG_OK) {
-                for (int k = 1; k < world; ++k)  // fixed order: deterministic
-                    for (int64_t i = 0; i < n6; ++i) part[0][(size_t)i] += part[k][(size_t)i];
-                m->w[0]->post([&] { rc = coreg_finalize_sums(m->h[0], part[0].data(), 0, corr_out, 0); });
-                m->w[0]->wait();
-                if (rc != COREG_OK) mfail(m, rc, coreg_last_error(m->h[0]));
-            }
-        } else {
-            // no launch happened anywhere (every lag-point invalid): the NaN-filled output of device 0
-            m->w[0]->post([&] {
-                rc = bind_device(m->h[0]);
-                if (rc == COREG_OK && hipMemcpyAsync(corr_out, m->blk[0].p, (size_t)n_lags * sizeof(double),
-                                                     hipMemcpyDeviceToHost, m->h[0]->stream) != hipSuccess)
-                    rc = COREG_EHIP;
-                if (rc == COREG_OK && hipStreamSynchronize(m->h[0]->stream) != hipSuccess) rc = COREG_EHIP;
+        const bool reduced = sweep_group(m, "RCCL all-reduce", [&](int k) {
+            return RcclApi::get().AllReduce(m->h[k]->sums.p, m->gat[k].p, (size_t)n6, ncclDouble, ncclSum, m->comms[k],
+                                            m->h[k]->stream);
+        });
+        if (reduced)
+            return multi_on(m, 0, [&](coreg_handle* h) {
+                return coreg_finalize_sums(h, m->gat[0].as<double>(), 1, corr_out, 0);
             });
-            m->w[0]->wait();
-        }
-        return rc;  // (~Unshard: back to unsharded contexts, every stream drained before the caller's buffers go)
     }
+    std::vector<std::vector<double>> part(world, std::vector<double>((size_t)n6));
+    RETCHK(multi_run(m, [&](int k) { return coreg_copy_sums(m->h[k], part[k].data(), 0); }));
+    for (int k = 1; k < world; ++k)  // fixed order: deterministic
+        for (int64_t i = 0; i < n6; ++i) part[0][(size_t)i] += part[k][(size_t)i];
+    return multi_on(m, 0, [&](coreg_handle* h) { return coreg_finalize_sums(h, part[0].data(), 0, corr_out, 0); });
+}
 
-    // ---- lag sharding: a g_combo x (g1 x g2) grid of (combination run) x (block of the CRVAL plane), or contiguous
-    //      slices of the raveled index
-    const bool grid = mode == MULTI_BLOCKS || mode == MULTI_COMBOS;
-    long long chunk;
-    if (grid)
-        chunk = (long long)((n1 + plan.g1 - 1) / plan.g1) * ((n2 + plan.g2 - 1) / plan.g2) *
-                ((inner + plan.g_combo - 1) / plan.g_combo);
-    else
-        chunk = (n_lags + world - 1) / world;
+// gathered chunks (device k's at k * chunk, n_mine[k] doubles of it filled) -> the C-order raveled map
+void scatter_chunks(const MultiPlan& plan, int n1, int n2, long long inner, long long chunk,
+                    const std::vector<long long>& n_mine, const double* gathered, double* corr_out) {
+    const int world = (int)n_mine.size();
+    for (int k = 0; k < world; ++k) {
+        if (n_mine[k] <= 0) continue;
+        const double* mine = gathered + (size_t)k * chunk;
+        if (plan.mode == MULTI_SLICES) {
+            std::memcpy(corr_out + (size_t)k * chunk, mine, (size_t)n_mine[k] * sizeof(double));
+            continue;
+        }
+        int b[4];
+        long long c_lo, c_hi;
+        multi_grid_share(plan, n1, n2, inner, k, b, &c_lo, &c_hi);
+        const int w2 = b[3] - b[2];
+        const long long ncm = c_hi - c_lo;
+        for (int i1 = b[0]; i1 < b[1]; ++i1)
+            for (int i2 = b[2]; i2 < b[3]; ++i2)
+                std::memcpy(corr_out + ((size_t)i1 * n2 + i2) * inner + c_lo,
+                            mine + ((size_t)(i1 - b[0]) * w2 + (i2 - b[2])) * ncm, (size_t)ncm * sizeof(double));
+    }
+}
+
+// Lag sharding: a g_combo x (g1 x g2) grid of (combination run) x (block of the CRVAL plane), or contiguous slices of the
+// raveled index; ONE all-gather of the per-device chunks (or one copy per device to the host), scattered into the map.
+int sweep_sharded(coreg_multi* m, const MultiPlan& plan, const coreg_lags* lags, long long inner, double* corr_out,
+                  const SweepLaunch& launch) {
+    const int n1 = lags->n_crval1, n2 = lags->n_crval2, world = m->n;
+    const long long n_lags = (long long)n1 * n2 * inner;
+    const bool grid = plan.mode != MULTI_SLICES, rccl = m->use_rccl;
+    const long long chunk = grid ? (long long)((n1 + plan.g1 - 1) / plan.g1) * ((n2 + plan.g2 - 1) / plan.g2) *
+                                       ((inner + plan.g_combo - 1) / plan.g_combo)
+                                 : (n_lags + world - 1) / world;
     if (m->host_gather.reserve((size_t)chunk * world * sizeof(double)) != hipSuccess)
         return mfail(m, COREG_ENOMEM, "hipHostMalloc (gather buffer) failed");
     std::vector<long long> n_mine(world, 0);
@@ -628,34 +648,12 @@ int multi_sweep(coreg_multi* m, const coreg_lags* lags, double* corr_out, bool p
     if (rccl) {
         // THE collective: one all-gather of `chunk` doubles per device, all devices in one group, each on the stream its
         // sweep was enqueued on
-        StallFlag stall;
-        ncclResult_t e = ncclSuccess, e2 = ncclSuccess;
-        RETCHK(multi_mark_pre_group(m));
-        if (multi_test_stall() && stall.p) {
-            (void)multi_run(m, [&](int k) {
-                RETCHK(bind_device(m->h[k]));
-                hipLaunchKernelGGL(k_test_stall, dim3(1), dim3(1), 0, m->h[k]->stream, stall.p, multi_test_stall_legacy());
-                return COREG_OK;
-            });
-        } else {
-            e = RcclApi::get().GroupStart();
-            for (int k = 0; k < world && e == ncclSuccess; ++k)
-                e = RcclApi::get().AllGather(m->blk[k].p, m->gat[k].p, (size_t)chunk, ncclDouble, m->comms[k], m->h[k]->stream);
-            e2 = RcclApi::get().GroupEnd();
-        }
-        if (e != ncclSuccess || e2 != ncclSuccess) {
-            // the blocks themselves are intact on their devices: hand them over through the host instead, now and for
-            // every later sweep of this handle
-            multi_drop_rccl(m, "RCCL all-gather failed");
-            m->collective = "host-copy (RCCL all-gather failed)";
-            rccl = false;
+        const bool gathered = sweep_group(m, "RCCL all-gather", [&](int k) {
+            return RcclApi::get().AllGather(m->blk[k].p, m->gat[k].p, (size_t)chunk, ncclDouble, m->comms[k], m->h[k]->stream);
+        });
+        if (!gathered)  // the blocks themselves are intact on their devices: hand them over through the host instead
             RETCHK(multi_run(m, to_host));
-        } else if (!multi_wait_group(m, "RCCL all-gather", &stall) || multi_test_stall()) {
-            // a group that did not come back within the limit: aborted; the blocks are intact on their devices
-            m->collective = "host-copy (RCCL all-gather did not complete)";
-            rccl = false;
-            RETCHK(multi_run(m, to_host));
-        } else {
+        else
             RETCHK(multi_run(m, [&](int k) {
                 coreg_handle* h = m->h[k];
                 RETCHK(bind_device(h));
@@ -665,32 +663,35 @@ int multi_sweep(coreg_multi* m, const coreg_lags* lags, double* corr_out, bool p
                 HIPCHK(hipStreamSynchronize(h->stream));
                 return COREG_OK;
             }));
-        }
     }
-    const double* gathered = (const double*)m->host_gather.p;
-    // gathered chunks -> C-order raveled map
-    if (!grid) {
-        for (int k = 0; k < world; ++k)
-            if (n_mine[k] > 0)
-                std::memcpy(corr_out + (size_t)k * chunk, gathered + (size_t)k * chunk, (size_t)n_mine[k] * sizeof(double));
-    } else {
-        for (int k = 0; k < world; ++k) {
-            int b[4];
-            long long c_lo, c_hi;
-            multi_grid_share(plan, n1, n2, inner, k, b, &c_lo, &c_hi);
-            const int w2 = b[3] - b[2];
-            const long long ncm = c_hi - c_lo;
-            if (ncm <= 0) continue;
-            for (int i1 = b[0]; i1 < b[1]; ++i1)
-                for (int i2 = b[2]; i2 < b[3]; ++i2)
-                    std::memcpy(corr_out + ((size_t)i1 * n2 + i2) * inner + c_lo,
-                                gathered + (size_t)k * chunk + ((size_t)(i1 - b[0]) * w2 + (i2 - b[2])) * ncm,
-                                (size_t)ncm * sizeof(double));
-        }
-    }
+    scatter_chunks(plan, n1, n2, inner, chunk, n_mine, (const double*)m->host_gather.p, corr_out);
     return COREG_OK;
 }
 
+// one sweep on every device + the collective: the argument checks, the plan and the dispatch to its mode
+int multi_sweep(coreg_multi* m, const coreg_lags* lags, double* corr_out, bool per_combo_launch, const SweepLaunch& launch) {
+    if (!m) return COREG_EINVAL;
+    if (!lags || !lags->crval1 || !lags->crval2 || !lags->cdelt1 || !lags->cdelt2 || !lags->crota || lags->n_crval1 < 1 ||
+        lags->n_crval2 < 1 || lags->n_cdelt1 < 1 || lags->n_cdelt2 < 1 || lags->n_crota < 1)
+        return mfail(m, COREG_EINVAL, "lags: null array or empty axis");
+    const int n1 = lags->n_crval1, n2 = lags->n_crval2, world = m->n;
+    const long long inner = (long long)lags->n_cdelt1 * lags->n_cdelt2 * lags->n_crota;
+    const long long n_lags = (long long)n1 * n2 * inner;
+    if (!corr_out && n_lags > 0) return mfail(m, COREG_EINVAL, "corr_out is null");
+    MultiPlan plan = multi_lag_plan(n1, n2, inner, world, per_combo_launch);
+    if (m->force_mode >= 0 && world > 1) plan = forced_plan(plan, m->force_mode, n1, n2, inner, world);
+    if (plan.mode == MULTI_NONE && m->force_collective) plan.mode = MULTI_SLICES;  // one slice, one-rank all-gather
+    m->last_mode = plan.mode;
+    if (plan.mode == MULTI_NONE) {
+        m->collective = "none";
+        return multi_on(m, 0, [&](coreg_handle*) { return launch(0, lags, 0, n_lags, nullptr); });
+    }
+    m->collective = m->use_rccl ? "rccl" : "host-copy";
+    if (plan.mode == MULTI_POINTS) return sweep_points(m, lags, n_lags, corr_out, launch);
+    return sweep_sharded(m, plan, lags, inner, corr_out, launch);
+}
+
+// ---- the image to align -------------------------------------------------------------------------------------------
 // The image to align crosses PCIe ONCE in all: device k uploads rows [k * ceil(H / N), ...) over its own link, ONE
 // all-gather over xGMI (in place: every device's share sits where the gathered image wants it) assembles the replica on
 // every GPU, and each device adopts (and, for raw FITS bytes, decodes) its copy.  The reference hands its workers the
@@ -712,111 +713,15 @@ int multi_set_small_shares(coreg_multi* m, const void* src, const PixFmt& fmt, i
                                  (hi - lo) * row_bytes));
         return COREG_OK;
     }));
-    RETCHK(multi_mark_pre_group(m));
-    RcclApi& api = RcclApi::get();
-    ncclResult_t e = api.GroupStart();
-    for (int k = 0; k < world && e == ncclSuccess; ++k)
-        e = api.AllGather((const char*)m->img[k].p + (size_t)k * share, m->img[k].p, share, ncclChar, m->comms[k],
-                          m->h[k]->stream);
-    const ncclResult_t e2 = api.GroupEnd();
-    if (e != ncclSuccess || e2 != ncclSuccess) {
-        multi_drop_rccl(m, "RCCL all-gather of the image failed");
-        return COREG_ENOTIMPL;
-    }
-    if (!multi_wait_group(m, "RCCL all-gather of the image")) return COREG_ENOTIMPL;  // (the caller stages the whole image)
+    const bool gathered = multi_group(m, "RCCL all-gather of the image", wait_limit("COREG_RCCL_WAIT_SECONDS"), [&](int k) {
+        return RcclApi::get().AllGather((const char*)m->img[k].p + (size_t)k * share, m->img[k].p, share, ncclChar,
+                                        m->comms[k], m->h[k]->stream);
+    });
+    if (!gathered) return COREG_ENOTIMPL;  // (the caller stages the whole image)
     return multi_run(m, [&](int k) {
         RETCHK(set_small_from(m->h[k], m->img[k].p, fmt, SRC_DEVICE, ny, nx));
         return coreg_synchronize(m->h[k]);  // the caller's host buffer and the share buffers are free again on return
     });
-}
-
-// The communicators have never carried data: before any result depends on them, every device contributes (k + 1) * 1.5
-// to ONE grouped all-gather -- the very call a sweep makes -- and checks what it received.  The wait is bounded
-// (COREG_RCCL_SELFTEST_SECONDS, default 20): a group that does not come back is aborted (ncclCommAbort) and the handle
-// falls back to host copies, as it does when the pattern is wrong or a call fails.
-void multi_rccl_selftest(coreg_multi* m) {
-    const int world = m->n;
-    RcclApi& api = RcclApi::get();
-    std::string why;
-    bool ok = multi_run(m, [&](int k) {
-                  coreg_handle* h = m->h[k];
-                  RETCHK(bind_device(h));
-                  HIPCHK(m->blk[k].reserve(sizeof(double)));
-                  HIPCHK(m->gat[k].reserve((size_t)world * sizeof(double)));
-                  const double v = (k + 1) * 1.5;
-                  HIPCHK(hipMemcpyAsync(m->blk[k].p, &v, sizeof(double), hipMemcpyHostToDevice, h->stream));
-                  HIPCHK(hipMemsetAsync(m->gat[k].p, 0, (size_t)world * sizeof(double), h->stream));
-                  HIPCHK(hipStreamSynchronize(h->stream));
-                  return COREG_OK;
-              }) == COREG_OK;
-    if (!ok) why = "self-test setup failed";
-    if (ok) {
-        ncclResult_t e = api.GroupStart();
-        for (int k = 0; k < world && e == ncclSuccess; ++k)
-            e = api.AllGather(m->blk[k].p, m->gat[k].p, 1, ncclDouble, m->comms[k], m->h[k]->stream);
-        const ncclResult_t e2 = api.GroupEnd();
-        if (e != ncclSuccess || e2 != ncclSuccess) {
-            ok = false;
-            why = "self-test all-gather returned an error";
-        }
-    }
-    bool timed_out = false;
-    if (ok) {
-        const char* env = std::getenv("COREG_RCCL_SELFTEST_SECONDS");
-        const double limit = env && std::atof(env) > 0 ? std::atof(env) : 20.0;
-        std::vector<int> state(world, 0);  // 1 = done and right, 2 = done and wrong, 3 = timed out
-        (void)multi_run(m, [&](int k) {
-            coreg_handle* h = m->h[k];
-            RETCHK(bind_device(h));
-            const auto t0 = std::chrono::steady_clock::now();
-            for (;;) {
-                const hipError_t q = hipStreamQuery(h->stream);
-                if (q == hipSuccess) break;
-                if (q != hipErrorNotReady) {
-                    state[k] = 2;
-                    return COREG_OK;
-                }
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit) {
-                    state[k] = 3;
-                    return COREG_OK;
-                }
-                std::this_thread::sleep_for(std::chrono::milliseconds(1));
-            }
-            std::vector<double> got((size_t)world);
-            if (hipMemcpy(got.data(), m->gat[k].p, (size_t)world * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
-                state[k] = 2;
-                return COREG_OK;
-            }
-            state[k] = 1;
-            for (int j = 0; j < world; ++j)
-                if (got[(size_t)j] != (j + 1) * 1.5) state[k] = 2;
-            return COREG_OK;
-        });
-        for (int k = 0; k < world; ++k) {
-            if (state[k] == 3) timed_out = true;
-            if (state[k] != 1) ok = false;
-        }
-        if (!ok) why = timed_out ? "self-test all-gather did not complete in time" : "self-test all-gather gave wrong values";
-    }
-    if (ok) return;
-    // give the communicators up; an aborted group releases the streams it holds
-    for (ncclComm_t c : m->comms)
-        if (c) {
-            if (timed_out && api.CommAbort) (void)api.CommAbort(c);
-            else (void)api.CommDestroy(c);
-        }
-    m->comms.clear();
-    m->use_rccl = false;
-    m->rccl_error = why;
-}
-
-// run `fn` on device k's worker thread and translate its error into the multi-handle's
-template <typename F>
-int multi_on(coreg_multi* m, int k, F fn) {
-    int rc = COREG_OK;
-    m->w[k]->post([&] { rc = fn(m->h[k]); });
-    m->w[k]->wait();
-    return rc == COREG_OK ? rc : mfail(m, rc, coreg_last_error(m->h[k]));
 }
 
 // The image to align on every device, native pixels or a FITS data unit's raw bytes alike: shares over each device's own
@@ -834,6 +739,107 @@ int multi_set_small_from(coreg_multi* m, const void* src, const PixFmt& fmt, int
         RETCHK(set_small_from(m->h[k], m->stage.p, fmt, SRC_PINNED, ny, nx));
         return coreg_synchronize(m->h[k]);  // the shared staging is free again on return
     });
+}
+
+// The communicators have never carried data: before any result depends on them, every device contributes (k + 1) * 1.5
+// to ONE grouped all-gather -- the very call a sweep makes, through the same helper, under COREG_RCCL_SELFTEST_SECONDS
+// -- and checks what it received.  A group that fails or does not come back is given up by the helper; a wrong pattern
+// here: either way the handle falls back to host copies.
+void multi_rccl_selftest(coreg_multi* m) {
+    const int world = m->n;
+    std::string why;
+    const int rc = multi_run(m, [&](int k) {
+        coreg_handle* h = m->h[k];
+        RETCHK(bind_device(h));
+        HIPCHK(m->blk[k].reserve(sizeof(double)));
+        HIPCHK(m->gat[k].reserve((size_t)world * sizeof(double)));
+        const double v = (k + 1) * 1.5;
+        HIPCHK(hipMemcpyAsync(m->blk[k].p, &v, sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemsetAsync(m->gat[k].p, 0, (size_t)world * sizeof(double), h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return COREG_OK;
+    });
+    if (rc != COREG_OK) {
+        why = "self-test setup failed";
+    } else if (multi_group(m, "self-test all-gather", wait_limit("COREG_RCCL_SELFTEST_SECONDS"), [&](int k) {
+                   return RcclApi::get().AllGather(m->blk[k].p, m->gat[k].p, 1, ncclDouble, m->comms[k], m->h[k]->stream);
+               })) {
+        std::vector<int> right(world, 0);
+        (void)multi_run(m, [&](int k) {
+            coreg_handle* h = m->h[k];
+            RETCHK(bind_device(h));
+            std::vector<double> got((size_t)world);
+            HIPCHK(hipMemcpy(got.data(), m->gat[k].p, (size_t)world * sizeof(double), hipMemcpyDeviceToHost));
+            right[k] = 1;
+            for (int j = 0; j < world; ++j)
+                if (got[(size_t)j] != (j + 1) * 1.5) right[k] = 0;
+            return COREG_OK;
+        });
+        if (std::find(right.begin(), right.end(), 0) == right.end()) return;
+        why = "self-test all-gather gave wrong values";
+    }
+    // (a group the helper gave up has left its reason; communicators it did not abort are destroyed)
+    give_up_comms(m->comms, false);
+    m->use_rccl = false;
+    if (!why.empty()) m->rccl_error = why;
+}
+
+// One communicator per device, created together (ncclCommInitAll: the single-process form), then tried (the self-test).
+// ncclCommInitAll runs on a helper thread, waited for with the self-test's limit: a bootstrap that never returns costs
+// this handle RCCL (host copies instead), never the process.  The thread owns its arguments (shared state), so that it
+// may outlive this function; it is detached only when it has not come back in time.
+void multi_init_comms(coreg_multi* m) {
+    struct InitState {
+        std::vector<ncclComm_t> comms;
+        std::vector<int> devs;
+        std::mutex mu;
+        std::condition_variable cv;
+        bool done = false;
+        bool abandoned = false;  // the creator gave up waiting: whatever the thread still obtains is its own to free
+        ncclResult_t rc = ncclSuccess;
+    };
+    auto st = std::make_shared<InitState>();
+    st->comms.assign(m->n, nullptr);
+    st->devs = m->devices;
+    std::thread init([st] {
+        const char* stall = std::getenv("COREG_RCCL_TEST_INIT_STALL_SECONDS");  // tests: a bootstrap that hangs
+        if (stall && std::atof(stall) > 0)
+            std::this_thread::sleep_for(std::chrono::milliseconds((long long)(std::atof(stall) * 1000)));
+        const ncclResult_t r = RcclApi::get().CommInitAll(st->comms.data(), (int)st->devs.size(), st->devs.data());
+        bool abandoned;
+        {
+            std::lock_guard<std::mutex> lk(st->mu);
+            st->rc = r;
+            st->done = true;
+            abandoned = st->abandoned;
+            st->cv.notify_all();
+        }
+        // nobody will ever use these communicators -- the late thread gives them back itself
+        // (abort: nothing is queued on them) instead of leaving them to process teardown
+        if (abandoned && r == ncclSuccess) give_up_comms(st->comms, true);
+    });
+    const double limit = wait_limit("COREG_RCCL_SELFTEST_SECONDS");
+    bool in_time;
+    {
+        std::unique_lock<std::mutex> lk(st->mu);
+        in_time = st->cv.wait_for(lk, std::chrono::milliseconds((long long)(limit * 1000)), [&] { return st->done; });
+        if (!in_time) st->abandoned = true;  // (under the lock: the thread either sees it or has already finished)
+    }
+    if (!in_time) {
+        // its communicators, if it ever gets them, are never used: it frees them itself.  Until it has come back the
+        // process should not count on a clean exit from inside RCCL's bootstrap (documented in include/coreg_hip.h)
+        init.detach();
+        m->rccl_error = "ncclCommInitAll did not return in time";
+    } else {
+        init.join();
+        if (st->rc == ncclSuccess) {
+            m->comms = st->comms;
+            m->use_rccl = true;
+            multi_rccl_selftest(m);  // a group that does not gather a known pattern is not used for results
+        } else {
+            m->rccl_error = "ncclCommInitAll failed";
+        }
+    }
 }
 
 }  // namespace
@@ -898,86 +904,17 @@ int coreg_multi_create(coreg_multi** out, int n_devices, const int* device_ids) 
     m->gat.resize(m->n);
     m->img.resize(m->n);
     for (int k = 0; k < m->n; ++k) m->w.emplace_back(new DeviceWorker());
-    std::vector<int> rc(m->n, COREG_OK);
-    for (int k = 0; k < m->n; ++k) m->w[k]->post([&, k] { rc[k] = coreg_create(&m->h[k], m->devices[k]); });
-    for (int k = 0; k < m->n; ++k) m->w[k]->wait();
-    for (int k = 0; k < m->n; ++k)
-        if (rc[k] != COREG_OK) {
-            const int r = rc[k];
-            coreg_multi_destroy(m);
-            return r;
-        }
-    // one communicator per device, created together (ncclCommInitAll: the single-process form).  COREG_MULTI_COLLECTIVE=host
-    // keeps RCCL out of it (the blocks then reach the host by one copy per device, a few KB each).
+    const int rc = multi_each(m, [&](int k) { return coreg_create(&m->h[k], m->devices[k]); });
+    if (rc != COREG_OK) {
+        coreg_multi_destroy(m);
+        return rc;
+    }
+    // COREG_MULTI_COLLECTIVE=host keeps RCCL out of it (the blocks then reach the host by one copy per device, a few KB each)
     const char* force = std::getenv("COREG_MULTI_FORCE_RCCL");
     const char* coll = std::getenv("COREG_MULTI_COLLECTIVE");
     const bool want_rccl = !(coll && std::string(coll) == "host");
     m->force_collective = m->n == 1 && force && std::atoi(force) == 1;
-    if (want_rccl && (m->n > 1 || m->force_collective) && distinct && RcclApi::get().ok()) {
-        // ncclCommInitAll on a helper thread, waited for with the self-test's limit: a bootstrap that never returns costs
-        // this handle RCCL (host copies instead), never the process.  The thread owns its arguments (shared state), so
-        // that it may outlive this function; it is detached only when it has not come back in time.
-        struct InitState {
-            std::vector<ncclComm_t> comms;
-            std::vector<int> devs;
-            std::mutex mu;
-            std::condition_variable cv;
-            bool done = false;
-            bool abandoned = false;  // the creator gave up waiting: whatever the thread still obtains is its own to free
-            ncclResult_t rc = ncclSuccess;
-        };
-        auto st = std::make_shared<InitState>();
-        st->comms.assign(m->n, nullptr);
-        st->devs = m->devices;
-        std::thread init([st] {
-            const char* stall = std::getenv("COREG_RCCL_TEST_INIT_STALL_SECONDS");  // tests: a bootstrap that hangs
-            if (stall && std::atof(stall) > 0)
-                std::this_thread::sleep_for(std::chrono::milliseconds((long long)(std::atof(stall) * 1000)));
-            const ncclResult_t r = RcclApi::get().CommInitAll(st->comms.data(), (int)st->devs.size(), st->devs.data());
-            bool abandoned;
-            {
-                std::lock_guard<std::mutex> lk(st->mu);
-                st->rc = r;
-                st->done = true;
-                abandoned = st->abandoned;
-                st->cv.notify_all();
-            }
-            if (abandoned && r == ncclSuccess) {
-                // nobody will ever use these communicators -- the late thread gives them back itself
-                // (abort: nothing is queued on them) instead of leaving them to process teardown
-                RcclApi& api = RcclApi::get();
-                for (ncclComm_t c : st->comms)
-                    if (c) {
-                        if (api.CommAbort) (void)api.CommAbort(c);
-                        else (void)api.CommDestroy(c);
-                    }
-                st->comms.clear();
-            }
-        });
-        const char* env = std::getenv("COREG_RCCL_SELFTEST_SECONDS");
-        const double limit = env && std::atof(env) > 0 ? std::atof(env) : 20.0;
-        bool in_time;
-        {
-            std::unique_lock<std::mutex> lk(st->mu);
-            in_time = st->cv.wait_for(lk, std::chrono::milliseconds((long long)(limit * 1000)), [&] { return st->done; });
-            if (!in_time) st->abandoned = true;  // (under the lock: the thread either sees it or has already finished)
-        }
-        if (!in_time) {
-            // its communicators, if it ever gets them, are never used: it frees them itself.  Until it has come back the
-            // process should not count on a clean exit from inside RCCL's bootstrap (documented in include/coreg_hip.h)
-            init.detach();
-            m->rccl_error = "ncclCommInitAll did not return in time";
-        } else {
-            init.join();
-            if (st->rc == ncclSuccess) {
-                m->comms = st->comms;
-                m->use_rccl = true;
-                multi_rccl_selftest(m);  // a group that does not gather a known pattern is not used for results
-            } else {
-                m->rccl_error = "ncclCommInitAll failed";
-            }
-        }
-    }
+    if (want_rccl && (m->n > 1 || m->force_collective) && distinct && RcclApi::get().ok()) multi_init_comms(m);
     m->collective = m->use_rccl ? "rccl" : (m->n > 1 ? "host-copy" : "none");
     *out = m;
     return COREG_OK;
@@ -997,9 +934,7 @@ void coreg_multi_destroy(coreg_multi* m) {
         });
         m->w[k]->wait();
     }
-    for (ncclComm_t c : m->comms)  // (empty when RCCL was never set up or has been given up)
-        if (c) (void)RcclApi::get().CommDestroy(c);
-    m->comms.clear();
+    give_up_comms(m->comms, false);  // (empty when RCCL was never set up or has been given up)
     for (int k = 0; k < m->n; ++k) {
         if (!m->h[k]) continue;
         m->w[k]->post([m, k] { coreg_destroy(m->h[k]); });
