@@ -78,6 +78,14 @@ class FitsTiled(C.Structure):
                 ("bscale", C.c_double), ("bzero", C.c_double)]
 
 
+class PixelsPlan(C.Structure):
+    """coreg_pixels_plan (include/coreg_hip.h)."""
+    _fields_ = [("ratio1", C.c_double), ("ratio2", C.c_double), ("lag_dx", C.POINTER(C.c_int32)),
+                ("lag_dy", C.POINTER(C.c_int32)), ("lag_drot", C.POINTER(C.c_double)), ("n_dx", C.c_int32),
+                ("n_dy", C.c_int32), ("n_rot", C.c_int32), ("sub_ny", C.c_int32), ("sub_nx", C.c_int32),
+                ("l0", C.c_int32), ("l1", C.c_int32), ("xc", C.c_int32), ("yc", C.c_int32)]
+
+
 def _is_tiled(img):
     """utils.fits_io.CompressedImage that the GPU can decode as it is (duck-typed)."""
     return hasattr(img, "tile_nbytes") and hasattr(img, "ztile") and getattr(img, "on_gpu", False)
@@ -277,6 +285,14 @@ SYMBOLS = [
       C.c_double, C.c_int64, C.c_int64, _P, C.c_int]),
     ("coreg_context_lag_headers", C.c_int,
      [_WP, _WP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _WP, _WP, _WP]),
+    # integer pixel-lag sweep (pxlshift.AlignmentPixels)
+    ("coreg_pixels_set_large", C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32]),
+    ("coreg_pixels_set_small", C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32]),
+    ("coreg_pixels_shift_large", C.c_int, [_P, C.c_double, C.c_double]),
+    ("coreg_pixels_sweep", C.c_int, [_P, C.POINTER(PixelsPlan), _P]),
+    ("coreg_pixels_get_large_box", C.c_int, [_P, _P]),
+    ("coreg_pixels_get_rotated", C.c_int, [_P, C.c_int32, _P]),
+    ("coreg_pixels_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     # all GPUs of the node from one process
     ("coreg_device_count", C.c_int, []),
     ("coreg_physical_device_count", C.c_int, []),
@@ -685,6 +701,56 @@ class CoregHandle(_ImageIntake):
         return out
 
     # -- multi-GPU point sharding (see include/coreg_hip.h, coreg_finalize_sums)
+    # -- integer pixel-lag sweep (pxlshift.AlignmentPixels): `plan` is the dict of AlignmentPixels.host_plan
+    def _pixels_set(self, fn, img):
+        img = np.ascontiguousarray(img)
+        if img.ndim != 2 or img.dtype not in (np.float32, np.float64):
+            raise ValueError("pixel-lag images must be 2-D float32/float64 arrays")
+        dt = COREG_F32 if img.dtype == np.float32 else COREG_F64
+        self._chk(fn(self._h, img.ctypes.data, dt, img.shape[0], img.shape[1]))
+
+    def pixels_set_large(self, img):
+        self._pixels_set(self._lib.coreg_pixels_set_large, img)
+
+    def pixels_set_small(self, img):
+        self._pixels_set(self._lib.coreg_pixels_set_small, img)
+
+    def pixels_shift_large(self, dx, dy):
+        self._chk(self._lib.coreg_pixels_shift_large(self._h, float(dx), float(dy)))
+
+    def pixels_sweep(self, plan):
+        dx = np.ascontiguousarray(plan["lag_dx"], dtype=np.int32)
+        dy = np.ascontiguousarray(plan["lag_dy"], dtype=np.int32)
+        rot = np.ascontiguousarray(plan["lag_drot_rad"], dtype=np.float64)
+        p = PixelsPlan(float(plan["ratio_res_1"]), float(plan["ratio_res_2"]),
+                       dx.ctypes.data_as(C.POINTER(C.c_int32)), dy.ctypes.data_as(C.POINTER(C.c_int32)),
+                       rot.ctypes.data_as(C.POINTER(C.c_double)), len(dx), len(dy), len(rot),
+                       int(plan["sub_shape"][0]), int(plan["sub_shape"][1]), int(plan["slc_small_ref"][0]),
+                       int(plan["slc_small_ref"][1]), int(plan["xc"]), int(plan["yc"]))
+        out = np.empty((len(dx), len(dy), len(rot)), dtype=np.float64)
+        rc = self._lib.coreg_pixels_sweep(self._h, C.byref(p), out.ctypes.data)
+        if rc == COREG_EINVAL:
+            msg = self._lib.coreg_last_error(self._h).decode("utf-8", "replace")
+            if msg.startswith("too large shift"):
+                raise ValueError(msg)
+        self._chk(rc)
+        return out
+
+    def pixels_get_large_box(self, shape):
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self._lib.coreg_pixels_get_large_box(self._h, out.ctypes.data))
+        return out
+
+    def pixels_get_rotated(self, k, shape):
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self._lib.coreg_pixels_get_rotated(self._h, int(k), out.ctypes.data))
+        return out
+
+    def pixels_last_timing(self) -> dict:
+        ms = (C.c_double * 3)()
+        self._chk(self._lib.coreg_pixels_last_timing(self._h, ms))
+        return {"prepare_ms": ms[0], "pass0_ms": ms[1], "pass1_ms": ms[2]}
+
     def set_point_shard(self, rank, world):
         self.set_option("shard_world", int(world))
         self.set_option("shard_rank", int(rank))

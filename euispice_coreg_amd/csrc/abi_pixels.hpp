@@ -1,0 +1,42 @@
+// Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the C ABI of the integer
+// pixel-lag sweep (include/coreg_hip.h).
+#pragma once
+
+extern "C" {
+
+int coreg_pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx) {
+    if (!h) return COREG_EINVAL;
+    return pixels_set_large(h, img, dtype, ny, nx);
+}
+
+int coreg_pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx) {
+    if (!h) return COREG_EINVAL;
+    return pixels_set_small(h, img, dtype, ny, nx);
+}
+
+int coreg_pixels_shift_large(coreg_handle* h, double dx, double dy) {
+    if (!h) return COREG_EINVAL;
+    return pixels_shift_large(h, dx, dy);
+}
+
+int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* corr_out) {
+    if (!h) return COREG_EINVAL;
+    return pixels_sweep(h, plan, corr_out);
+}
+
+int coreg_pixels_get_large_box(coreg_handle* h, double* out) {
+    if (!h) return COREG_EINVAL;
+    return pixels_get_large_box(h, out);
+}
+
+int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out) {
+    if (!h) return COREG_EINVAL;
+    return pixels_get_rotated(h, k, out);
+}
+
+int coreg_pixels_last_timing(coreg_handle* h, double* ms) {
+    if (!h) return COREG_EINVAL;
+    return pixels_last_timing(h, ms);
+}
+
+}  // extern "C"

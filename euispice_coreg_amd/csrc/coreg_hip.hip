@@ -38,6 +38,7 @@ using namespace coreg;
 #include "host_fix_lists.hpp"    // wcslib-decided border pixels / single samples
 #include "host_sweep_io.hpp"     // begin / end of a sweep call, stats, plan upload
 #include "host_context.hpp"      // iterative-context sweep: frame stack, per-lag plan, launches
+#include "host_pixels.hpp"       // integer pixel-lag sweep (pxlshift): state, resamples, the two passes
 
 
 // =====================================================================================================================
@@ -94,6 +95,7 @@ void coreg_destroy(coreg_handle* h) {
     }
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     context_release(h);
+    pixels_release(h);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
     for (int k = 0; k < 2; ++k) {
         h->pin_small[k].release();
@@ -242,6 +244,7 @@ int coreg_set_option(coreg_handle* h, const char* name, int64_t value) {
 #include "abi_sweeps.hpp"        // the sweeps, grid-shared sums, stats
 #include "abi_host.hpp"          // host-only helpers
 #include "abi_context.hpp"       // iterative-context sweep
+#include "abi_pixels.hpp"        // integer pixel-lag sweep (pxlshift)
 
 
 #include "multi.hpp"

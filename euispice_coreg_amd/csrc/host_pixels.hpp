@@ -1,0 +1,289 @@
+// Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the integer pixel-lag sweep
+// of pxlshift.AlignmentPixels -- per-handle state, uploads, the displacement of the large image, the
+// sub-resolved box, the rotation planes and the two sweep passes (csrc/kernels_pixels.hpp).
+#pragma once
+
+struct PixelsState {
+    DevBuf large, large_tmp, small, box, planes, sums, plan, corr;
+    int lW = 0, lH = 0, sW = 0, sH = 0;
+    int bW = 0, bH = 0, n_rot = 0;  // what the last sweep left in `box` / `planes`
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    bool timed = false;
+};
+
+namespace {
+std::mutex g_pixels_mutex;
+std::map<coreg_handle*, PixelsState*> g_pixels;  // (coreg_handle's own fields are those of the header-shift sweeps)
+}  // namespace
+
+static PixelsState* pixels_state(coreg_handle* h, bool create) {
+    std::lock_guard<std::mutex> lk(g_pixels_mutex);
+    auto it = g_pixels.find(h);
+    if (it != g_pixels.end()) return it->second;
+    if (!create) return nullptr;
+    PixelsState* st = new (std::nothrow) PixelsState();
+    if (st) g_pixels[h] = st;
+    return st;
+}
+
+// called by coreg_destroy with the handle's device current and its stream idle
+void pixels_release(coreg_handle* h) {
+    PixelsState* st = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_pixels_mutex);
+        auto it = g_pixels.find(h);
+        if (it == g_pixels.end()) return;
+        st = it->second;
+        g_pixels.erase(it);
+    }
+    DevBuf* bufs[] = {&st->large, &st->large_tmp, &st->small, &st->box, &st->planes, &st->sums, &st->plan, &st->corr};
+    for (DevBuf* b : bufs) b->release();
+    for (hipEvent_t e : st->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete st;
+}
+
+static int pixels_upload(coreg_handle* h, DevBuf& buf, const void* img, int dtype, int32_t ny, int32_t nx, int* W, int* H) {
+    if (!img || ny < 1 || nx < 1) return fail(h, COREG_EINVAL, "pixels: null image or empty shape");
+    if (dtype != COREG_F32 && dtype != COREG_F64) return fail(h, COREG_EINVAL, "pixels: dtype must be COREG_F32 or COREG_F64");
+    if (too_many(ny, nx)) return fail(h, COREG_EINVAL, "pixels: image too large");
+    RETCHK(bind_device(h));
+    const size_t n = (size_t)ny * nx;
+    HIPCHK(buf.reserve(n * sizeof(double)));
+    std::vector<double> conv;
+    const void* src = img;
+    if (dtype == COREG_F32) {
+        conv.resize(n);
+        const float* f = (const float*)img;
+        for (size_t q = 0; q < n; ++q) conv[q] = (double)f[q];
+        src = conv.data();
+    }
+    HIPCHK(hipMemcpyAsync(buf.p, src, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // (the caller's / the converted pixels are free again)
+    *W = nx;
+    *H = ny;
+    return COREG_OK;
+}
+
+static int pixels_resample(coreg_handle* h, int mode, const PixResample& a) {
+    const long long n = (long long)a.dW * a.dH;
+    const int nb = (int)std::min<long long>((n + kPixThreads - 1) / kPixThreads, 65535);
+    if (mode == PIX_AFFINE)
+        hipLaunchKernelGGL(k_pixels_resample<PIX_AFFINE>, dim3(nb), dim3(kPixThreads), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(k_pixels_resample<PIX_POLAR>, dim3(nb), dim3(kPixThreads), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return COREG_OK;
+}
+
+int pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx) {
+    PixelsState* st = pixels_state(h, true);
+    if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
+    st->bW = st->bH = 0;  // (the box of the last sweep is no longer this image's)
+    return pixels_upload(h, st->large, img, dtype, ny, nx, &st->lW, &st->lH);
+}
+
+int pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx) {
+    PixelsState* st = pixels_state(h, true);
+    if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
+    st->n_rot = 0;
+    return pixels_upload(h, st->small, img, dtype, ny, nx, &st->sW, &st->sH);
+}
+
+// alignment_pixels.py:86-107: an identity pass, then the pass at (x + dx, y + dy); fill -32762 -> NaN after each
+int pixels_shift_large(coreg_handle* h, double dx, double dy) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || !st->large.p) return fail(h, COREG_ESTATE, "pixels: the large image is not set");
+    if (!(dx == dx) || !(dy == dy)) return fail(h, COREG_EINVAL, "pixels: the displacement is not a number");
+    RETCHK(bind_device(h));
+    st->bW = st->bH = 0;
+    const size_t n = (size_t)st->lW * st->lH;
+    HIPCHK(st->large_tmp.reserve(n * sizeof(double)));
+    PixResample a = {};
+    a.sW = a.dW = st->lW;
+    a.sH = a.dH = st->lH;
+    a.ax = a.ay = 1.0;
+    a.fill = -32762.0;
+    a.src = st->large.as<double>();
+    a.dst = st->large_tmp.as<double>();
+    RETCHK(pixels_resample(h, PIX_AFFINE, a));
+    a.src = st->large_tmp.as<double>();
+    a.dst = st->large.as<double>();
+    a.bx = dx;
+    a.by = dy;
+    return pixels_resample(h, PIX_AFFINE, a);
+}
+
+int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, double* corr_out) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || !st->large.p || !st->small.p) return fail(h, COREG_ESTATE, "pixels: the large and the small image must be set");
+    if (!pl || !corr_out || !pl->lag_dx || !pl->lag_dy || !pl->lag_drot) return fail(h, COREG_EINVAL, "pixels: null pointer");
+    if (pl->n_dx < 1 || pl->n_dy < 1 || pl->n_rot < 1) return fail(h, COREG_EINVAL, "pixels: empty lag axis");
+    if (pl->n_dy > 65535 || pl->n_rot > 65535) return fail(h, COREG_EINVAL, "pixels: more than 65535 dy or rotation lags");
+    if (!(pl->ratio1 > 0.0) || !(pl->ratio2 > 0.0) || pl->sub_nx < 1 || pl->sub_ny < 1)
+        return fail(h, COREG_EINVAL, "pixels: ratios and sub-resolved shape must be positive");
+    const int w = st->sW, hh = st->sH;
+    const long long n_lag = (long long)pl->n_dx * pl->n_dy * pl->n_rot;
+    if (n_lag > (1ll << 28)) return fail(h, COREG_EINVAL, "pixels: too many lags");
+    int min_dx = pl->lag_dx[0], max_dx = min_dx, min_dy = pl->lag_dy[0], max_dy = min_dy;
+    for (int i = 0; i < pl->n_dx; ++i) {
+        min_dx = std::min(min_dx, pl->lag_dx[i]);
+        max_dx = std::max(max_dx, pl->lag_dx[i]);
+    }
+    for (int j = 0; j < pl->n_dy; ++j) {
+        min_dy = std::min(min_dy, pl->lag_dy[j]);
+        max_dy = std::max(max_dy, pl->lag_dy[j]);
+    }
+    // alignment_pixels.py:150-156, for every lag before any GPU work
+    if ((long long)pl->l0 + min_dy < 0 || (long long)pl->l0 + max_dy + hh > pl->sub_ny || (long long)pl->l1 + min_dx < 0 ||
+        (long long)pl->l1 + max_dx + w > pl->sub_nx)
+        return fail(h, COREG_EINVAL, "too large shift : outside FSI");
+    for (int k = 0; k < pl->n_rot; ++k)
+        if (!std::isfinite(pl->lag_drot[k])) return fail(h, COREG_EINVAL, "pixels: a rotation lag is not finite");
+    const int bW = w + (max_dx - min_dx), bH = hh + (max_dy - min_dy);
+    if (too_many(bW, bH) || too_many((long long)w * hh, pl->n_rot)) return fail(h, COREG_EINVAL, "pixels: work space too large");
+    RETCHK(bind_device(h));
+
+    // groups: runs of the dx list, at most kPixG entries, all within kPixG columns of the run's smallest
+    std::vector<PixGroup> groups;
+    for (int i = 0; i < pl->n_dx;) {
+        int lo = pl->lag_dx[i], hi = lo, n = 1;
+        while (i + n < pl->n_dx && n < kPixG) {
+            const int v = pl->lag_dx[i + n];
+            if (std::max(hi, v) - std::min(lo, v) > kPixG - 1) break;
+            lo = std::min(lo, v);
+            hi = std::max(hi, v);
+            ++n;
+        }
+        groups.push_back(PixGroup{i, n, lo, 0});
+        i += n;
+    }
+    const size_t n_groups = groups.size();
+    // plan on the device: groups, dx, dy
+    const size_t off_dx = n_groups * sizeof(PixGroup), off_dy = off_dx + (size_t)pl->n_dx * sizeof(int);
+    std::vector<unsigned char> blob(off_dy + (size_t)pl->n_dy * sizeof(int));
+    std::memcpy(blob.data(), groups.data(), off_dx);
+    std::memcpy(blob.data() + off_dx, pl->lag_dx, (size_t)pl->n_dx * sizeof(int));
+    std::memcpy(blob.data() + off_dy, pl->lag_dy, (size_t)pl->n_dy * sizeof(int));
+    HIPCHK(st->plan.reserve(blob.size()));
+    HIPCHK(st->box.reserve((size_t)bW * bH * sizeof(double)));
+    HIPCHK(st->planes.reserve((size_t)w * hh * pl->n_rot * sizeof(double)));
+    HIPCHK(st->sums.reserve((size_t)n_lag * 6 * sizeof(double)));
+    HIPCHK(st->corr.reserve((size_t)n_lag * sizeof(double)));
+    for (hipEvent_t& e : st->ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    st->timed = false;
+    HIPCHK(hipMemcpyAsync(st->plan.p, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipEventRecord(st->ev[0], h->stream));
+
+    // the part of the sub-resolved large image the lags can reach (alignment_pixels.py:126-143)
+    PixResample a = {};
+    a.src = st->large.as<double>();
+    a.sW = st->lW;
+    a.sH = st->lH;
+    a.dst = st->box.as<double>();
+    a.dW = bW;
+    a.dH = bH;
+    a.i0 = pl->l1 + min_dx;
+    a.j0 = pl->l0 + min_dy;
+    a.ax = pl->ratio1;
+    a.ay = pl->ratio2;
+    a.fill = -32768.0;
+    RETCHK(pixels_resample(h, PIX_AFFINE, a));
+    st->bW = bW;
+    st->bH = bH;
+    // rotation planes (alignment_pixels.py:72-81), each from the original
+    for (int k = 0; k < pl->n_rot; ++k) {
+        double* plane = st->planes.as<double>() + (size_t)k * w * hh;
+        if (pl->lag_drot[k] == 0.0) {
+            HIPCHK(hipMemcpyAsync(plane, st->small.p, (size_t)w * hh * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            continue;
+        }
+        PixResample r = {};
+        r.src = st->small.as<double>();
+        r.sW = r.dW = w;
+        r.sH = r.dH = hh;
+        r.dst = plane;
+        r.xc = (double)pl->xc;
+        r.yc = (double)pl->yc;
+        r.drot = pl->lag_drot[k];
+        r.fill = -32762.0;
+        RETCHK(pixels_resample(h, PIX_POLAR, r));
+    }
+    st->n_rot = pl->n_rot;
+    HIPCHK(hipEventRecord(st->ev[1], h->stream));
+
+    PixSweep s = {};
+    s.planes = st->planes.as<double>();
+    s.box = st->box.as<double>();
+    s.groups = (const PixGroup*)st->plan.p;
+    s.lag_dx = (const int*)((const unsigned char*)st->plan.p + off_dx);
+    s.lag_dy = (const int*)((const unsigned char*)st->plan.p + off_dy);
+    s.w = w;
+    s.h = hh;
+    s.bW = bW;
+    s.bH = bH;
+    s.n_dx = pl->n_dx;
+    s.n_dy = pl->n_dy;
+    s.min_dx = min_dx;
+    s.min_dy = min_dy;
+    s.cw = std::min(w, kPixTile);
+    s.bh = std::max(1, std::min(std::min(kPixBandRows, kPixTile / s.cw), hh));
+    double* sums0 = st->sums.as<double>();
+    double* sums1 = sums0 + 3 * n_lag;
+    const dim3 grid((unsigned)n_groups, (unsigned)pl->n_dy, (unsigned)pl->n_rot);
+    s.sums0 = nullptr;
+    s.sums = sums0;
+    hipLaunchKernelGGL(k_pixels_sweep<0>, grid, dim3(kPixThreads), 0, h->stream, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(st->ev[2], h->stream));
+    s.sums0 = sums0;
+    s.sums = sums1;
+    hipLaunchKernelGGL(k_pixels_sweep<1>, grid, dim3(kPixThreads), 0, h->stream, s);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(st->ev[3], h->stream));
+    hipLaunchKernelGGL(k_pixels_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0,
+                       h->stream, (const double*)sums0, (const double*)sums1, pl->n_dx, pl->n_dy, pl->n_rot,
+                       st->corr.as<double>());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_lag * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    st->timed = true;
+    return COREG_OK;
+}
+
+int pixels_last_timing(coreg_handle* h, double* ms) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || !st->timed) return fail(h, COREG_ESTATE, "pixels: no sweep has run");
+    if (!ms) return fail(h, COREG_EINVAL, "pixels: null pointer");
+    RETCHK(bind_device(h));
+    for (int k = 0; k < 3; ++k) {
+        float t = 0.f;
+        HIPCHK(hipEventElapsedTime(&t, st->ev[k], st->ev[k + 1]));
+        ms[k] = (double)t;
+    }
+    return COREG_OK;
+}
+
+static int pixels_read(coreg_handle* h, const void* dev, size_t n, double* out) {
+    if (!out) return fail(h, COREG_EINVAL, "pixels: null pointer");
+    RETCHK(bind_device(h));
+    HIPCHK(hipMemcpyAsync(out, dev, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return COREG_OK;
+}
+
+int pixels_get_large_box(coreg_handle* h, double* out) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || st->bW < 1) return fail(h, COREG_ESTATE, "pixels: no sweep has run");
+    return pixels_read(h, st->box.p, (size_t)st->bW * st->bH, out);
+}
+
+int pixels_get_rotated(coreg_handle* h, int32_t k, double* out) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || st->n_rot < 1) return fail(h, COREG_ESTATE, "pixels: no sweep has run");
+    if (k < 0 || k >= st->n_rot) return fail(h, COREG_EINVAL, "pixels: rotation index out of range");
+    const size_t n = (size_t)st->sW * st->sH;
+    return pixels_read(h, st->planes.as<double>() + n * k, n, out);
+}

@@ -27,3 +27,4 @@
 #include "kernels_fix.hpp"       // noise-decided samples: border / parity / tap scan + fix
 #include "kernels_finalize.hpp"  // k_finalize, k_refine_list, k_refine
 #include "kernels_context.hpp"   // iterative-context sweep (per-lag synthetic rasters)
+#include "kernels_pixels.hpp"    // integer pixel-lag sweep (pxlshift): resample, two-pass sweep, finalize

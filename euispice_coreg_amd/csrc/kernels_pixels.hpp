@@ -1,0 +1,209 @@
+// Part of csrc/kernels.hpp: the integer pixel-lag sweep (pxlshift.AlignmentPixels).
+//
+//   k_pixels_resample<MODE>   order-1 map_coordinates(mode='constant', prefilter=False) of a float64 image at an affine
+//                             (sub-resolution, identity, displacement) or polar (rotation plane) coordinate rule; a
+//                             sample outside the image, and every value equal to the fill, becomes NaN
+//   k_pixels_sweep<PASS>      one workgroup per (rotation plane, dy, group of <= 16 dx lags within 16 columns): pass 0
+//                             leaves n, sum a, sum b of the kept pixels per lag, pass 1 the centred sums about the
+//                             means of pass 0.  No atomics, no accumulation across workgroups: the sums of a lag depend
+//                             on the lag alone, not on the group it runs in
+//   k_pixels_finalize         float32-rounded numerator / sqrt(product of the centred squares), NaN for an empty or flat
+//                             overlap
+//
+// Reference arithmetic restated (paths relative to euispice_coreg/): pxlshift/alignment_pixels.py:38-55 (mask),
+// pxlshift/c_correlate.py:41-63 (Pearson, numerator stored as float32), :126-143 (sub-resolution), :72-81 +
+// utils/matrix_transform.py:78-106 (polar round trip), :86-107 (displacement of the large image).
+#pragma once
+namespace coreg {
+
+constexpr int kPixG = 16;         // dx lags per workgroup, all within kPixG columns of the group's first
+constexpr int kPixThreads = 256;
+constexpr int kPixTile = 2048;    // small-image pixels staged per band (8 per thread)
+constexpr int kPixBandRows = 64;  // rows per band at most: bounds the G - 1 extra columns of the large rows
+constexpr int kPixLdsB = kPixTile + kPixBandRows * (kPixG - 1);
+
+enum { PIX_AFFINE = 0, PIX_POLAR = 1 };
+
+struct PixResample {
+    const double* src;  // [sH][sW]
+    double* dst;        // [dH][dW]: destination pixel (j, i) is sample (j0 + j, i0 + i) of the rule
+    int sW, sH, dW, dH, i0, j0;
+    double ax, bx, ay, by;  // affine: x = i * ax + bx, y = j * ay + by
+    double xc, yc, drot;    // polar: rotation by drot [rad] about (xc, yc)
+    double fill;
+};
+
+// scipy's order-1 sample, products and additions in ni_interpolation.c's order ((pixel * wy) * wx, taps row by row, summed
+// from 0), so that an unrotated sample equals the reference's to the bit.  A tap one past the last pixel (coordinate
+// exactly n - 1, weight 0) is the mirrored pixel n - 2, through which a NaN still propagates.
+__device__ __forceinline__ double pixels_sample(const double* __restrict__ img, int W, int H, double x, double y, double fill) {
+#pragma clang fp contract(off)
+    if (!((x >= 0.0) & (x <= (double)(W - 1)) & (y >= 0.0) & (y <= (double)(H - 1)))) return fill;
+    const double fx = floor(x), fy = floor(y);
+    const double tx = x - fx, ty = y - fy;
+    const double wx[2] = {1.0 - tx, tx}, wy[2] = {1.0 - ty, ty};
+    const int x0 = (int)fx, y0 = (int)fy;
+    const int xs[2] = {x0, x0 + 1 < W ? x0 + 1 : (W > 1 ? W - 2 : 0)};
+    const int ys[2] = {y0, y0 + 1 < H ? y0 + 1 : (H > 1 ? H - 2 : 0)};
+    double t = 0.0;
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            double c = img[(size_t)ys[a] * W + xs[b]];
+            c = c * wy[a];
+            c = c * wx[b];
+            t = t + c;
+        }
+    return t;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kPixThreads) void k_pixels_resample(PixResample p) {
+#pragma clang fp contract(off)
+    const long long n = (long long)p.dW * p.dH;
+    for (long long q = (long long)blockIdx.x * kPixThreads + threadIdx.x; q < n; q += (long long)gridDim.x * kPixThreads) {
+        const int j = (int)(q / p.dW), i = (int)(q - (long long)j * p.dW);
+        const double gi = (double)(p.i0 + i), gj = (double)(p.j0 + j);
+        double x, y;
+        if (MODE == PIX_AFFINE) {
+            x = gi * p.ax + p.bx;
+            y = gj * p.ay + p.by;
+        } else {
+            const double ddx = gi - p.xc, ddy = gj - p.yc;
+            const double r = sqrt(ddx * ddx + ddy * ddy);
+            const double th = atan2(ddy, ddx) + p.drot;
+            x = r * cos(th) + p.xc;
+            y = r * sin(th) + p.yc;
+        }
+        const double v = pixels_sample(p.src, p.sW, p.sH, x, y, p.fill);
+        p.dst[q] = v == p.fill ? __builtin_nan("") : v;
+    }
+}
+
+// One group of dx lags: entries [first, first + count) of the dx list, every one within kPixG columns of dx_min.
+struct PixGroup {
+    int first, count, dx_min, pad;
+};
+
+struct PixSweep {
+    const double* planes;  // [n_rot][h][w]
+    const double* box;     // [bH][bW]: the sub-resolved large image from (slice origin + min lag) on
+    const PixGroup* groups;
+    const int* lag_dx;
+    const int* lag_dy;
+    const double* sums0;   // pass 1 reads: [n_rot][n_dy][n_dx][3] = n, sum a, sum b
+    double* sums;          // the pass's output, same layout
+    int w, h, bW, bH, n_dx, n_dy, min_dx, min_dy;
+    int cw, bh;            // band: columns [c0, c0 + cw) x rows [r0, r0 + bh), cw * bh <= kPixTile, bh <= kPixBandRows
+};
+
+template <int PASS>
+__global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
+    __shared__ double lds_a[kPixTile];
+    __shared__ double lds_b[kPixLdsB];
+    __shared__ double lds_red[kPixThreads / 64][3 * kPixG];
+    const int tid = threadIdx.x;
+    const PixGroup g = p.groups[blockIdx.x];
+    const int jy = blockIdx.y, kr = blockIdx.z;
+    const int row_off = p.lag_dy[jy] - p.min_dy;  // box row of the window's first row
+    const int col_off = g.dx_min - p.min_dx;      // box column of the group's first window's first column
+    const long long lag0 = ((long long)kr * p.n_dy + jy) * p.n_dx + g.first;
+    const double* plane = p.planes + (size_t)kr * p.w * p.h;
+
+    int off[kPixG];
+    double ma[kPixG], mb[kPixG];
+#pragma unroll
+    for (int s = 0; s < kPixG; ++s) {
+        const bool used = s < g.count;
+        off[s] = used ? p.lag_dx[g.first + s] - g.dx_min : 0;
+        ma[s] = mb[s] = 0.0;
+        if (PASS == 1 && used) {
+            const double* s0 = p.sums0 + 3 * (lag0 + s);
+            ma[s] = s0[1] / s0[0];
+            mb[s] = s0[2] / s0[0];
+        }
+    }
+    double acc0[kPixG], acc1[kPixG], acc2[kPixG];
+#pragma unroll
+    for (int s = 0; s < kPixG; ++s) acc0[s] = acc1[s] = acc2[s] = 0.0;
+
+    for (int r0 = 0; r0 < p.h; r0 += p.bh) {
+        const int nr = min(p.bh, p.h - r0);
+        for (int c0 = 0; c0 < p.w; c0 += p.cw) {
+            const int nc = min(p.cw, p.w - c0);
+            const int ncb = nc + kPixG - 1;
+            __syncthreads();  // the previous band has been read
+            for (int q = tid; q < nr * nc; q += kPixThreads) {
+                const int r = q / nc, c = q - r * nc;
+                lds_a[q] = plane[(size_t)(r0 + r) * p.w + c0 + c];
+            }
+            for (int q = tid; q < nr * ncb; q += kPixThreads) {
+                const int r = q / ncb, c = q - r * ncb;
+                const int bc = col_off + c0 + c;  // (columns past the box belong to unused slots only)
+                lds_b[q] = bc < p.bW ? p.box[(size_t)(row_off + r0 + r) * p.bW + bc] : 0.0;
+            }
+            __syncthreads();
+            for (int q = tid; q < nr * nc; q += kPixThreads) {
+                const int r = q / nc, c = q - r * nc;
+                const double a = lds_a[q];
+                const double* brow = lds_b + r * ncb + c;
+                const bool a_ok = a == a;
+#pragma unroll
+                for (int s = 0; s < kPixG; ++s) {
+                    const double b = brow[off[s]];
+                    const bool keep = a_ok & (b == b);
+                    if (PASS == 0) {
+                        acc0[s] += keep ? 1.0 : 0.0;
+                        acc1[s] += keep ? a : 0.0;
+                        acc2[s] += keep ? b : 0.0;
+                    } else {
+                        const double da = a - ma[s], db = b - mb[s];
+                        acc0[s] += keep ? da * db : 0.0;
+                        acc1[s] += keep ? da * da : 0.0;
+                        acc2[s] += keep ? db * db : 0.0;
+                    }
+                }
+            }
+        }
+    }
+    // lanes of a wave, then the four waves in a fixed order
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int s = 0; s < kPixG; ++s) {
+        double v0 = acc0[s], v1 = acc1[s], v2 = acc2[s];
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) {
+            v0 += __shfl_down(v0, d, 64);
+            v1 += __shfl_down(v1, d, 64);
+            v2 += __shfl_down(v2, d, 64);
+        }
+        if (lane == 0) {
+            lds_red[wave][3 * s + 0] = v0;
+            lds_red[wave][3 * s + 1] = v1;
+            lds_red[wave][3 * s + 2] = v2;
+        }
+    }
+    __syncthreads();
+    if (tid < 3 * g.count) {
+        double v = lds_red[0][tid];
+#pragma unroll
+        for (int k = 1; k < kPixThreads / 64; ++k) v += lds_red[k][tid];
+        p.sums[3 * lag0 + tid] = v;
+    }
+}
+
+// corr[(i * n_dy + j) * n_rot + k] from the sums of lag (k, j, i)
+__global__ __launch_bounds__(kPixThreads) void k_pixels_finalize(const double* __restrict__ sums0, const double* __restrict__ sums1,
+                                                                  int n_dx, int n_dy, int n_rot, double* __restrict__ corr) {
+    const long long n = (long long)n_dx * n_dy * n_rot;
+    const long long q = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (q >= n) return;
+    const int i = (int)(q % n_dx), j = (int)((q / n_dx) % n_dy), k = (int)(q / ((long long)n_dx * n_dy));
+    const double cnt = sums0[3 * q], num = sums1[3 * q], va = sums1[3 * q + 1], vb = sums1[3 * q + 2];
+    double r = __builtin_nan("");
+    if (cnt > 0.0 && va != 0.0 && vb != 0.0) r = (double)(float)num / sqrt(va * vb);
+    corr[((long long)i * n_dy + j) * n_rot + k] = r;
+}
+
+}  // namespace coreg

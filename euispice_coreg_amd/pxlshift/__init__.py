@@ -1,0 +1,2 @@
+from .alignment_pixels import AlignmentPixels, align_pixels_shift  # noqa: F401
+from .alignment_spice_pixel import AlignmentSpicePixel  # noqa: F401

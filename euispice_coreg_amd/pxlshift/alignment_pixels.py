@@ -1,0 +1,156 @@
+"""
+`AlignmentPixels` -- drop-in for euispice_coreg.pxlshift.AlignmentPixels (pxlshift/alignment_pixels.py:14-157): the
+large image is brought to the small image's pixel size and the small image is slid over it in whole pixels, and
+rotated about its centre, one masked Pearson coefficient per (dx, dy, drot).  The whole lag cube is one library call
+(include/coreg_hip.h: coreg_pixels_sweep); what is not per-pixel work -- ratios, shapes, slice, bounds, the displacement
+of `shift_solar_rotation_dx_large` -- is `host_plan`, numpy only and callable without a GPU.
+
+Differences from the reference, all deliberate:
+  * a second `find_best_parameters` call starts from the file's pixels again (the reference sub-resolves the already
+    sub-resolved image);
+  * a lag whose window leaves the sub-resolved image raises the reference's ValueError before any work is done (the
+    reference raises it when its loop gets there);
+  * an unknown `unit_rot` raises ValueError (the reference dies on an unbound name).
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from .. import _lib
+from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
+
+
+def _integer_lags(v, name):
+    a = np.atleast_1d(np.asarray(v))
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError(f"{name} must be a non-empty 1-D array")
+    if a.dtype.kind in "iu":
+        return a.astype(np.int64)
+    if a.dtype.kind == "f" and np.all(np.isfinite(a)) and np.all(a == np.rint(a)):
+        return a.astype(np.int64)
+    raise TypeError(f"{name}: slice indices must be integers")
+
+
+class AlignmentPixels:
+
+    def __init__(self, large_fov_known_pointing, window_large, small_fov_to_correct, window_small, device=None):
+        data, hdr = fits_io.read_image(large_fov_known_pointing, window_large)
+        self.hdr_large = fits_io.Header(hdr).copy()
+        self.data_large = np.array(fits_io.native_pixels(data), dtype=np.float64)
+        data, hdr = fits_io.read_image(small_fov_to_correct, window_small)
+        self.hdr_small = fits_io.Header(hdr).copy()
+        self.data_small = np.array(fits_io.native_pixels(data), dtype=np.float64)
+        self.device = device
+        self.slc_small_ref = None
+        self.ratio_res_1 = self.ratio_res_2 = None
+        self.last_timing = None
+
+    # ------------------------------------------------------------------------------------------------------------
+    def _return_shift_large_fov_solar_rotation(self):
+        """alignment_pixels.py:109-124: apparent solar rotation between the two exposures [arcsec]."""
+        hl = self.hdr_large
+        band = hl["WAVELNTH"]
+        B0 = np.deg2rad(hl["SOLAR_B0"])
+        omega_car = np.deg2rad(360 / 25.38 / 86400)
+        if band == 174:
+            band = 171
+        omega = omega_car + spice_header.diff_rot(B0, f"EIT {band}")
+        Rsun, Dsun = hl["RSUN_REF"], hl["DSUN_OBS"]
+        phi = np.rad2deg(omega * Rsun / (Dsun - Rsun)) * 3600
+        # (astropy's Time difference: whole days and day fractions apart, then to seconds)
+        day_s, frac_s = spice_header._mjd_parts(self.hdr_small["DATE-AVG"])
+        day_l, frac_l = spice_header._mjd_parts(hl["DATE-AVG"])
+        dt = ((day_s - day_l) + (frac_s - frac_l)) * 86400.0
+        return dt * phi
+
+    def _shift_large_fov_displacement(self):
+        """alignment_pixels.py:91-99: (dx, dy) in pixels of the large image."""
+        hl = self.hdr_large
+        dcrval = self._return_shift_large_fov_solar_rotation()
+        d1 = float(hdrutil.convert(dcrval, "arcsec", hl["CUNIT1"]))
+        if "CROTA" in hl:
+            theta = np.deg2rad(hl["CROTA"])
+            d2 = float(hdrutil.convert(dcrval, "arcsec", hl["CUNIT2"]))
+            return float((d1 / hl["CDELT1"]) * np.cos(-theta)), float((d2 / hl["CDELT2"]) * np.sin(-theta))
+        return float(d1 / hl["CDELT1"]), 0.0
+
+    def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False) -> dict:
+        """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU)."""
+        dx, dy = _integer_lags(lag_dx, "lag_dx"), _integer_lags(lag_dy, "lag_dy")
+        drot = np.atleast_1d(np.asarray(lag_drot, dtype=np.float64))
+        if drot.ndim != 1 or drot.size == 0:
+            raise ValueError("lag_drot must be a non-empty 1-D array")
+        if unit_rot == "degree":
+            drot_rad = np.radians(drot)
+        elif unit_rot == "radian":
+            drot_rad = drot.copy()
+        else:
+            raise ValueError("unit_rot must be 'degree' or 'radian'")
+        hs, hl = self.hdr_small, self.hdr_large
+        ratio1 = float(hdrutil.convert(hs["CDELT1"], hs["CUNIT1"], hl["CUNIT1"])) / hl["CDELT1"]
+        ratio2 = float(hdrutil.convert(hs["CDELT2"], hs["CUNIT2"], hl["CUNIT2"])) / hl["CDELT2"]
+        if not (ratio1 > 0 and ratio2 > 0):
+            raise ValueError("the pixel sizes of the two images must have the same sign")
+        H, W = self.data_large.shape
+        h, w = self.data_small.shape
+        sub = (len(np.arange(0, H, ratio2)), len(np.arange(0, W, ratio1)))
+        l = [int((sub[n] - (h, w)[n] - 1) / 2) for n in range(2)]
+        # alignment_pixels.py:150-156, for every lag
+        if (l[0] + dy.min() < 0 or l[0] + h + dy.max() > sub[0] or l[1] + dx.min() < 0 or l[1] + w + dx.max() > sub[1]):
+            raise ValueError("too large shift : outside FSI")
+        plan = {"lag_dx": dx, "lag_dy": dy, "lag_drot": drot, "lag_drot_rad": drot_rad, "unit_rot": unit_rot,
+                "ratio_res_1": float(ratio1), "ratio_res_2": float(ratio2), "sub_shape": sub, "slc_small_ref": tuple(l),
+                "xc": round(w / 2), "yc": round(h / 2), "shift_large": None}
+        if shift_solar_rotation_dx_large:
+            plan["shift_large"] = self._shift_large_fov_displacement()
+        return plan
+
+    def find_best_parameters(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False):
+        """alignment_pixels.py:57-84: correlation cube [len(lag_dx), len(lag_dy), len(lag_drot)], float64."""
+        plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large)
+        self.lag_dx, self.lag_dy, self.lag_drot, self.unit_rot = lag_dx, lag_dy, lag_drot, unit_rot
+        self.ratio_res_1, self.ratio_res_2 = plan["ratio_res_1"], plan["ratio_res_2"]
+        l, (h, w) = plan["slc_small_ref"], self.data_small.shape
+        self.slc_small_ref = (slice(l[0], l[0] + h), slice(l[1], l[1] + w))
+        hnd = _lib.shared_handle(-1 if self.device is None else self.device)
+        # every call starts from the file's pixels
+        hnd.pixels_set_large(self.data_large)
+        hnd.pixels_set_small(self.data_small)
+        if plan["shift_large"] is not None:
+            dx, dy = plan["shift_large"]
+            hnd.pixels_shift_large(dx, dy)
+            print(f"corrected solar rotation on FSI on CRVAL1: {dx=}, {dy=}")
+        corr = hnd.pixels_sweep(plan)
+        self.last_timing = hnd.pixels_last_timing()
+        self._last_plan = plan
+        return corr
+
+    # read-backs of the last call's device images (tests, inspection)
+    def _large_box(self):
+        p = self._last_plan
+        h, w = self.data_small.shape
+        shape = (h + int(p["lag_dy"].max() - p["lag_dy"].min()), w + int(p["lag_dx"].max() - p["lag_dx"].min()))
+        return _lib.shared_handle(-1 if self.device is None else self.device).pixels_get_large_box(shape)
+
+    def _rotated(self, k):
+        return _lib.shared_handle(-1 if self.device is None else self.device).pixels_get_rotated(k, self.data_small.shape)
+
+
+def align_pixels_shift(delta_pix1, delta_pix2, windows, large_fov_fits_path, large_fov_window, small_fov_path):
+    """Util.AlignCommonUtil.align_pixels_shift (utils/Util.py:248-278): the header of the small image's window with
+    CRVAL at the large image's centre plus (delta_pix1, delta_pix2) of its own pixels, CRPIX at its own centre.  As the
+    reference, it returns the header of the last window of `windows`."""
+    header_fsi = fits_io.Header(fits_io.read_header(large_fov_fits_path, large_fov_window))
+    w_fsi = wcs_tan.TanWcs(header_fsi)
+    naxis1, naxis2 = w_fsi.naxis
+    lon_mid, lat_mid = w_fsi.pixel_to_world(np.array([(naxis1 - 1) / 2]), np.array([(naxis2 - 1) / 2]))
+    out = None
+    for win in windows:
+        out = fits_io.Header(fits_io.read_header(small_fov_path, win)).copy()
+        n1 = out["ZNAXIS1"] if "ZNAXIS1" in out else out["NAXIS1"]
+        n2 = out["ZNAXIS2"] if "ZNAXIS2" in out else out["NAXIS2"]
+        out["CRVAL1"] = float(hdrutil.convert(lon_mid[0], "deg", out["CUNIT1"])) + delta_pix1 * out["CDELT1"]
+        out["CRVAL2"] = float(hdrutil.convert(lat_mid[0], "deg", out["CUNIT2"])) + delta_pix2 * out["CDELT2"]
+        out["CRPIX1"] = (n1 + 1) / 2
+        out["CRPIX2"] = (n2 + 1) / 2
+    return out

@@ -1,0 +1,75 @@
+"""
+`AlignmentSpicePixel` -- drop-in for euispice_coreg.pxlshift.AlignmentSpicePixel
+(pxlshift/alignment_spice_pixel.py:9-101): the small image is a SPICE L2 window summed over wavelength between the
+slit edges, with a 2-D header in degrees whose CDELT1 is shortened by the apparent solar rotation during one raster
+step; the sweep is `AlignmentPixels.find_best_parameters`.  Level-3 input raises NotImplementedError.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from ..utils import fits_io, header as hdrutil, spice_header
+from .alignment_pixels import AlignmentPixels
+
+
+class AlignmentSpicePixel(AlignmentPixels):
+
+    def __init__(self, fsi_path, fsi_window, spice_path, spice_window, index_amplitude=None, device=None):
+        self.fsi_path, self.spice_path = fsi_path, spice_path
+        self.fsi_window, self.spice_window = fsi_window, spice_window
+        name = spice_path if isinstance(spice_path, str) else ""
+        if "L2" in name:
+            level = 2
+        elif "L3" in name:
+            raise NotImplementedError("AlignmentSpicePixel: level-3 input is not implemented (the pixel-lag sweep takes "
+                                      "SPICE L2 windows)")
+        else:
+            raise ValueError("the SPICE level is read from the file name: it must contain 'L2'")
+        data, hdr = fits_io.read_image(fsi_path, fsi_window)
+        self.hdr_large = fits_io.Header(hdr).copy()
+        self.data_large = np.array(fits_io.native_pixels(data), dtype=np.float64)
+        self.device = device
+        self.slc_small_ref = None
+        self.ratio_res_1 = self.ratio_res_2 = None
+        self.last_timing = None
+        self._extract_spice_data_header(level=level, index_amplitude=index_amplitude)
+
+    def _extract_spice_data_header(self, level, index_amplitude=None):
+        """alignment_spice_pixel.py:29-45."""
+        cube, hdr = fits_io.open_cube(self.spice_path, self.spice_window)
+        hdr = fits_io.Header(hdr)
+        dt = hdr["PC4_1"]
+        self._prepare_spice_from_l2(cube, hdr)
+        for k in ("SOLAR_B0", "RSUN_REF", "DSUN_OBS"):
+            self.hdr_small[k] = hdr[k]
+        self._correct_solar_rotation(dt)
+
+    def _correct_solar_rotation(self, dt):
+        """alignment_spice_pixel.py:47-62: CDELT1 -= dt * (apparent rotation rate), with the SPICE header's own B0,
+        RSUN_REF and DSUN_OBS."""
+        h = self.hdr_small
+        B0 = np.deg2rad(h["SOLAR_B0"])
+        band = self.hdr_large["WAVELNTH"]
+        omega_car = np.deg2rad(360 / 25.38 / 86400)
+        if band == 174:
+            band = 171
+        omega = omega_car + spice_header.diff_rot(B0, f"EIT {band}")
+        Rsun, Dsun = h["RSUN_REF"], h["DSUN_OBS"]
+        phi = np.rad2deg(omega * Rsun / (Dsun - Rsun)) * 3600  # arcsec / s
+        h["CDELT1"] = float(h["CDELT1"] - hdrutil.convert(dt * phi, "arcsec", h["CUNIT1"]))
+
+    def _prepare_spice_from_l2(self, cube, hdr):
+        """alignment_spice_pixel.py:64-86."""
+        cube = np.asarray(cube)
+        if cube.ndim != 4:
+            raise ValueError("a SPICE L2 window is a 4-D cube [time, wavelength, y, x]")
+        ymin, ymax = spice_header.vertical_edges_limits(hdr)
+        self.hdr_small = spice_header.celestial_header(hdr)
+        ylen = cube.shape[2]
+        ylim = max(ymin, ylen - ymax - 1)
+        # (a reduction over the outer axis adds the planes one after another, as the reference's nansum does)
+        self.data_small = np.nansum(np.asarray(cube[0][:, ylim:(ylen - ylim), :], dtype=np.float64), axis=0)
+        self.hdr_small["CRPIX1"] = (self.data_small.shape[1] + 1) / 2
+        self.hdr_small["CRPIX2"] = (self.data_small.shape[0] + 1) / 2
+        self.hdr_small["NAXIS1"] = self.data_small.shape[1]
+        self.hdr_small["NAXIS2"] = self.data_small.shape[0]

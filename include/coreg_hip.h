@@ -525,6 +525,43 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
                               double d_crval2, double d_cdelt1, double d_cdelt2, double d_crota, int cdelt_semantics,
                               coreg_wcs2d* ctx, coreg_wcs2d* grid, coreg_wcs2d* shifted);
 
+/* Integer pixel-lag sweep (pxlshift.AlignmentPixels, pxlshift/alignment_pixels.py:14-157): the large image is
+ * sub-resolved to the small image's pixel size (order 1, fill -32768 -> NaN), and for every (dx, dy, drot) the small
+ * image -- rotated about its centre by a polar round trip for drot != 0 (order 1, fill -32762 -> NaN), always from the
+ * original -- is correlated with the window of the sub-resolved image at rows l0 + dy ..., columns l1 + dx ...: masked
+ * Pearson coefficient about the means of the kept pixels, the numerator rounded to float32 before the division
+ * (pxlshift/c_correlate.py:51-61), NaN for an empty or flat overlap.  Two deterministic passes (csrc/kernels_pixels.hpp);
+ * the result of a lag does not depend on the other lags of the call.  All calls run on the handle's stream and return
+ * with their work complete as far as the caller's memory is concerned.
+ *   coreg_pixels_set_large / _set_small  host pixels [ny][nx], dtype COREG_F32 / COREG_F64; kept as float64
+ *   coreg_pixels_shift_large             alignment_pixels.py:86-107 on the resident large image, at file resolution: an
+ *                                        identity order-1 pass, then one at (x + dx, y + dy); fill -32762 -> NaN after each
+ *   coreg_pixels_sweep                   corr_out[n_dx][n_dy][n_rot], C order.  COREG_EINVAL with the reference's text
+ *                                        "too large shift : outside FSI" when a lag's window leaves the sub-resolved image
+ *                                        (checked for every lag before any GPU work)
+ *   coreg_pixels_get_large_box           the part of the sub-resolved image the last sweep could read:
+ *                                        [h + max dy - min dy][w + max dx - min dx] from (l0 + min dy, l1 + min dx) on
+ *   coreg_pixels_get_rotated             plane k [h][w] of the last sweep
+ *   coreg_pixels_last_timing             ms[3]: preparation (box + planes), pass 0, pass 1 of the last sweep (HIP events) */
+typedef struct coreg_pixels_plan {
+    double ratio1, ratio2;    /* sample k of the sub-resolved image lies at x = k ratio1, y = k ratio2 of the large image:
+                                 CDELTi(small, in the large image's unit) / CDELTi(large)                              */
+    const int32_t* lag_dx;    /* [n_dx] columns                                                                        */
+    const int32_t* lag_dy;    /* [n_dy] rows                                                                           */
+    const double* lag_drot;   /* [n_rot] radians; exactly 0: the unrotated image                                       */
+    int32_t n_dx, n_dy, n_rot;
+    int32_t sub_ny, sub_nx;   /* shape of the sub-resolved image: len(np.arange(0, n, ratio)) per axis                 */
+    int32_t l0, l1;           /* slice origin (row, column): int((N_sub - n_small - 1) / 2)                            */
+    int32_t xc, yc;           /* rotation centre: round(w / 2), round(h / 2), halves to even                           */
+} coreg_pixels_plan;
+int coreg_pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx);
+int coreg_pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx);
+int coreg_pixels_shift_large(coreg_handle* h, double dx, double dy);
+int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* corr_out);
+int coreg_pixels_get_large_box(coreg_handle* h, double* out);
+int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out);
+int coreg_pixels_last_timing(coreg_handle* h, double* ms);
+
 /* ---- All GPUs of the node from ONE process ------------------------------------------------------------------------
  * The reference's `Alignment(..., parallelism=True, counts_cpu_max=N)` uses the whole machine from a plain
  * `python script.py`: its lag loop is fanned out over a process pool (hdrshift/alignment.py:692-744, README.md:47-87).
