@@ -1,5 +1,6 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order; round 6 split by concern,
-// no behaviour change): C ABI: coreg_sweep_carrington / coreg_sweep_helioprojective, grid-shared sums, pivots, stats.
+// no behaviour change): C ABI: coreg_sweep_carrington / coreg_sweep_helioprojective (each launch described by a SweepLaunchSpec),
+// grid-shared sums, pivots, stats.
 #pragma once
 namespace {
 // ---- the steps every sweep shares ---------------------------------------------------------------------------------
@@ -113,6 +114,21 @@ int precompute(coreg_handle* h, const PrecomputeArgs& pa, int n_tiles, int n_gro
     return COREG_OK;
 }
 
+// The launch of `call` whose slots start at slot `slot_off` of the uploaded plan; the entry point adds what only it has
+// (car_inv, fix, pitch_sel).
+SweepLaunchSpec sweep_launch(const SweepCall& call, int mode, size_t slot_off, int n_batches, int n_tiles) {
+    SweepLaunchSpec sl;
+    sl.mode = mode;
+    sl.order = call.order;
+    sl.method = call.method;
+    sl.slot_off = slot_off;
+    sl.n_batches = n_batches;
+    sl.n_tiles = n_tiles;
+    sl.lag_begin = call.lag_begin;
+    sl.out_dev = call.out_dev;
+    return sl;
+}
+
 // k_finalize of pending launch `pf` of a grid-shared sweep, from the reduced sums (work-space pointers taken afresh: a
 // later launch of the sweep may have grown the buffers)
 int finalize_pending(coreg_handle* h, const coreg_handle::PendingFinalize& pf, long long* refine_count, double* out_dev,
@@ -131,8 +147,7 @@ int finalize_pending(coreg_handle* h, const coreg_handle::PendingFinalize& pf, l
     f->out = out_dev;
     f->residus = pf.residus;
     f->n_required = (long long)h->gW * h->gH;
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)((pf.n_slots + kFinSlots - 1) / kFinSlots)),
-                       dim3(kFinSlots * kFinLanes), 0, h->stream, *f);
+    launch_finalize(h, *f);
     return COREG_OK;
 }
 }  // namespace
@@ -271,11 +286,9 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
             pa.dlat += row_slip;
         }
         RETCHK(precompute<MODE_TRANSLATE>(h, pa, n_tiles, pick_groups(h, L.n_batches, n_tiles), L.n_batches));
-        // SoA block of this launch starts at 2 * slot_off doubles (every earlier launch contributed 2 per slot)
-        RETCHK(launch_sweep(h, MODE_TRANSLATE, order, method, h->lane_params.as<double>() + 2 * L.slot_off,
-                            h->out_index.as<long long>() + L.slot_off, L.n_batches, n_tiles, lag_begin, call.out_dev,
-                            nullptr, nullptr, (long long)L.slot_off,
-                            pick_pitch(h, plan, h->opt_use_lds ? lds_window_elems(h) : 0, order)));
+        SweepLaunchSpec sl = sweep_launch(call, MODE_TRANSLATE, L.slot_off, L.n_batches, n_tiles);
+        sl.pitch_sel = pick_pitch(h, plan, h->opt_use_lds ? lds_window_elems(h) : 0, order);
+        RETCHK(launch_sweep(h, sl));
     }
     return close_sweep(h, call);
 }
@@ -458,9 +471,9 @@ static int sweep_car(coreg_handle* h, const SweepCall& call, const coreg_wcs2d* 
             std::memset(&pi.car_fwd, 0, sizeof(pi.car_fwd));
             RETCHK(precompute<MODE_HOMOGRAPHY>(h, pi, n_tiles, pick_groups(h, 1, n_tiles), 1));
             last_groups = last_batches = -1;  // (the compacted points now hold pixel indices, not unit vectors)
-            RETCHK(launch_sweep(h, MODE_HOMOGRAPHY, order, call.method, h->lane_params.as<double>() + 9 * L.slot_off,
-                                h->out_index.as<long long>() + L.slot_off, 1, n_tiles, call.lag_begin, call.out_dev, nullptr,
-                                &id_fix, (long long)L.slot_off));
+            SweepLaunchSpec sl = sweep_launch(call, MODE_HOMOGRAPHY, L.slot_off, 1, n_tiles);
+            sl.fix = &id_fix;
+            RETCHK(launch_sweep(h, sl));
             continue;
         }
         // the work partition (k_tile_list) depends on the group count of the launch: redo it only when that changes
@@ -477,9 +490,10 @@ static int sweep_car(coreg_handle* h, const SweepCall& call, const coreg_wcs2d* 
                 [&](int slot) { return shifted(L.hc, L.i1[(size_t)slot], L.i2[(size_t)slot]); }, &tap,
                 h->lane_params.as<double>() + 9 * L.slot_off, &L.inv, &pa.car_fwd));
         }
-        RETCHK(launch_sweep(h, MODE_CAR, order, call.method, h->lane_params.as<double>() + 9 * L.slot_off,
-                            h->out_index.as<long long>() + L.slot_off, L.n_batches, n_tiles, call.lag_begin, call.out_dev,
-                            &L.inv, L.tap_any ? &tap : nullptr, (long long)L.slot_off));
+        SweepLaunchSpec sl = sweep_launch(call, MODE_CAR, L.slot_off, L.n_batches, n_tiles);
+        sl.car_inv = &L.inv;
+        sl.fix = L.tap_any ? &tap : nullptr;
+        RETCHK(launch_sweep(h, sl));
     }
     return close_sweep(h, call);
 }
@@ -703,9 +717,10 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
             },
             &fix));
     trace("sweep_helioprojective: single-sample scan done");
-    RETCHK(launch_sweep(h, sweep_mode, order, method, h->lane_params.as<double>(), h->out_index.as<long long>(), n_batches,
-                        n_tiles, lag_begin, call.out_dev, nullptr, &fix, 0,
-                        pick_pitch(h, plan, h->opt_use_lds ? lds_window_elems(h) : 0, order)));
+    SweepLaunchSpec sl = sweep_launch(call, sweep_mode, 0, n_batches, n_tiles);
+    sl.fix = &fix;
+    sl.pitch_sel = pick_pitch(h, plan, h->opt_use_lds ? lds_window_elems(h) : 0, order);
+    RETCHK(launch_sweep(h, sl));
     return close_sweep(h, call);
 }
 
@@ -795,15 +810,8 @@ int coreg_finalize_sums(coreg_handle* h, const double* sums, int sums_on_device,
             RETCHK(pf.replay_precompute(h));
             points_of = ip;
         }
-        RefineArgs rf2 = rf;
-        if (!pf.fixes.empty()) {
-            // the launch's noise-decided samples about the flagged slots' own pivots (as launch_sweep does on one GPU)
-            HIPCHK(h->rf_fix_slab.reserve((size_t)kNumSums * pf.n_slots * sizeof(double)));
-            HIPCHK(hipMemsetAsync(h->rf_fix_slab.p, 0, (size_t)kNumSums * pf.n_slots * sizeof(double), h->stream));
-            rf2.fix_slab = h->rf_fix_slab.as<double>();
-            RETCHK(launch_fix_kernels(h, pf.fixes, h->rf_fix_slab.as<double>(), rf.slot_pivots, rf.flags));
-        }
-        RETCHK(launch_refine(h, rf2, pf.n_slots, f.out_index, pf.lag_begin, out_dev, false));
+        // (with the launch's noise-decided samples about the flagged slots' own pivots, as launch_sweep does on one GPU)
+        RETCHK(refine_with_fixes(h, rf, pf.fixes, pf.n_slots, f.out_index, pf.lag_begin, out_dev));
     }
     HIPCHK(hipGetLastError());
     if (!out_on_device && n_out > 0) {

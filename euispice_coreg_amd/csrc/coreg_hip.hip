@@ -17,6 +17,8 @@
 #include <string>
 #include <thread>
 #include <functional>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "fit.hpp"
@@ -33,8 +35,9 @@ using namespace coreg;
 #include "host_state.hpp"        // buffers, FixLaunch, coreg_handle
 #include "host_upload.hpp"       // uploads, FITS decode, reference crop
 #include "host_plan.hpp"         // lag batching, tiles, groups, precompute
-#include "host_fix_launch.hpp"   // re-evaluation work space, fix kernels of a launch
-#include "host_sweep_launch.hpp" // launch_sweep
+#include "host_fix_launch.hpp"   // re-evaluation work space, k_finalize, fix kernels of a launch
+#include "sweep_variant.hpp"     // the list of k_sweep instantiations and the rule that picks one (no HIP in it)
+#include "host_sweep_launch.hpp" // SweepLaunchSpec, launch_sweep
 #include "host_fix_lists.hpp"    // wcslib-decided border pixels / single samples
 #include "host_sweep_io.hpp"     // begin / end of a sweep call, stats, plan upload
 #include "host_context.hpp"      // iterative-context sweep: frame stack, per-lag plan, launches

@@ -306,8 +306,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
             r.out_index = f.out_index;
             r.lag_begin = lag_begin;
             r.out = out_dev;
-            hipLaunchKernelGGL(k_finalize, dim3((unsigned)((ns_ + kFinSlots - 1) / kFinSlots)), dim3(kFinThreads), 0,
-                               h->stream, f);
+            launch_finalize(h, f);
             if (r.enabled) {
                 hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, r, ns_, h->counters.as<long long>());
                 context_types(c->f32, h->small_f32, [&](auto frame, auto spice) {

@@ -1,5 +1,6 @@
-// Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order; round 6 split by concern,
-// no behaviour change): noise-decided samples, launch side: work space of the re-evaluation, the fix kernels of one launch.
+// Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): noise-decided samples
+// (DESIGN 4b), launch side: the fixes of a launch as the planner leaves them (BorderFix), work space of the re-evaluation,
+// the one k_finalize launch, the fix kernels of one launch, and their second run with k_refine.
 #pragma once
 namespace {
 struct BorderFix {  // lag-points of a launch whose border pixels are decided by wcslib's rounding noise
@@ -10,11 +11,8 @@ struct BorderFix {  // lag-points of a launch whose border pixels are decided by
     };
     std::vector<Item> items;
     std::vector<int> pixels;  // concatenated linear grid indices (host copy of h->border_dev)
-    // single samples near an integer coordinate (odd spline orders): device arrays ready for k_tap_fix
-    int tap_segs = 0;
-    int tap_mode = 0;
-    long long tap_count = 0;
-    TapFixArgs tap = {};
+    TapFix tap;  // single samples near an integer coordinate (odd spline orders): device arrays ready for k_tap_fix
+    bool any() const { return !items.empty() || tap.segs > 0; }
 };
 
 // work space + arguments of the re-evaluation of ill-conditioned lag-points (kernels.hpp: RefineArgs) for a launch of
@@ -53,56 +51,67 @@ int fill_refine(coreg_handle* h, RefineArgs* r, int mode, int order, const doubl
     return COREG_OK;
 }
 
-// after a k_finalize that has written the flags: list the flagged slots (one block), re-evaluate them and overwrite their
-// coefficients (the last block of k_refine).  Two launches, no host round trip; with nothing flagged (the normal case)
-// every block leaves at once.
-int launch_refine(coreg_handle* h, const RefineArgs& r0, long long n_slots, const long long* outidx_dev,
-                  long long lag_begin, double* out_dev, bool list = true) {
-    RefineArgs r = r0;
-    r.out_index = outidx_dev;
-    r.lag_begin = lag_begin;
-    r.out = out_dev;
-    if (list) hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, r, n_slots, h->counters.as<long long>());
-    hipLaunchKernelGGL(k_refine, dim3(kRefineBlocks), dim3(kRefineThreads), 0, h->stream, r, n_slots);
-    HIPCHK(hipGetLastError());
-    return COREG_OK;
+// k_finalize over the n_slots lag slots of `f`: the one place that knows its launch geometry
+void launch_finalize(coreg_handle* h, const FinalizeArgs& f) {
+    hipLaunchKernelGGL(k_finalize, dim3((unsigned)((f.n_slots + kFinSlots - 1) / kFinSlots)), dim3(kFinThreads), 0, h->stream, f);
+}
+
+// fn(TS()) with TS the element type of the image to align (float or double), as context_types
+template <typename Fn>
+void with_pixel_type(bool f32, Fn fn) {
+    if (f32) fn(float());
+    else fn(double());
 }
 
 // the fix kernels of one launch (FixLaunch) into `slab`; slot_pivots / only_flagged: the second run (kernels.hpp:
 // BorderFixArgs)
 int launch_fix_kernels(coreg_handle* h, const FixLaunch& fl, double* slab, const double* slot_pivots, const int* only_flagged) {
-    for (BorderFixArgs b : fl.border) {
-        b.slab = slab;
-        b.slot_pivots = slot_pivots;
-        b.only_flagged = only_flagged;
-        if (fl.small_f32) hipLaunchKernelGGL((k_border_fix<float>), dim3(1), dim3(256), 0, h->stream, b);
-        else hipLaunchKernelGGL((k_border_fix<double>), dim3(1), dim3(256), 0, h->stream, b);
-    }
-    for (ParityFixArgs p : fl.parity) {
-        p.slab = slab;
-        p.slot_pivots = slot_pivots;
-        p.only_flagged = only_flagged;
-        if (fl.small_f32) hipLaunchKernelGGL((k_parity_fix<float>), dim3(p.n_partial), dim3(256), 0, h->stream, p);
-        else hipLaunchKernelGGL((k_parity_fix<double>), dim3(p.n_partial), dim3(256), 0, h->stream, p);
-        hipLaunchKernelGGL(k_parity_fix_final, dim3(1), dim3(64), 0, h->stream, p);
-    }
-    if (fl.have_tap) {
-        TapFixArgs t = fl.tap;
-        t.slab = slab;
-        t.slot_pivots = slot_pivots;
-        t.only_flagged = only_flagged;
-        const dim3 tg((unsigned)fl.tap_segs), tb(256);
-        if (fl.tap_mode == MODE_CAR) {
-            if (fl.small_f32) hipLaunchKernelGGL((k_tap_fix<float, MODE_CAR>), tg, tb, 0, h->stream, t);
-            else hipLaunchKernelGGL((k_tap_fix<double, MODE_CAR>), tg, tb, 0, h->stream, t);
-        } else if (fl.tap_mode == MODE_HOMOGRAPHY_SERIES) {
-            if (fl.small_f32) hipLaunchKernelGGL((k_tap_fix<float, MODE_HOMOGRAPHY_SERIES>), tg, tb, 0, h->stream, t);
-            else hipLaunchKernelGGL((k_tap_fix<double, MODE_HOMOGRAPHY_SERIES>), tg, tb, 0, h->stream, t);
-        } else {
-            if (fl.small_f32) hipLaunchKernelGGL((k_tap_fix<float, MODE_HOMOGRAPHY>), tg, tb, 0, h->stream, t);
-            else hipLaunchKernelGGL((k_tap_fix<double, MODE_HOMOGRAPHY>), tg, tb, 0, h->stream, t);
+    auto second_run = [&](auto args) {
+        args.slab = slab;
+        args.slot_pivots = slot_pivots;
+        args.only_flagged = only_flagged;
+        return args;
+    };
+    with_pixel_type(fl.small_f32, [&](auto ts) {
+        using TS = decltype(ts);
+        for (const BorderFixArgs& b : fl.border)
+            hipLaunchKernelGGL((k_border_fix<TS>), dim3(1), dim3(256), 0, h->stream, second_run(b));
+        for (const ParityFixArgs& p0 : fl.parity) {
+            const ParityFixArgs p = second_run(p0);
+            hipLaunchKernelGGL((k_parity_fix<TS>), dim3(p.n_partial), dim3(256), 0, h->stream, p);
+            hipLaunchKernelGGL(k_parity_fix_final, dim3(1), dim3(64), 0, h->stream, p);
         }
+        if (fl.tap.segs > 0) {
+            const TapFixArgs t = second_run(fl.tap.args);
+            const dim3 tg((unsigned)fl.tap.segs), tb(256);
+            if (fl.tap.mode == MODE_CAR) hipLaunchKernelGGL((k_tap_fix<TS, MODE_CAR>), tg, tb, 0, h->stream, t);
+            else if (fl.tap.mode == MODE_HOMOGRAPHY_SERIES)
+                hipLaunchKernelGGL((k_tap_fix<TS, MODE_HOMOGRAPHY_SERIES>), tg, tb, 0, h->stream, t);
+            else hipLaunchKernelGGL((k_tap_fix<TS, MODE_HOMOGRAPHY>), tg, tb, 0, h->stream, t);
+        }
+    });
+    HIPCHK(hipGetLastError());
+    return COREG_OK;
+}
+
+// After a k_finalize that has written the flags and a k_refine_list that has listed the flagged slots: the launch's
+// noise-decided samples (if it has any) about the flagged slots' OWN pivots into a slab of their own (kernels that leave
+// at once unless the slot is flagged), then k_refine re-evaluates the listed slots, adds that slab and overwrites their
+// coefficients (its last block).  No host round trip; with nothing flagged (the normal case) every block leaves at once.
+// launch_sweep on one GPU, coreg_finalize_sums on every rank of a grid-shared sweep.
+int refine_with_fixes(coreg_handle* h, RefineArgs r, const FixLaunch& fixes, long long n_slots,
+                      const long long* outidx_dev, long long lag_begin, double* out_dev) {
+    if (!fixes.empty()) {
+        const size_t bytes = (size_t)kNumSums * n_slots * sizeof(double);
+        HIPCHK(h->rf_fix_slab.reserve(bytes));
+        HIPCHK(hipMemsetAsync(h->rf_fix_slab.p, 0, bytes, h->stream));
+        r.fix_slab = h->rf_fix_slab.as<double>();
+        RETCHK(launch_fix_kernels(h, fixes, h->rf_fix_slab.as<double>(), r.slot_pivots, r.flags));
     }
+    r.out_index = outidx_dev;
+    r.lag_begin = lag_begin;
+    r.out = out_dev;
+    hipLaunchKernelGGL(k_refine, dim3(kRefineBlocks), dim3(kRefineThreads), 0, h->stream, r, n_slots);
     HIPCHK(hipGetLastError());
     return COREG_OK;
 }

@@ -301,16 +301,16 @@ int prepare_tap_fix(coreg_handle* h, int sweep_mode, int order, const coreg_wcs2
     HIPCHK(hipMemcpy(h->tap_pixel.p, pixel.data(), (size_t)count * sizeof(unsigned), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->tap_xw.p, xw.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(h->tap_yw.p, yw.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
-    fix->tap_segs = n_seg;
-    fix->tap_count = (long long)count;
-    fix->tap_mode = sweep_mode;
-    fix->tap.seg_slot = h->tap_seg_slot.as<int>();
-    fix->tap.seg_begin = h->tap_seg_begin.as<int>();
-    fix->tap.pixel = h->tap_pixel.as<unsigned>();
-    fix->tap.xw = h->tap_xw.as<double>();
-    fix->tap.yw = h->tap_yw.as<double>();
-    fix->tap.cu = a.cu;
-    fix->tap.fwd = a.fwd;
+    fix->tap.segs = n_seg;
+    fix->tap.count = (long long)count;
+    fix->tap.mode = sweep_mode;
+    fix->tap.args.seg_slot = h->tap_seg_slot.as<int>();
+    fix->tap.args.seg_begin = h->tap_seg_begin.as<int>();
+    fix->tap.args.pixel = h->tap_pixel.as<unsigned>();
+    fix->tap.args.xw = h->tap_xw.as<double>();
+    fix->tap.args.yw = h->tap_yw.as<double>();
+    fix->tap.args.cu = a.cu;
+    fix->tap.args.fwd = a.fwd;
     h->tap_last[1] = n_seg;
     return COREG_OK;
 }

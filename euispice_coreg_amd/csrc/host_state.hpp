@@ -92,19 +92,24 @@ struct EventPair {
 // own pivots (launch_sweep, coreg_finalize_sums).  The device lists the arguments point to live until the next sweep.
 // (a launch's single-sample lists kept past the next launch of the same sweep: grid-shared plate-carree sweeps)
 struct KeptTapLists {
-    DevBuf all;  // the five lists of TapFixArgs, one after another (launch_sweep)
+    DevBuf all;  // the five lists of TapFixArgs, one after another (keep_tap_lists)
     ~KeptTapLists() { all.release(); }
+};
+// single samples near an integer coordinate: the device lists k_tap_fix reads (prepare_tap_fix fills them into the
+// BorderFix of a launch, build_fix_launch adds the fields every fix kernel shares)
+struct TapFix {
+    TapFixArgs args = {};
+    int segs = 0;         // lag-points listed = workgroups of k_tap_fix; 0: no single-sample pass
+    int mode = 0;         // sweep mode the coordinates were scanned under (k_tap_fix<TS, mode>)
+    long long count = 0;  // entries of the lists
 };
 struct FixLaunch {
     std::vector<BorderFixArgs> border;
     std::vector<ParityFixArgs> parity;
-    TapFixArgs tap = {};
-    bool have_tap = false;
-    int tap_segs = 0, tap_mode = 0;
-    long long tap_count = 0;  // entries of the lists
+    TapFix tap;
     std::shared_ptr<KeptTapLists> kept;
     bool small_f32 = true;
-    bool empty() const { return border.empty() && parity.empty() && !have_tap; }
+    bool empty() const { return border.empty() && parity.empty() && tap.segs == 0; }
 };
 
 struct ContextState;  // frames and work space of the iterative-context sweep (host_context.hpp)
@@ -200,7 +205,6 @@ struct coreg_handle {
     long long sums_slots = 0;  // slots of the pending sharded sweep (all its launches)
     struct PendingFinalize {
         long long slot_off, n_slots, lag_begin;
-        const long long* outidx_dev;
         int residus;
         // what coreg_finalize_sums needs to re-evaluate the ill-conditioned lag-points of this launch once the ranks' sums
         // are added (the flags come from the REDUCED sums): the launch's refine arguments and, when later launches of the

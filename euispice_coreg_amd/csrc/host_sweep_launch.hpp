@@ -1,20 +1,78 @@
-// Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order; round 6 split by concern,
-// no behaviour change): launch_sweep: k_sweep dispatch by (mode, order, pixel type, pitch), the fix slab, k_finalize, re-evaluation of flagged lag-points.
+// Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): one sweep launch, from "the
+// plan is on the device" to "coefficients are in out" -- its description (SweepLaunchSpec), the k_sweep variant it runs
+// (sweep_variant.hpp) out of the table of instantiations, its fix kernels, k_finalize, and the re-evaluation of flagged
+// lag-points or, for a grid-shared sweep, the PendingFinalize that coreg_finalize_sums finishes.
 #pragma once
 namespace {
-int launch_sweep(coreg_handle* h, int mode, int order, int method, const double* params_dev,
-                 const long long* outidx_dev, int n_batches, int n_tiles, long long lag_begin, double* out_dev,
-                 const LaunchU* car_inv = nullptr, const BorderFix* fix = nullptr, long long sums_off = 0,
-                 int pitch_sel = 0) {
-    const long long n_slots = (long long)n_batches * kBlock;
-    const int n_groups = pick_groups(h, n_batches, n_tiles);
-    const bool sharded = h->opt_shard_world > 1;
-    const int g_per = sharded ? n_groups / (int)h->opt_shard_world : n_groups;  // groups swept by this launch
-    const int g_lo = sharded ? g_per * (int)h->opt_shard_rank : 0;
-    // (the border correction is a property of the lag-point, not of a share of the grid: rank 0 carries it)
-    const bool fixing = fix && (!fix->items.empty() || fix->tap_segs > 0) && (!sharded || h->opt_shard_rank == 0);
-    HIPCHK(h->partials.reserve((size_t)(g_per + (fixing ? 1 : 0)) * kNumSums * n_slots * sizeof(double)));
+using sweep_variant::SweepVariant;
+static_assert(sweep_variant::kTranslate == MODE_TRANSLATE && sweep_variant::kHomography == MODE_HOMOGRAPHY &&
+                  sweep_variant::kHomographySeries == MODE_HOMOGRAPHY_SERIES && sweep_variant::kCar == MODE_CAR &&
+                  sweep_variant::kOrderRt == ORDER_RT, "sweep_variant.hpp restates the kernels' constants");
 
+// One sweep launch: n_batches x kBlock lag slots (padding included) of the uploaded plan, from slot `slot_off` on, over
+// the compacted points of the precompute launch before it.
+struct SweepLaunchSpec {
+    int mode = MODE_TRANSLATE;  // TRANSLATE = Carrington (float64 samples); HOMOGRAPHY[_SERIES], CAR = helioprojective
+    int order = 2;
+    int method = COREG_METHOD_CORRELATION;
+    // first slot in the plan: h->out_index and, in a grid-shared sweep, h->sums count slots; h->lane_params holds one
+    // SoA block [2 or 9][n_slots] per launch, one after another
+    size_t slot_off = 0;
+    int n_batches = 0, n_tiles = 0;
+    long long lag_begin = 0;
+    double* out_dev = nullptr;
+    const LaunchU* car_inv = nullptr;  // MODE_CAR: the launch's native -> pixel map
+    const BorderFix* fix = nullptr;    // noise-decided samples of the launch
+    int pitch_sel = 0;                 // compile-time LDS window pitch asked for (pick_pitch), 0: per visit
+    long long n_slots() const { return (long long)n_batches * kBlock; }
+    bool residus() const { return method == COREG_METHOD_RESIDUS; }
+    const double* params_dev(const coreg_handle* h) const {
+        return h->lane_params.as<double>() + (mode == MODE_TRANSLATE ? 2 : 9) * slot_off;
+    }
+    const long long* outidx_dev(const coreg_handle* h) const { return h->out_index.as<long long>() + slot_off; }
+};
+
+// ---- the k_sweep variant of a launch ------------------------------------------------------------------------------
+struct SweepKernel {
+    void (*fn)(const SweepArgs);
+    size_t attr_bytes[kMaxDevices];  // per device: the largest dynamic-LDS size the function attribute was raised to
+};
+template <size_t... I>
+SweepKernel* sweep_kernel_table(std::index_sequence<I...>) {
+    constexpr const SweepVariant* v = sweep_variant::kSweepVariants.v;
+    static SweepKernel table[] = {
+        {k_sweep<v[I].mode, v[I].order, std::conditional_t<v[I].f32, float, double>, v[I].round, v[I].resid, v[I].pitch>, {0}}...};
+    return table;
+}
+
+// per instantiation and device: raise the dynamic-LDS limit once, not per launch (handles of several threads share the
+// function attribute, hence the lock)
+int raise_dynamic_lds(coreg_handle* h, SweepKernel* k, size_t lds_bytes) {
+    std::lock_guard<std::mutex> lock(g_attr_mutex);
+    size_t& ab = k->attr_bytes[h->device % kMaxDevices];
+    if (lds_bytes > 48 * 1024 && lds_bytes > ab) {
+        HIPCHK(hipFuncSetAttribute((const void*)k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        ab = lds_bytes;
+    }
+    return COREG_OK;
+}
+
+int launch_k_sweep(coreg_handle* h, const SweepLaunchSpec& L, const SweepArgs& a, dim3 grid, size_t lds_bytes) {
+    const SweepVariant v = sweep_variant::pick_sweep_variant(L.mode, L.order, h->small_f32, L.residus(), L.pitch_sel);
+    const int at = sweep_variant::sweep_variant_index(v);
+    if (at < 0) return fail(h, COREG_EINVAL, "launch_sweep: no k_sweep instantiation for this mode / order / pitch");
+    SweepKernel* k = sweep_kernel_table(std::make_index_sequence<sweep_variant::kNumSweepVariants>()) + at;
+    EventPair* ev = next_event(h, h->ev_sweep, h->ev_sweep_used);
+    if (!ev) return fail(h, COREG_EHIP, "hipEventCreate failed");
+    RETCHK(raise_dynamic_lds(h, k, lds_bytes));
+    HIPCHK(hipEventRecord(ev->a, h->stream));
+    hipLaunchKernelGGL(k->fn, grid, dim3(kSweepThreads), lds_bytes, h->stream, a);
+    HIPCHK(hipEventRecord(ev->b, h->stream));
+    HIPCHK(hipGetLastError());
+    return COREG_OK;
+}
+
+SweepArgs sweep_args(const coreg_handle* h, const SweepLaunchSpec& L, int n_groups, int group_lo, size_t lds_bytes) {
     SweepArgs a;
     a.img = h->small.p;
     a.W = h->sW;
@@ -26,281 +84,189 @@ int launch_sweep(coreg_handle* h, int mode, int order, int method, const double*
     a.group_first = h->group_first.as<int>();
     a.tile_info = h->tile_info.as<long long>();
     a.tile_bbox = h->tile_bbox.as<double>();
-    a.lane_params = params_dev;
-    a.n_slots = n_slots;
-    a.n_batches = n_batches;
+    a.lane_params = L.params_dev(h);
+    a.n_slots = L.n_slots();
+    a.n_batches = L.n_batches;
     a.n_groups = n_groups;
-    a.group_lo = g_lo;
+    a.group_lo = group_lo;
     a.partials = h->partials.as<double>();
     a.pivots = h->pivots.as<double>();
     a.use_lds = h->opt_use_lds ? 1 : 0;
     a.clean_path = h->opt_clean_path ? 1 : 0;
+    a.lds_elems = (int)(lds_bytes / sizeof(double));
+    a.car_inv = L.car_inv ? *L.car_inv : LaunchU{};
+    a.car_inv.order_rt = L.order;
+    a.car_inv.h_incr = (int)h->opt_h_incr;
+    return a;
+}
+
+// ---- the noise-decided samples of a launch as kernel arguments ------------------------------------------------------
+// the fields the three fix kernels' arguments share (BorderFixArgs, ParityFixArgs, TapFixArgs)
+template <typename Args>
+void fill_fix_common(Args& x, const coreg_handle* h, const SweepLaunchSpec& L) {
+    x.img = h->small.p;
+    x.W = h->sW;
+    x.H = h->sH;
+    x.ref = h->ref.p;
+    x.ref_f32 = h->ref_dtype == COREG_F32 ? 1 : 0;
+    x.gw = h->gW;
+    x.order = L.order;
+    x.round_f32 = L.mode == MODE_TRANSLATE ? 0 : 1;
+    x.residus = L.residus() ? 1 : 0;
+    x.pivots = h->pivots.as<double>();
+    x.hom = L.params_dev(h);  // SoA [9][n_slots]: the (snapped) map of the slot gives the sample coordinates
+    x.n_slots = L.n_slots();
+}
+
+// L.fix as FixLaunch: built on every rank of a grid-shared sweep (the re-evaluation of a flagged lag-point runs on every
+// rank), run by launch_sweep on the rank that carries the correction
+int build_fix_launch(coreg_handle* h, const SweepLaunchSpec& L, FixLaunch* fl) {
+    fl->small_f32 = h->small_f32;
+    if (!L.fix || !L.fix->any()) return COREG_OK;
+    for (const BorderFix::Item& it : L.fix->items) {
+        if (it.flags_off >= 0) {
+            // odd spline order: re-decide the tap set of every pixel of this lag-point (k_parity_fix), after
+            // k_border_fix has set the slab entry (same stream)
+            ParityFixArgs p = {};
+            fill_fix_common(p, h, L);
+            p.flags = h->border_flags.as<unsigned char>() + it.flags_off;
+            p.gh = h->gH;
+            p.slot = it.slot;
+            p.n_partial = 256;
+            if (h->fix_partial.reserve((size_t)p.n_partial * kNumSums * sizeof(double)) != hipSuccess)
+                return fail(h, COREG_EHIP, "hipMalloc failed (parity fix)");
+            p.partial = h->fix_partial.as<double>();
+            fl->parity.push_back(p);
+        }
+        if (it.n == 0) continue;
+        BorderFixArgs b = {};
+        fill_fix_common(b, h, L);
+        b.slot = it.slot;
+        b.dropped = h->border_dev.as<int>() + it.first;
+        b.n_dropped = it.n;
+        fl->border.push_back(b);
+    }
+    if (L.fix->tap.segs > 0) {
+        fl->tap = L.fix->tap;
+        fill_fix_common(fl->tap.args, h, L);
+    }
+    return COREG_OK;
+}
+
+// A plate-carree sweep has one launch per combination and every launch lists its single samples anew in the handle's
+// buffers: a grid-shared launch's lists are COPIED so that coreg_finalize_sums can run the fix kernels a second time
+// about the flagged slots' pivots, as FixLaunch lets it do for the one-launch helioprojective sweeps.  Rare path
+// (unrotated maps, single-axis lags).  One allocation, the five lists at 8-byte-rounded offsets; the copies are ordered
+// on the handle's stream after the kernels that read the sources, and the next launch's prepare_tap_fix waits for that
+// stream before it writes the sources again.
+int keep_tap_lists(coreg_handle* h, FixLaunch* fixes) {
+    auto kept = std::make_shared<KeptTapLists>();
+    const size_t nseg = (size_t)fixes->tap.segs, cnt = (size_t)fixes->tap.count;
+    TapFixArgs& t = fixes->tap.args;
+    const void* src[5] = {t.xw, t.yw, t.pixel, t.seg_begin, t.seg_slot};
+    const size_t bytes[5] = {cnt * sizeof(double), cnt * sizeof(double), cnt * sizeof(unsigned), (nseg + 1) * sizeof(int),
+                             nseg * sizeof(int)};
+    size_t off[6] = {0};
+    for (int k = 0; k < 5; ++k) off[k + 1] = off[k] + ((bytes[k] + 7) & ~(size_t)7);
+    HIPCHK(kept->all.reserve(off[5]));
+    char* all = kept->all.as<char>();
+    for (int k = 0; k < 5; ++k)
+        if (bytes[k]) HIPCHK(hipMemcpyAsync(all + off[k], src[k], bytes[k], hipMemcpyDeviceToDevice, h->stream));
+    t.xw = (const double*)(all + off[0]);
+    t.yw = (const double*)(all + off[1]);
+    t.pixel = (const unsigned*)(all + off[2]);
+    t.seg_begin = (const int*)(all + off[3]);
+    t.seg_slot = (const int*)(all + off[4]);
+    fixes->kept = kept;
+    return COREG_OK;
+}
+
+// A launch of a grid-shared sweep leaves its six sums per slot in h->sums; what coreg_finalize_sums needs to finish it
+// from the REDUCED sums is queued here (the extra slab is inside those sums; the second run of the fix kernels happens on
+// every rank).
+int queue_pending_finalize(coreg_handle* h, const SweepLaunchSpec& L, const RefineArgs& refine, bool refinable,
+                           const FixLaunch& fl) {
+    coreg_handle::PendingFinalize pf;
+    pf.slot_off = (long long)L.slot_off;
+    pf.n_slots = L.n_slots();
+    pf.lag_begin = L.lag_begin;
+    pf.residus = L.residus() ? 1 : 0;
+    pf.refine = refine;
+    pf.refine.enabled = refinable ? 1 : 0;
+    pf.replay_precompute = h->last_precompute;
+    pf.fixes = fl;
+    if (L.mode == MODE_CAR && fl.tap.segs > 0) RETCHK(keep_tap_lists(h, &pf.fixes));
+    h->pending_fin.push_back(pf);
+    return COREG_OK;
+}
+
+// ---- the launch ---------------------------------------------------------------------------------------------------
+int launch_sweep(coreg_handle* h, const SweepLaunchSpec& L) {
+    // work space: one slab of six sums per slot and tile group of this launch's share of the grid, one more for the
+    // noise-decided samples (a property of the lag-point, not of a share of the grid: rank 0 carries it)
+    const long long n_slots = L.n_slots();
+    const int n_groups = pick_groups(h, L.n_batches, L.n_tiles);
+    const bool sharded = h->opt_shard_world > 1;
+    const int g_per = sharded ? n_groups / (int)h->opt_shard_world : n_groups;  // groups swept by this launch
+    const int g_lo = sharded ? g_per * (int)h->opt_shard_rank : 0;
+    const bool fixing = L.fix && L.fix->any() && (!sharded || h->opt_shard_rank == 0);
+    HIPCHK(h->partials.reserve((size_t)(g_per + (fixing ? 1 : 0)) * kNumSums * n_slots * sizeof(double)));
+    double* fix_slab = fixing ? h->partials.as<double>() + (size_t)g_per * kNumSums * n_slots : nullptr;
     // the dynamic LDS also carries the end-of-kernel point-group reduction: (kPointGroups-1) x 6 x 256 doubles
     const size_t lds_min = (size_t)(kPointGroups - 1) * kNumSums * kBlock * sizeof(double);
-    const size_t lds_bytes = std::max(lds_min, a.use_lds ? (size_t)h->opt_lds_bytes : 0);
-    a.lds_elems = (int)(lds_bytes / sizeof(double));
-    std::memset(&a.car_inv, 0, sizeof(a.car_inv));
-    if (car_inv) a.car_inv = *car_inv;
-    a.car_inv.order_rt = order;
-    a.car_inv.h_incr = (int)h->opt_h_incr;
+    const size_t lds_bytes = std::max(lds_min, h->opt_use_lds ? (size_t)h->opt_lds_bytes : 0);
 
-    const dim3 grid((unsigned)((long long)g_per * n_batches)), block(kSweepThreads);
+    const SweepArgs a = sweep_args(h, L, n_groups, g_lo, lds_bytes);
     RETCHK(join_small(h));  // the first kernel of the call that reads the image to align
     trace("launch_sweep: launching k_sweep");
-    EventPair* ev = next_event(h, h->ev_sweep, h->ev_sweep_used);
-    if (!ev) return fail(h, COREG_EHIP, "hipEventCreate failed");
-#define SWP(M, O, TS, R, Q, P)                                                                                       \
-    do {                                                                                                              \
-        {                                                                                                             \
-            /* per instantiation and device: raise the dynamic-LDS limit once, not per launch (handles of several  */ \
-            /* threads share the function attribute, hence the lock)                                                */ \
-            static size_t attr_bytes[kMaxDevices] = {0};                                                              \
-            std::lock_guard<std::mutex> lock(g_attr_mutex);                                                           \
-            size_t& ab = attr_bytes[h->device % kMaxDevices];                                                         \
-            if (lds_bytes > 48 * 1024 && lds_bytes > ab) {                                                            \
-                HIPCHK(hipFuncSetAttribute((const void*)(k_sweep<M, O, TS, R, Q, P>),                                 \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));              \
-                ab = lds_bytes;                                                                                       \
-            }                                                                                                         \
-        }                                                                                                             \
-        HIPCHK(hipEventRecord(ev->a, h->stream));                                                                     \
-        hipLaunchKernelGGL((k_sweep<M, O, TS, R, Q, P>), grid, block, lds_bytes, h->stream, a);                       \
-        HIPCHK(hipEventRecord(ev->b, h->stream));                                                                     \
-    } while (0)
-#define SW(M, O, TS, R, Q) SWP(M, O, TS, R, Q, 0)
-#define SW_Q(M, O, TS, R)                                        \
-    do {                                                         \
-        if (method == COREG_METHOD_RESIDUS) SW(M, O, TS, R, true); \
-        else SW(M, O, TS, R, false);                             \
-    } while (0)
-#define SW_T(M, O, R)                           \
-    do {                                        \
-        if (h->small_f32) SW_Q(M, O, float, R); \
-        else SW_Q(M, O, double, R);             \
-    } while (0)
-    // TRANSLATE = Carrington (float64 samples); HOMOGRAPHY[_SERIES] = helioprojective (samples rounded to float32)
-    if (mode == MODE_TRANSLATE && order == 2 && h->small_f32 && method != COREG_METHOD_RESIDUS && pitch_sel > 0) {
-        // the common Carrington sweep with a compile-time window pitch (pick_pitch)
-        switch (pitch_sel) {
-            case 89: SWP(MODE_TRANSLATE, 2, float, false, false, 89); break;
-            case 121: SWP(MODE_TRANSLATE, 2, float, false, false, 121); break;
-            case 153: SWP(MODE_TRANSLATE, 2, float, false, false, 153); break;
-            case 185: SWP(MODE_TRANSLATE, 2, float, false, false, 185); break;
-            case 217: SWP(MODE_TRANSLATE, 2, float, false, false, 217); break;
-            default: SW(MODE_TRANSLATE, 2, float, false, false); break;
-        }
-    } else if (mode == MODE_TRANSLATE && order == 2 && !h->small_f32 && method != COREG_METHOD_RESIDUS &&
-               (pitch_sel == 89 || pitch_sel == 121 || pitch_sel == 153)) {
-        // the same with float64 pixels (values that are not float32-exact): the three smallest pitches
-        if (pitch_sel == 89) SWP(MODE_TRANSLATE, 2, double, false, false, 89);
-        else if (pitch_sel == 121) SWP(MODE_TRANSLATE, 2, double, false, false, 121);
-        else SWP(MODE_TRANSLATE, 2, double, false, false, 153);
-    } else if ((mode == MODE_HOMOGRAPHY_SERIES || mode == MODE_HOMOGRAPHY) && order == 2 && h->small_f32 &&
-               method != COREG_METHOD_RESIDUS && (pitch_sel == 89 || pitch_sel == 121)) {
-        // the common helioprojective sweeps likewise
-        if (mode == MODE_HOMOGRAPHY_SERIES) {
-            if (pitch_sel == 89) SWP(MODE_HOMOGRAPHY_SERIES, 2, float, true, false, 89);
-            else SWP(MODE_HOMOGRAPHY_SERIES, 2, float, true, false, 121);
-        } else {
-            if (pitch_sel == 89) SWP(MODE_HOMOGRAPHY, 2, float, true, false, 89);
-            else SWP(MODE_HOMOGRAPHY, 2, float, true, false, 121);
-        }
-    } else if (mode == MODE_TRANSLATE && order == 3 && h->small_f32 && method != COREG_METHOD_RESIDUS &&
-               (pitch_sel == 89 || pitch_sel == 121 || pitch_sel == 153)) {
-        // the cubic Carrington sweep with a compile-time window pitch
-        if (pitch_sel == 89) SWP(MODE_TRANSLATE, 3, float, false, false, 89);
-        else if (pitch_sel == 121) SWP(MODE_TRANSLATE, 3, float, false, false, 121);
-        else SWP(MODE_TRANSLATE, 3, float, false, false, 153);
-    } else if (mode == MODE_TRANSLATE) {
-        if (order == 2) SW_T(MODE_TRANSLATE, 2, false);
-        else if (order == 1) SW_T(MODE_TRANSLATE, 1, false);
-        else if (order == 3) SW_T(MODE_TRANSLATE, 3, false);
-        else SW_T(MODE_TRANSLATE, ORDER_RT, false);
-    } else if (mode == MODE_CAR) {
-        if (order == 2) SW_T(MODE_CAR, 2, true);
-        else if (order == 1) SW_T(MODE_CAR, 1, true);
-        else SW_T(MODE_CAR, ORDER_RT, true);
-    } else if (mode == MODE_HOMOGRAPHY_SERIES && (order == 1 || order == 2 || order == 3)) {
-        if (order == 2) SW_T(MODE_HOMOGRAPHY_SERIES, 2, true);
-        else if (order == 3) SW_T(MODE_HOMOGRAPHY_SERIES, 3, true);
-        else SW_T(MODE_HOMOGRAPHY_SERIES, 1, true);
-    } else {
-        if (order == 2) SW_T(MODE_HOMOGRAPHY, 2, true);
-        else if (order == 1) SW_T(MODE_HOMOGRAPHY, 1, true);
-        else if (order == 3) SW_T(MODE_HOMOGRAPHY, 3, true);
-        else SW_T(MODE_HOMOGRAPHY, ORDER_RT, true);
-    }
-#undef SWP
-#undef SW_Q
-#undef SW_T
-#undef SW
-    HIPCHK(hipGetLastError());
+    RETCHK(launch_k_sweep(h, L, a, dim3((unsigned)((long long)g_per * L.n_batches)), lds_bytes));
     h->stats.n_sweep_launches++;
     h->stats.used_lds = a.use_lds;
 
-    // the noise-decided samples of this launch as kernel arguments (FixLaunch): built on every rank of a
-    // grid-shared sweep (the re-evaluation of a flagged lag-point runs on every rank), run here -- about the global
-    // pivots, into the extra slab -- on the rank that carries the correction
     FixLaunch fl;
-    fl.small_f32 = h->small_f32;
-    if (fix && (!fix->items.empty() || fix->tap_segs > 0)) {
-        BorderFixArgs b = {};
-        b.img = h->small.p;
-        b.W = h->sW;
-        b.H = h->sH;
-        b.ref = h->ref.p;
-        b.ref_f32 = h->ref_dtype == COREG_F32 ? 1 : 0;
-        b.gw = h->gW;
-        b.order = order;
-        b.round_f32 = mode == MODE_TRANSLATE ? 0 : 1;
-        b.residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
-        b.pivots = h->pivots.as<double>();
-        b.n_slots = n_slots;
-        for (const BorderFix::Item& it : fix->items) {
-            b.slot = it.slot;
-            b.dropped = h->border_dev.as<int>() + it.first;
-            b.n_dropped = it.n;
-            b.hom = params_dev;  // SoA [9][n_slots]: the (snapped) map of the slot gives the sample coordinates
-            if (it.flags_off >= 0) {
-                // odd spline order: re-decide the tap set of every pixel of this lag-point (k_parity_fix), after
-                // k_border_fix has set the slab entry (same stream)
-                ParityFixArgs p = {};
-                p.img = b.img;
-                p.W = b.W;
-                p.H = b.H;
-                p.ref = b.ref;
-                p.ref_f32 = b.ref_f32;
-                p.flags = h->border_flags.as<unsigned char>() + it.flags_off;
-                p.gw = h->gW;
-                p.gh = h->gH;
-                p.order = order;
-                p.round_f32 = b.round_f32;
-                p.residus = b.residus;
-                p.pivots = b.pivots;
-                p.hom = params_dev;
-                p.n_slots = n_slots;
-                p.slot = it.slot;
-                p.n_partial = 256;
-                if (h->fix_partial.reserve((size_t)p.n_partial * kNumSums * sizeof(double)) != hipSuccess)
-                    return fail(h, COREG_EHIP, "hipMalloc failed (parity fix)");
-                p.partial = h->fix_partial.as<double>();
-                fl.parity.push_back(p);
-            }
-            if (it.n == 0) continue;
-            fl.border.push_back(b);
-        }
-        if (fix->tap_segs > 0) {
-            TapFixArgs t = fix->tap;
-            t.img = b.img;
-            t.W = b.W;
-            t.H = b.H;
-            t.ref = b.ref;
-            t.ref_f32 = b.ref_f32;
-            t.gw = h->gW;
-            t.order = order;
-            t.round_f32 = b.round_f32;
-            t.residus = b.residus;
-            t.pivots = b.pivots;
-            t.hom = params_dev;
-            t.n_slots = n_slots;
-            fl.tap = t;
-            fl.have_tap = true;
-            fl.tap_segs = fix->tap_segs;
-            fl.tap_count = fix->tap_count;
-            fl.tap_mode = fix->tap_mode;
-        }
-    }
+    RETCHK(build_fix_launch(h, L, &fl));
     if (fixing) {
-        // one more slab: zero, except minus the dropped border pixels' totals at the identity lag's slot
-        double* slab = h->partials.as<double>() + (size_t)g_per * kNumSums * n_slots;
-        HIPCHK(hipMemsetAsync(slab, 0, (size_t)kNumSums * n_slots * sizeof(double), h->stream));
-        RETCHK(launch_fix_kernels(h, fl, slab, nullptr, nullptr));
+        // the extra slab: zero, except minus the dropped border pixels' totals at the identity lag's slot
+        HIPCHK(hipMemsetAsync(fix_slab, 0, (size_t)kNumSums * n_slots * sizeof(double), h->stream));
+        RETCHK(launch_fix_kernels(h, fl, fix_slab, nullptr, nullptr));
     }
 
+    // Ill-conditioned lag-points are flagged by k_finalize and re-evaluated about their own means (kernels.hpp:
+    // RefineArgs) -- not for method 'residus' (another statistic).  A launch with noise-decided samples runs its fix
+    // kernels a second time for them (refine.fix_slab: k_finalize only asks whether it is set; refine_with_fixes fills
+    // it).  Grid shares across GPUs: the flags can only come from the REDUCED sums, so the re-evaluation is run by
+    // coreg_finalize_sums, on every rank, over the whole grid.
+    const bool refinable = h->opt_refine && !L.residus();
     FinalizeArgs f = {};
-    // ill-conditioned lag-points are flagged by k_finalize and re-evaluated about their own means (kernels.hpp:
-    // RefineArgs) -- not for method 'residus' (another statistic) and not the lag-points whose noise-decided samples
-    // were taken out of (put into) the sums by the extra slab: those keep their one-pass value (FinalizeArgs.fix_slab).
-    // Grid shares across GPUs: the flags can only come from the REDUCED sums, so the re-evaluation is run by
-    // coreg_finalize_sums, on every rank, over the whole grid (with the second run of this launch's fix kernels).
-    const bool refinable = h->opt_refine && method != COREG_METHOD_RESIDUS;
-    RETCHK(fill_refine(h, &f.refine, mode, order, params_dev, a.car_inv, n_slots));
+    RETCHK(fill_refine(h, &f.refine, L.mode, L.order, a.lane_params, a.car_inv, n_slots));
     f.refine.enabled = (refinable && !sharded) ? 1 : 0;
-    f.fix_slab = fixing ? h->partials.as<double>() + (size_t)g_per * kNumSums * n_slots : nullptr;
     if (fixing && f.refine.enabled) {
-        // the re-evaluation of a flagged lag-point of THIS launch needs its noise-decided samples about its own pivots:
-        // a second slab, filled between the listing of the flags and k_refine (kernels that leave at once unless the
-        // slot is flagged)
         HIPCHK(h->rf_fix_slab.reserve((size_t)kNumSums * n_slots * sizeof(double)));
-        HIPCHK(hipMemsetAsync(h->rf_fix_slab.p, 0, (size_t)kNumSums * n_slots * sizeof(double), h->stream));
         f.refine.fix_slab = h->rf_fix_slab.as<double>();
     }
+    f.fix_slab = fix_slab;
     f.refine_count = h->counters.as<long long>();  // (null before the first plan: no sweep without one)
     f.partials = h->partials.as<double>();
     f.n_groups = g_per + (fixing ? 1 : 0);
     f.part_stride = n_slots;
-    f.sums_out = nullptr;
-    f.sums_stride = f.sums_off = 0;
-    if (sharded) {
-        // leave this launch's six sums per slot in h->sums (reserved by the caller for all launches of the sweep)
+    if (sharded) {  // this launch's six sums per slot into h->sums (reserved by the caller for all launches of the sweep)
         f.sums_out = h->sums.as<double>();
         f.sums_stride = h->sums_slots;
-        f.sums_off = sums_off;
-        coreg_handle::PendingFinalize pf;
-        pf.slot_off = sums_off;
-        pf.n_slots = n_slots;
-        pf.lag_begin = lag_begin;
-        pf.outidx_dev = nullptr;  // set by coreg_finalize_sums from fin_outidx
-        pf.residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
-        pf.refine = f.refine;
-        pf.refine.enabled = refinable ? 1 : 0;
-        pf.replay_precompute = h->last_precompute;
-        pf.fixes = fl;  // (the slab is inside the reduced sums; the second run of the fix kernels happens on every rank)
-        // a plate-carree sweep has one launch per combination and every launch lists its single samples anew in the
-        // handle's buffers: this launch's lists are COPIED (round 6, closes DESIGN 9 open 3 of round 5) so that
-        // coreg_finalize_sums can run the fix kernels a second time about the flagged slots' pivots, as FixLaunch lets it
-        // do for the one-launch helioprojective sweeps.  Rare path (unrotated maps, single-axis lags).  The copies are
-        // ordered on the handle's stream after the kernels that read the sources; the next launch's prepare_tap_fix
-        // waits for that stream before it writes the sources again.
-        if (mode == MODE_CAR && fl.have_tap) {
-            auto kept = std::make_shared<KeptTapLists>();
-            const size_t nseg = (size_t)fl.tap_segs, cnt = (size_t)fl.tap_count;
-            TapFixArgs& t = pf.fixes.tap;
-            const void* src[5] = {t.xw, t.yw, t.pixel, t.seg_begin, t.seg_slot};
-            const size_t bytes[5] = {cnt * sizeof(double), cnt * sizeof(double), cnt * sizeof(unsigned),
-                                     (nseg + 1) * sizeof(int), nseg * sizeof(int)};
-            size_t off[6] = {0};
-            for (int k = 0; k < 5; ++k) off[k + 1] = off[k] + ((bytes[k] + 7) & ~(size_t)7);
-            HIPCHK(kept->all.reserve(off[5]));
-            char* all = kept->all.as<char>();
-            for (int k = 0; k < 5; ++k)
-                if (bytes[k]) HIPCHK(hipMemcpyAsync(all + off[k], src[k], bytes[k], hipMemcpyDeviceToDevice, h->stream));
-            t.xw = (const double*)(all + off[0]);
-            t.yw = (const double*)(all + off[1]);
-            t.pixel = (const unsigned*)(all + off[2]);
-            t.seg_begin = (const int*)(all + off[3]);
-            t.seg_slot = (const int*)(all + off[4]);
-            pf.fixes.kept = kept;
-        }
-        h->pending_fin.push_back(pf);
+        f.sums_off = (long long)L.slot_off;
     }
     f.n_slots = n_slots;
-    f.out_index = outidx_dev;
-    f.lag_begin = lag_begin;
-    f.out = out_dev;
-    f.residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
+    f.out_index = L.outidx_dev(h);
+    f.lag_begin = L.lag_begin;
+    f.out = L.out_dev;
+    f.residus = L.residus() ? 1 : 0;
     f.n_required = (long long)h->gW * h->gH;
-    hipLaunchKernelGGL(k_finalize, dim3((unsigned)((n_slots + kFinSlots - 1) / kFinSlots)), dim3(kFinSlots * kFinLanes), 0,
-                       h->stream, f);
+    launch_finalize(h, f);
     HIPCHK(hipGetLastError());
-    if (f.refine.enabled && f.refine.fix_slab) {
-        hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, f.refine, n_slots, h->counters.as<long long>());
-        RETCHK(launch_fix_kernels(h, fl, h->rf_fix_slab.as<double>(), f.refine.slot_pivots, f.refine.flags));
-        RETCHK(launch_refine(h, f.refine, n_slots, outidx_dev, lag_begin, out_dev, false));
-    } else if (f.refine.enabled) {
-        RETCHK(launch_refine(h, f.refine, n_slots, outidx_dev, lag_begin, out_dev));
-    }
-    return COREG_OK;
+
+    if (sharded) return queue_pending_finalize(h, L, f.refine, refinable, fl);
+    if (!f.refine.enabled) return COREG_OK;
+    hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, f.refine, n_slots, h->counters.as<long long>());
+    return refine_with_fixes(h, f.refine, fl, n_slots, f.out_index, L.lag_begin, L.out_dev);
 }
 
 }  // namespace
