@@ -19,7 +19,7 @@ COREG_OK = 0
 COREG_EINVAL, COREG_EHIP, COREG_ESTATE, COREG_ENOTIMPL, COREG_ENOMEM = -1, -2, -3, -4, -5
 COREG_F32, COREG_F64 = 0, 1
 PROJ_TAN, PROJ_CAR = 0, 1
-METHOD_CORRELATION, METHOD_RESIDUS = 0, 1
+METHOD_CORRELATION, METHOD_RESIDUS, METHOD_RESIDUS_MASKED = 0, 1, 2
 CDELT_INTENDED, CDELT_REFERENCE = 0, 1
 
 
@@ -260,6 +260,7 @@ SYMBOLS = [
     ("coreg_get_pivots", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("coreg_set_pivots", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("coreg_last_stats", C.c_int, [_P, C.POINTER(Stats)]),
+    ("coreg_last_counts", C.c_int, [_P, _P, C.c_int]),
     ("coreg_last_visit_counts", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("coreg_last_tap_fix", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("coreg_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),
@@ -326,6 +327,7 @@ SYMBOLS = [
      [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.POINTER(Lags), C.c_int, C.c_int, C.c_int, _P]),
     ("coreg_multi_sweep_helioprojective", C.c_int, [_P, _WP, _WP, C.POINTER(Lags), C.c_int, C.c_int, C.c_int, _P]),
     ("coreg_multi_last_stats", C.c_int, [_P, C.c_int, C.POINTER(Stats)]),
+    ("coreg_multi_last_counts", C.c_int, [_P, _P]),
     ("coreg_multi_plan", C.c_int,
      [C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
       C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -636,6 +638,7 @@ class CoregHandle(_ImageIntake):
         lag_end = lags.size if lag_end is None else int(lag_end)
         w = wcs_from_header(hdr_small, carrington=True)
         out, ptr, on_dev = _sweep_out(lag_end - lag_begin, out_dev_ptr)
+        self._counts_n = lag_end - lag_begin
         self._chk(self._lib.coreg_sweep_carrington(self._h, C.byref(w), C.byref(grid.c), float(solar_r),
                                                    C.byref(lags.c), int(order), int(method), int(cdelt_semantics),
                                                    int(lag_begin), lag_end, ptr, on_dev))
@@ -646,6 +649,7 @@ class CoregHandle(_ImageIntake):
         lag_end = lags.size if lag_end is None else int(lag_end)
         wt, w = wcs_from_header(hdr_target), wcs_from_header(hdr_small)
         out, ptr, on_dev = _sweep_out(lag_end - lag_begin, out_dev_ptr)
+        self._counts_n = lag_end - lag_begin
         self._chk(self._lib.coreg_sweep_helioprojective(self._h, C.byref(wt), C.byref(w), C.byref(lags.c), int(order),
                                                         int(method), int(cdelt_semantics), int(lag_begin), lag_end,
                                                         ptr, on_dev))
@@ -694,6 +698,7 @@ class CoregHandle(_ImageIntake):
         if cf.size != w.naxis1:
             raise ValueError("col_frame needs one entry per raster column")
         out, ptr, on_dev = _sweep_out(lag_end - lag_begin, out_dev_ptr)
+        self._counts_n = lag_end - lag_begin
         self._chk(self._lib.coreg_sweep_context(
             self._h, C.byref(wt), C.byref(w), cf.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(lags.c), int(order),
             int(method), int(cdelt_semantics), int(vmin is not None), float(0.0 if vmin is None else vmin),
@@ -777,6 +782,7 @@ class CoregHandle(_ImageIntake):
             sptr, s_dev = sums.ctypes.data, 0
         else:
             sptr, s_dev = int(sums), 1
+        self._counts_n = int(n_out)
         if out_dev_ptr is None:
             out = np.empty(int(n_out), dtype=np.float64)
             self._chk(self._lib.coreg_finalize_sums(self._h, _P(sptr), s_dev, out.ctypes.data, 0))
@@ -798,6 +804,20 @@ class CoregHandle(_ImageIntake):
         s = Stats()
         self._chk(self._lib.coreg_last_stats(self._h, C.byref(s)))
         return {f: getattr(s, f) for f, _ in Stats._fields_}
+
+    def last_counts(self, dst_ptr=None):
+        """Per-lag sample counts of the last sweep / finalize_sums / sweep_context call made through this object, laid out
+        like its output (float64; NaN: never evaluated, 0: nothing overlapped): a host array, or written to the device
+        buffer `dst_ptr`.  Waits for the stream."""
+        n = getattr(self, "_counts_n", None)
+        if n is None:
+            raise CoregError(COREG_ESTATE, "last_counts: no sweep has run through this object")
+        if dst_ptr is not None:
+            self._chk(self._lib.coreg_last_counts(self._h, _P(int(dst_ptr)), 1))
+            return None
+        out = np.empty(int(n), dtype=np.float64)
+        self._chk(self._lib.coreg_last_counts(self._h, out.ctypes.data, 0))
+        return out
 
     def last_visit_counts(self) -> dict:
         """(tile, lag batch) visits of the sweep kernel's last launch by kind (diagnostics; waits for the stream)."""
@@ -943,6 +963,7 @@ class MultiHandle(_ImageIntake):
         self._whole(lags, lag_begin, lag_end)
         w = wcs_from_header(hdr_small, carrington=True)
         out = np.empty(lags.size, dtype=np.float64)
+        self._counts_n = lags.size
         self._chk(self._lib.coreg_multi_sweep_carrington(self._m, C.byref(w), C.byref(grid.c), float(solar_r),
                                                          C.byref(lags.c), int(order), int(method), int(cdelt_semantics),
                                                          out.ctypes.data))
@@ -953,6 +974,7 @@ class MultiHandle(_ImageIntake):
         self._whole(lags, lag_begin, lag_end)
         wt, w = wcs_from_header(hdr_target), wcs_from_header(hdr_small)
         out = np.empty(lags.size, dtype=np.float64)
+        self._counts_n = lags.size
         self._chk(self._lib.coreg_multi_sweep_helioprojective(self._m, C.byref(wt), C.byref(w), C.byref(lags.c),
                                                               int(order), int(method), int(cdelt_semantics),
                                                               out.ctypes.data))
@@ -964,6 +986,15 @@ class MultiHandle(_ImageIntake):
 
     def get_reference_on_grid(self, shape, dtype):
         return self.primary.get_reference_on_grid(shape, dtype)
+
+    def last_counts(self):
+        """Per-lag sample counts of the last sweep over all devices, laid out like its map (CoregHandle.last_counts)."""
+        n = getattr(self, "_counts_n", None)
+        if n is None:
+            raise CoregError(COREG_ESTATE, "last_counts: no sweep has run through this object")
+        out = np.empty(int(n), dtype=np.float64)
+        self._chk(self._lib.coreg_multi_last_counts(self._m, out.ctypes.data))
+        return out
 
     def last_stats(self, k=None):
         """Stats of device k's share of the last sweep; k = None: device 0's with the kernel times of all devices."""

@@ -26,8 +26,9 @@ template <typename OwnChecks>
 int open_sweep(coreg_handle* h, ComboRange combo, OwnChecks own_checks, const coreg_lags* lags, int order, int method,
                int sem, int64_t lag_begin, int64_t lag_end, int grid_w, int grid_h, const char* grid_what,
                double* corr_out, int out_on_device, SweepCall* call) {
-    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS)
-        return fail(h, COREG_ENOTIMPL, "method must be COREG_METHOD_CORRELATION or COREG_METHOD_RESIDUS");
+    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS && method != COREG_METHOD_RESIDUS_MASKED)
+        return fail(h, COREG_ENOTIMPL,
+                    "method must be COREG_METHOD_CORRELATION, COREG_METHOD_RESIDUS or COREG_METHOD_RESIDUS_MASKED");
     RETCHK(check_order(h, order));
     RETCHK(own_checks());
     RETCHK(check_lags(h, lags, &call->d, lag_begin, lag_end, combo));
@@ -53,6 +54,7 @@ int close_sweep(coreg_handle* h, const SweepCall& call) {
 // a plan without a launch: every lag-point NaN
 int close_empty_sweep(coreg_handle* h, const SweepCall& call) {
     RETCHK(fill_nan(h, call.out_dev, call.n_out));
+    RETCHK(fill_nan(h, h->counts.as<double>(), call.n_out));
     return close_sweep(h, call);
 }
 
@@ -145,6 +147,7 @@ int finalize_pending(coreg_handle* h, const coreg_handle::PendingFinalize& pf, l
     f->out_index = h->fin_outidx.as<long long>() + pf.slot_off;
     f->lag_begin = pf.lag_begin;
     f->out = out_dev;
+    f->counts = h->counts.as<double>();
     f->residus = pf.residus;
     f->n_required = (long long)h->gW * h->gH;
     launch_finalize(h, *f);
@@ -765,6 +768,9 @@ int coreg_finalize_sums(coreg_handle* h, const double* sums, int sums_on_device,
                            (long long)n_out, std::numeric_limits<double>::quiet_NaN());
         HIPCHK(hipGetLastError());
     }
+    HIPCHK(h->counts.reserve((size_t)std::max<long long>(n_out, 1) * sizeof(double)));
+    h->counts_n = n_out;
+    RETCHK(fill_nan(h, h->counts.as<double>(), n_out));
     const size_t n_pending = h->pending_fin.size();
     size_t points_of = n_pending - 1;  // the launch whose compacted points the handle holds: the sweep's last one
     // a plate-carree sweep has one pending launch per combination, and asking each one "anything flagged?"
@@ -836,6 +842,18 @@ int coreg_set_pivots(coreg_handle* h, const double* pivots2) {
     RETCHK(bind_device(h));
     HIPCHK(hipMemcpyAsync(h->pivots.p, pivots2, 2 * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));  // the caller's two doubles are free again on return
+    return COREG_OK;
+}
+
+int coreg_last_counts(coreg_handle* h, double* dst, int dst_on_device) {
+    if (!h) return COREG_EINVAL;
+    if (h->counts_n < 0) return fail(h, COREG_ESTATE, "last_counts: no sweep has run on this handle");
+    if (!dst && h->counts_n > 0) return fail(h, COREG_EINVAL, "last_counts: dst is null");
+    RETCHK(bind_device(h));
+    if (h->counts_n > 0)
+        HIPCHK(hipMemcpyAsync(dst, h->counts.p, (size_t)h->counts_n * sizeof(double),
+                              dst_on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return COREG_OK;
 }
 

@@ -107,7 +107,7 @@ void coreg_destroy(coreg_handle* h) {
     DevBuf* bufs[] = {&h->rf_flags, &h->rf_pivots, &h->rf_list, &h->rf_head, &h->rf_partial, &h->small, &h->ref, &h->pivots, &h->red_sum, &h->red_cnt, &h->t_sin_lon, &h->t_cos_lon,
                       &h->t_cos_lat, &h->t_sin_lat, &h->pts, &h->tile_count, &h->tile_list, &h->tile_cum, &h->group_first,
                       &h->tile_info, &h->tile_bbox, &h->counters, &h->lane_params, &h->out_index, &h->partials, &h->out_dev,
-                      &h->tmp_img, &h->up_f64, &h->up_flag, &h->up_raw, &h->rice_blob, &h->rice_rand, &h->dec_img, &h->border_dev, &h->sums, &h->fin_outidx, &h->border_flags, &h->fix_partial, &h->rf_fix_slab};
+                      &h->tmp_img, &h->up_f64, &h->up_flag, &h->up_raw, &h->rice_blob, &h->rice_rand, &h->dec_img, &h->border_dev, &h->sums, &h->fin_outidx, &h->border_flags, &h->fix_partial, &h->rf_fix_slab, &h->counts};
     for (DevBuf* b : bufs) b->release();
     for (int k = 0; k < 2; ++k) {
         h->pin_img[k].release();

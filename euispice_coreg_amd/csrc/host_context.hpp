@@ -168,7 +168,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
     // odd orders: scipy's first tap is floor(c), and every SPICE sample of this near-identity map sits within wcslib's
     // noise of an integer -- the tap set of EVERY sample would be noise-decided
     if (order & 1) return fail(h, COREG_ENOTIMPL, "sweep_context: odd reprojection orders are not implemented");
-    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS)
+    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS && method != COREG_METHOD_RESIDUS_MASKED)
         return fail(h, COREG_EINVAL, "sweep_context: unknown method");
     if (sem != COREG_CDELT_INTENDED && sem != COREG_CDELT_REFERENCE)
         return fail(h, COREG_EINVAL, "sweep_context: unknown cdelt semantics");
@@ -188,7 +188,10 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
     // re-evaluated lag-points of THIS sweep (coreg_last_visit_counts "refined_lag_points"), summed over its launches
     HIPCHK(h->counters.reserve(8 * sizeof(long long)));
     HIPCHK(hipMemsetAsync(h->counters.p, 0, 8 * sizeof(long long), h->stream));
+    HIPCHK(h->counts.reserve((size_t)std::max<long long>(n_out, 1) * sizeof(double)));
+    h->counts_n = n_out;
     if (n_out == 0) return COREG_OK;
+    double* const counts = h->counts.as<double>();  // (every lag-point of the slice is finalised below: no NaN fill)
 
     HIPCHK(c->mean.reserve(2 * sizeof(double)));
     if (!c->have_pivot) {
@@ -269,7 +272,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
         a.has_max = has_max ? 1 : 0;
         a.vmin = (float)vmin;  // (NumPy compares a float32 array with a Python float in float32)
         a.vmax = (float)vmax;
-        a.residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
+        a.residus = method == COREG_METHOD_RESIDUS_MASKED ? 2 : (method == COREG_METHOD_RESIDUS ? 1 : 0);
         a.n_slots = ns_;
         a.pa = a.residus ? 0.0 : c->pivot;
         a.pb = a.residus ? 0.0 : pb;
@@ -284,7 +287,8 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
         ++launches;
         if (a.residus) {
             hipLaunchKernelGGL(k_finalize_context_residus, dim3((unsigned)((ns_ + 255) / 256)), dim3(256), 0, h->stream,
-                               a.partials, n_groups, ns_, lag_begin, c->out_index.as<long long>(), out_dev);
+                               a.partials, n_groups, ns_, lag_begin, c->out_index.as<long long>(), out_dev,
+                               a.residus == 2 ? 1 : 0, counts);
             HIPCHK(hipGetLastError());
         } else {
             FinalizeArgs f = {};
@@ -294,6 +298,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
             f.out_index = c->out_index.as<long long>();
             f.lag_begin = lag_begin;
             f.out = out_dev;
+            f.counts = counts;
             f.part_stride = ns_;
             f.refine_count = h->counters.as<long long>();
             RefineArgs& r = f.refine;
@@ -306,6 +311,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
             r.out_index = f.out_index;
             r.lag_begin = lag_begin;
             r.out = out_dev;
+            r.counts = counts;
             launch_finalize(h, f);
             if (r.enabled) {
                 hipLaunchKernelGGL(k_refine_list, dim3(1), dim3(kListThreads), 0, h->stream, r, ns_, h->counters.as<long long>());

@@ -111,6 +111,7 @@ int refine_with_fixes(coreg_handle* h, RefineArgs r, const FixLaunch& fixes, lon
     r.out_index = outidx_dev;
     r.lag_begin = lag_begin;
     r.out = out_dev;
+    r.counts = h->counts.as<double>();
     hipLaunchKernelGGL(k_refine, dim3(kRefineBlocks), dim3(kRefineThreads), 0, h->stream, r, n_slots);
     HIPCHK(hipGetLastError());
     return COREG_OK;

@@ -335,7 +335,7 @@ int setup_precompute(coreg_handle* h, const Plan& plan, int method, PrecomputeAr
     a->pts = h->pts.as<Pt>();
     a->tile_count = h->tile_count.as<int>();
     a->tile_bbox = h->tile_bbox.as<double>();
-    a->residus = method == COREG_METHOD_RESIDUS ? 1 : 0;
+    a->residus = method != COREG_METHOD_CORRELATION ? 1 : 0;  // (both residus methods)
     return COREG_OK;
 }
 

@@ -148,6 +148,10 @@ struct coreg_handle {
     DevBuf counters;  // [0]: lag-points re-evaluated by k_finalize during the sweep in flight (reset by its prologue)
     // sweep
     DevBuf lane_params, out_index, partials, out_dev, tmp_img;
+    // per-lag sample counts of the last sweep / coreg_finalize_sums / coreg_sweep_context call, laid out like its output
+    // (coreg_last_counts); counts_n < 0: no such call yet
+    DevBuf counts;
+    long long counts_n = -1;
     DevBuf up_f64, up_flag;  // upload staging on the device (float64 copy, exactness flag)
     DevBuf up_raw;           // raw FITS elements awaiting their decode (BITPIX other than an unscaled -32)
     DevBuf rice_blob, rice_rand, dec_img;  // tile-compressed images: heap + tile tables, cfitsio's random sequence, a

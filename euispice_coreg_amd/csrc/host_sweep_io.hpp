@@ -43,6 +43,8 @@ int begin_sweep(coreg_handle* h, long long n_out, double* corr_out, int out_on_d
         HIPCHK(h->out_dev.reserve((size_t)std::max<long long>(n_out, 1) * sizeof(double)));
         *out_dev = h->out_dev.as<double>();
     }
+    HIPCHK(h->counts.reserve((size_t)std::max<long long>(n_out, 1) * sizeof(double)));
+    h->counts_n = n_out;
     // (no start event of its own: the opening event of the first k_precompute launch is the sweep's start, collect_stats)
     // (the output is NaN-initialised by the prologue part of the first k_precompute launch, or by fill_nan on the
     // paths that launch nothing)
@@ -131,6 +133,7 @@ int upload_plan(coreg_handle* h, const std::vector<double>& params, const std::v
     p.n_outidx = (long long)outidx.size();
     p.out = out_dev;
     p.n_out = n_out;
+    p.counts = h->counts.as<double>();
     HIPCHK(h->counters.reserve(8 * sizeof(long long)));
     p.refine_count = h->counters.as<long long>();
     return COREG_OK;

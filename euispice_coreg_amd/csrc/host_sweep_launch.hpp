@@ -25,7 +25,9 @@ struct SweepLaunchSpec {
     const BorderFix* fix = nullptr;    // noise-decided samples of the launch
     int pitch_sel = 0;                 // compile-time LDS window pitch asked for (pick_pitch), 0: per visit
     long long n_slots() const { return (long long)n_batches * kBlock; }
-    bool residus() const { return method == COREG_METHOD_RESIDUS; }
+    // both residus methods run the `resid` instantiations of k_sweep; they part in k_finalize (FinalizeArgs.residus)
+    bool residus() const { return method != COREG_METHOD_CORRELATION; }
+    int residus_kind() const { return method == COREG_METHOD_RESIDUS_MASKED ? 2 : (residus() ? 1 : 0); }
     const double* params_dev(const coreg_handle* h) const {
         return h->lane_params.as<double>() + (mode == MODE_TRANSLATE ? 2 : 9) * slot_off;
     }
@@ -190,7 +192,7 @@ int queue_pending_finalize(coreg_handle* h, const SweepLaunchSpec& L, const Refi
     pf.slot_off = (long long)L.slot_off;
     pf.n_slots = L.n_slots();
     pf.lag_begin = L.lag_begin;
-    pf.residus = L.residus() ? 1 : 0;
+    pf.residus = L.residus_kind();
     pf.refine = refine;
     pf.refine.enabled = refinable ? 1 : 0;
     pf.replay_precompute = h->last_precompute;
@@ -232,7 +234,7 @@ int launch_sweep(coreg_handle* h, const SweepLaunchSpec& L) {
     }
 
     // Ill-conditioned lag-points are flagged by k_finalize and re-evaluated about their own means (kernels.hpp:
-    // RefineArgs) -- not for method 'residus' (another statistic).  A launch with noise-decided samples runs its fix
+    // RefineArgs) -- not for the residus methods (another statistic).  A launch with noise-decided samples runs its fix
     // kernels a second time for them (refine.fix_slab: k_finalize only asks whether it is set; refine_with_fixes fills
     // it).  Grid shares across GPUs: the flags can only come from the REDUCED sums, so the re-evaluation is run by
     // coreg_finalize_sums, on every rank, over the whole grid.
@@ -258,7 +260,8 @@ int launch_sweep(coreg_handle* h, const SweepLaunchSpec& L) {
     f.out_index = L.outidx_dev(h);
     f.lag_begin = L.lag_begin;
     f.out = L.out_dev;
-    f.residus = L.residus() ? 1 : 0;
+    f.counts = h->counts.as<double>();
+    f.residus = L.residus_kind();
     f.n_required = (long long)h->gW * h->gH;
     launch_finalize(h, f);
     HIPCHK(hipGetLastError());

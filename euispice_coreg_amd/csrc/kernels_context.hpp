@@ -35,7 +35,7 @@ struct ContextArgs {
     const unsigned char* edge;
     int has_min, has_max;
     float vmin, vmax;  // thresholds on the float32 SPICE sample (compared in float32, alignment_spice.py:396-399)
-    int residus;
+    int residus;  // 0: Pearson, 1: 'residus', 2: 'residus_masked'
     long long n_slots;
     double pa, pb;      // pivots of the sums (context, SPICE)
     double* partials;   // [n_groups][kNumSums][n_slots]
@@ -90,6 +90,18 @@ __device__ __forceinline__ bool ctx_selected(const ContextArgs& c, double b) {
 __device__ __forceinline__ void ctx_accumulate(const ContextArgs& c, double a, double b, double pa, double pb,
                                                double s[kNumSums]) {
     if (!ctx_selected(c, b) && (c.has_min || c.has_max)) return;
+    if (c.residus == 2) {  // 'residus_masked': co-finite samples only; a term that is not finite poisons (sum 1)
+        if (!isfinite(a) || !isfinite(b)) return;
+        const double d = (a - b) / sqrt(a);
+        if (isfinite(d)) {
+            s[0] += 1.0;
+            s[2] += d;
+            s[4] += d * d;
+        } else {
+            s[1] += 1.0;
+        }
+        return;
+    }
     if (c.residus) {
         const double d = (a - b) / sqrt(a);
         s[0] += 1.0;
@@ -153,19 +165,23 @@ __global__ void __launch_bounds__(kCtxThreads) k_context_sweep(const ContextArgs
 // sample is NaN or nothing is selected, and when a term is infinite (a = 0 with b != 0): np.std's mean is then infinite,
 // its deviations NaN, while s4 / n - m * m would be inf - inf and fmax(NaN, 0) = 0, the best possible score.  (Unlike the
 // main sweeps, whose point_lag drops a non-finite term, ctx_accumulate adds every selected term.)
+// 'residus_masked' (masked = 1): the terms are finite by construction; NaN when nothing is co-finite and selected, or
+// when a poisoned term was met (sum 1, ctx_accumulate).  `counts` (or null): n per lag-point, as FinalizeArgs.counts.
 __global__ void k_finalize_context_residus(const double* partials, int n_groups, long long n_slots,
-                                           long long lag_begin, const long long* out_index, double* out) {
+                                           long long lag_begin, const long long* out_index, double* out, int masked,
+                                           double* counts) {
     const long long slot = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (slot >= n_slots) return;
-    double n = 0.0, s2 = 0.0, s4 = 0.0;
+    double n = 0.0, s1 = 0.0, s2 = 0.0, s4 = 0.0;
     for (int g = 0; g < n_groups; ++g) {
         const double* p = partials + (size_t)g * kNumSums * n_slots + slot;
         n += p[0];
+        s1 += p[n_slots];
         s2 += p[2 * n_slots];
         s4 += p[4 * n_slots];
     }
     double r = __builtin_nan("");
-    if (n > 0.0 && isfinite(s2) && s4 == s4) {
+    if (n > 0.0 && isfinite(s2) && s4 == s4 && (!masked || s1 == 0.0)) {
         // m * m rounded on its own, not fused with the subtraction: the fma would leave the product's rounding error
         // (up to half an ulp of m * m), so one selected sample, or equal terms, would give sqrt(that) instead of 0
 #pragma clang fp contract(off)
@@ -173,6 +189,7 @@ __global__ void k_finalize_context_residus(const double* partials, int n_groups,
         r = sqrt(fmax(s4 / n - m * m, 0.0));
     }
     out[out_index[slot] - lag_begin] = r;
+    if (counts) counts[out_index[slot] - lag_begin] = n;
 }
 
 // Re-evaluation of the lag-points k_finalize flagged (list from k_refine_list): one workgroup per flagged slot walks the
@@ -205,6 +222,7 @@ __global__ void __launch_bounds__(kCtxThreads) k_refine_context(const ContextArg
                 res = cov / sqrt(va * vb);
             }
             r.out[r.out_index[slot] - r.lag_begin] = res;
+            if (r.counts) r.counts[r.out_index[slot] - r.lag_begin] = cnt;
         }
         __syncthreads();
     }

@@ -38,6 +38,7 @@ struct RefineArgs {
     const long long* out_index;  // (k_refine's last block writes the coefficients)
     long long lag_begin;
     double* out;
+    double* counts;  // as FinalizeArgs.counts, or null
     long long* refine_count;
 };
 constexpr double kRefineCond = 1e5;  // default threshold on sum xx / (n var) (one-pass error below it: < 1e-11)
@@ -55,8 +56,13 @@ struct FinalizeArgs {
     const long long* out_index;  // C-order raveled lag index of each slot, or -1 (padding)
     long long lag_begin;
     double* out;  // [lag_end - lag_begin]
-    int residus;          // 1: np.std((A - B) / sqrt(A)) over ALL grid points (alignment.py:544-547)
-    long long n_required;  // residus: number of grid points G; fewer contributions -> NaN (no mask in that method)
+    // [lag_end - lag_begin] or null: the lag-point's sample count n (Pearson: samples in the six sums; residus methods:
+    // finite terms), one store per lag-point next to the score's (coreg_last_counts)
+    double* counts;
+    // 1: np.std((A - B) / sqrt(A)) over ALL grid points (alignment.py:544-547); 2 ('residus_masked'): over the
+    // co-finite points only -- NaN when there is none or when one of their terms is not finite (sum 1 counts those)
+    int residus;
+    long long n_required;  // residus 1: number of grid points G; fewer contributions -> NaN (no mask in that method)
     // multi-GPU point sharding: instead of the coefficient, write the six sums of this rank's groups to
     // sums_out[k * sums_stride + sums_off + slot] (all-reduced over the ranks, then finalised by a second call with
     // n_groups = 1 and partials = the reduced sums)
@@ -161,7 +167,7 @@ __global__ void __launch_bounds__(kFinThreads) k_finalize(const FinalizeArgs a) 
                 const double n = s[0];
                 double r = __builtin_nan("");
                 if (a.residus) {
-                    if (n == (double)a.n_required) {
+                    if (a.residus == 2 ? (n > 0.0 && s[1] == 0.0) : n == (double)a.n_required) {
                         const double m = s[2] / n;
                         r = sqrt(fmax(s[4] / n - m * m, 0.0));
                     }
@@ -187,6 +193,7 @@ __global__ void __launch_bounds__(kFinThreads) k_finalize(const FinalizeArgs a) 
                     }
                 }
                 a.out[idx - a.lag_begin] = r;
+                if (a.counts) a.counts[idx - a.lag_begin] = n;
             }
         }
         if (a.refine.enabled) a.refine.flags[slot] = flag;
@@ -314,6 +321,7 @@ __global__ void __launch_bounds__(kRefineThreads) k_refine(const RefineArgs r, l
             res = cov / sqrt(va * vb);
         }
         r.out[r.out_index[slot] - r.lag_begin] = res;
+        if (r.counts) r.counts[r.out_index[slot] - r.lag_begin] = cnt;
     }
     if (threadIdx.x == 0) r.head[3] = 0;  // the ticket, for the next launch
 }

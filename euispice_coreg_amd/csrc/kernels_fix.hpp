@@ -69,6 +69,8 @@ __global__ void __launch_bounds__(256) k_border_fix(const BorderFixArgs a) {
                 s[0] += 1.0;
                 s[2] += d;
                 s[4] = fma(d, d, s[4]);
+            } else if (isfinite(v)) {
+                s[1] += 1.0;  // poisoned term (point_lag, RESID)
             }
         } else if (isfinite(v)) {
             const double av = (araw - pivot_a) - own_a, bm = (v - pivot_b) - own_b;
@@ -158,6 +160,8 @@ __global__ void __launch_bounds__(256) k_parity_fix(const ParityFixArgs a) {
                 s[0] += sign;
                 s[2] += sign * d;
                 s[4] += sign * d * d;
+            } else {
+                s[1] += sign;  // poisoned term (point_lag, RESID); v is the finite one of the two samples
             }
         } else {
             const double av = (araw - pivot_a) - own_a, bm = (v - pivot_b) - own_b;
@@ -543,6 +547,8 @@ __global__ void __launch_bounds__(256) k_tap_fix(const TapFixArgs a) {
                     s[0] += sign;
                     s[2] += sign * d;
                     s[4] += sign * d * d;
+                } else if (isfinite(v)) {
+                    s[1] += sign;  // poisoned term (point_lag, RESID)
                 }
             } else if (isfinite(v)) {
                 const double av = (araw - pivot_a) - own_a, bm = (v - pivot_b) - own_b;

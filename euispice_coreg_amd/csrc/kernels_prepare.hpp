@@ -198,6 +198,7 @@ struct PrologueArgs {
     long long n_outidx;
     double* out;
     long long n_out;
+    double* counts;           // [n_out] or null: the sweep's per-lag sample counts, NaN-initialised with the output
     long long* refine_count;  // the sweep's counter of re-evaluated lag-points (k_finalize), reset here
 };
 __device__ __forceinline__ void run_prologue(const PrologueArgs& p) {
@@ -210,6 +211,8 @@ __device__ __forceinline__ void run_prologue(const PrologueArgs& p) {
     for (long long i = i0; i < p.n_outidx; i += stride) p.dst_outidx[i] = src_idx[i];
     const double nan = __builtin_nan("");
     for (long long i = i0; i < p.n_out; i += stride) p.out[i] = nan;
+    if (p.counts)
+        for (long long i = i0; i < p.n_out; i += stride) p.counts[i] = nan;
 }
 
 struct PrecomputeArgs {

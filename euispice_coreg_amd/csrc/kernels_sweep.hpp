@@ -253,6 +253,8 @@ __device__ __forceinline__ double gather_o2(unsigned win, int pitch, double ux, 
 // bounds rule cannot trigger and is not evaluated (padding lanes never get here).
 // RESID (method 'residus', alignment.py:544-547): d = (a - b) / sqrt(a) summed instead of the Pearson moments;
 // `isa` = 1/sqrt(a).  No NaN mask exists in that method: k_finalize returns NaN unless EVERY grid point contributed.
+// 'residus_masked' runs the same instantiations: a term that is not finite under a finite sample (reference <= 0) is a
+// POISONED term, counted in acc.a (unused by these methods); numpy's std over the co-finite points is NaN with one.
 // pxw, pyw (interior LDS visits): TRANSLATE: lane origin + (0.5 for order 2) - (first tap's offset + window origin), so
 // that trunc(pxw + b0) is the window column of the first tap and fract() gives the spline argument; other modes: the
 // same constant to add to the mapped coordinate.
@@ -331,6 +333,8 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
                 acc.n += 1;
                 acc.b += d;
                 acc.bb = fma(d, d, acc.bb);
+            } else if (isfinite(v)) {
+                acc.a += 1.0;  // poisoned term (finite sample, reference <= 0): NaN for the masked method
             }
         } else if (isfinite(v)) {
             acc.n += 1;
@@ -420,6 +424,8 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
                 acc.n += 1;
                 acc.b += d;
                 acc.bb = fma(d, d, acc.bb);
+            } else if (isfinite(v)) {
+                acc.a += 1.0;  // poisoned term, as above
             }
         } else if (isfinite(v)) {
             acc.n += 1;

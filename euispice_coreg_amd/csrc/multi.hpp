@@ -299,6 +299,12 @@ struct coreg_multi {
                                     // bounded wait times is the collective, not the sweep queued in front of it)
     double phase_s[3] = {0, 0, 0};  // the last abandoned group: polling the streams, ncclCommAbort, draining the streams
     bool force_collective = false;  // COREG_MULTI_FORCE_RCCL=1 with ONE device: the RCCL calls run with a one-rank group
+    // the last sweep's partition, for coreg_multi_last_counts: the plan, the lag set's shape, and (lag sharding) the
+    // chunk size and every device's number of lag-points; last_n1 < 0: no sweep yet
+    MultiPlan last_plan;
+    int last_n1 = -1, last_n2 = 0;
+    long long last_inner = 0, last_chunk = 0;
+    std::vector<long long> last_n_mine;
 };
 
 namespace {
@@ -606,6 +612,15 @@ int sweep_sharded(coreg_multi* m, const MultiPlan& plan, const coreg_lags* lags,
     if (m->host_gather.reserve((size_t)chunk * world * sizeof(double)) != hipSuccess)
         return mfail(m, COREG_ENOMEM, "hipHostMalloc (gather buffer) failed");
     std::vector<long long> n_mine(world, 0);
+    struct KeepShares {  // (for coreg_multi_last_counts, however this function is left)
+        coreg_multi* m;
+        const std::vector<long long>& n_mine;
+        long long chunk;
+        ~KeepShares() {
+            m->last_n_mine = n_mine;
+            m->last_chunk = chunk;
+        }
+    } keep_shares{m, n_mine, chunk};
     auto to_host = [&](int k) {  // device k's block straight to its place in the host buffer, and its stream drained
         coreg_handle* h = m->h[k];
         RETCHK(bind_device(h));
@@ -682,6 +697,11 @@ int multi_sweep(coreg_multi* m, const coreg_lags* lags, double* corr_out, bool p
     if (m->force_mode >= 0 && world > 1) plan = forced_plan(plan, m->force_mode, n1, n2, inner, world);
     if (plan.mode == MULTI_NONE && m->force_collective) plan.mode = MULTI_SLICES;  // one slice, one-rank all-gather
     m->last_mode = plan.mode;
+    m->last_plan = plan;
+    m->last_n1 = n1;
+    m->last_n2 = n2;
+    m->last_inner = inner;
+    m->last_n_mine.clear();
     if (plan.mode == MULTI_NONE) {
         m->collective = "none";
         return multi_on(m, 0, [&](coreg_handle*) { return launch(0, lags, 0, n_lags, nullptr); });
@@ -1096,6 +1116,28 @@ int coreg_multi_sweep_helioprojective(coreg_multi* m, const coreg_wcs2d* hdr_tar
                        : coreg_sweep_helioprojective(m->h[k], hdr_target, hdr_small, l, order, method, cdelt_semantics, lo,
                                                      hi, corr_out, 0);
     });
+}
+
+int coreg_multi_last_counts(coreg_multi* m, double* dst_host) {
+    if (!m) return COREG_EINVAL;
+    if (m->last_n1 < 0) return mfail(m, COREG_ESTATE, "multi_last_counts: no sweep has run");
+    if (!dst_host) return mfail(m, COREG_EINVAL, "multi_last_counts: dst_host is null");
+    const MultiPlan& plan = m->last_plan;
+    // one device swept everything, or (grid shares) device 0 finalised the reduced sums: its counts are the map's
+    if (plan.mode == MULTI_NONE || plan.mode == MULTI_POINTS)
+        return multi_on(m, 0, [&](coreg_handle* h) { return coreg_last_counts(h, dst_host, 0); });
+    const int world = m->n;
+    if ((int)m->last_n_mine.size() != world) return mfail(m, COREG_ESTATE, "multi_last_counts: the last sweep did not complete");
+    const long long n_lags = (long long)m->last_n1 * m->last_n2 * m->last_inner;
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    std::fill(dst_host, dst_host + n_lags, nan);
+    std::vector<double> gathered((size_t)m->last_chunk * world, nan);
+    RETCHK(multi_run(m, [&](int k) {
+        if (m->last_n_mine[k] <= 0) return (int)COREG_OK;
+        return coreg_last_counts(m->h[k], gathered.data() + (size_t)k * m->last_chunk, 0);
+    }));
+    scatter_chunks(plan, m->last_n1, m->last_n2, m->last_inner, m->last_chunk, m->last_n_mine, gathered.data(), dst_host);
+    return COREG_OK;
 }
 
 int coreg_multi_last_stats(coreg_multi* m, int k, coreg_stats* out) {

@@ -18,6 +18,10 @@ surface.  Differences, all deliberate and listed in DESIGN.md:
   * with torch.distributed initialised (one process per GPU) the lag grid is sharded and all-gathered
     (euispice_coreg_amd/parallel.py); without it, `parallelism=True` drives every visible GPU from this one process
     (include/coreg_hip.h: coreg_multi) -- the unchanged user script uses the whole node, as it does with the reference.
+  * `method="residus_masked"` (every `align_using_*`): the residus over the co-finite grid points only, best entry =
+    the MINIMUM (quirk Q8: the reference's `residus` forgets its NaN mask and is NaN on any practical grid; it stays
+    so).  After a sweep `self.last_counts` holds the per-lag sample counts (6-D like the map); `min_overlap` (an
+    integer count, or a fraction in (0, 1) of the sweep's largest count) turns lag-points with fewer samples into NaN.
 There is no CPU fallback: without the HIP library / a GPU the sweep raises.
 """
 from __future__ import annotations
@@ -33,13 +37,58 @@ from ..utils import diffrot, fits_io, header as hdrutil, wcs_tan
 from .alignment_results import AlignmentResults
 
 
+_METHODS = {"correlation": _lib.METHOD_CORRELATION,
+            # alignment.py:544-547: no NaN mask, NaN unless every grid pixel overlaps
+            "residus": _lib.METHOD_RESIDUS,
+            "residus_masked": _lib.METHOD_RESIDUS_MASKED}
+
+
+def library_method(name):
+    """The library's method code of an `align_using_*` method name (alignment.py:549: anything else is not implemented)."""
+    if name not in _METHODS:
+        raise NotImplementedError
+    return _METHODS[name]
+
+
+def min_overlap_floor(min_overlap, counts=None):
+    """The smallest sample count `min_overlap` admits: an integer >= 1 is that count, a float in (0, 1) a fraction of the
+    largest finite entry of `counts` (NaN without one: nothing is admitted); anything else raises ValueError."""
+    if isinstance(min_overlap, (int, np.integer)) and not isinstance(min_overlap, (bool, np.bool_)):
+        if min_overlap < 1:
+            raise ValueError("min_overlap as a count must be >= 1")
+        return float(min_overlap)
+    if isinstance(min_overlap, (float, np.floating)) and 0.0 < min_overlap < 1.0:
+        finite = np.zeros(0) if counts is None else counts[np.isfinite(counts)]
+        return float(min_overlap) * float(finite.max()) if finite.size else np.nan
+    raise ValueError("min_overlap must be None, an integer >= 1 or a float in (0, 1)")
+
+
+def apply_min_overlap(corr, counts, min_overlap):
+    """The map with every lag-point of fewer than `min_overlap` samples set to NaN (pandas' `min_periods`).  `counts`:
+    per-lag sample counts, shaped like `corr` (NaN: never evaluated -- such a lag-point goes too).  `min_overlap`: None
+    (the map as it is) or as `min_overlap_floor` takes it.  ValueError when no finite entry is left."""
+    if min_overlap is None:
+        return corr
+    corr = np.asarray(corr, dtype=np.float64)
+    counts = np.asarray(counts, dtype=np.float64)
+    if counts.shape != corr.shape:
+        raise ValueError("min_overlap: the sample counts do not have the shape of the map")
+    floor = min_overlap_floor(min_overlap, counts)
+    with np.errstate(invalid="ignore"):
+        keep = counts >= floor
+    out = np.where(keep, corr, np.nan)
+    if not np.isfinite(out).any():
+        raise ValueError(f"min_overlap={min_overlap!r} leaves no lag-point of the sweep")
+    return out
+
+
 class Alignment:
 
     def __init__(self, large_fov_known_pointing, small_fov_to_correct, lag_crval1, lag_crval2, lag_cdelt1, lag_cdelt2,
                  lag_crota, lag_solar_r=None, small_fov_value_min=None, parallelism=False, display_progress_bar=False,
                  small_fov_value_max=None, counts_cpu_max=40, large_fov_window=-1, small_fov_window=-1,
                  path_save_figure=None, reprojection_order=2, force_crota_0=False, unit_lag="arcsec",
-                 cdelt_semantics="intended", device=None, differential_rotation="reference"):
+                 cdelt_semantics="intended", device=None, differential_rotation="reference", min_overlap=None):
         self.large_fov_known_pointing = large_fov_known_pointing
         self.small_fov_to_correct = small_fov_to_correct
         self.lag_crval1 = lag_crval1
@@ -77,6 +126,10 @@ class Alignment:
         # plain image HDUs of local files go to the GPU as the file stores them (COREG_RAW_FITS=0: decode on the host)
         self.raw_fits_upload = os.environ.get("COREG_RAW_FITS", "1") != "0"
         self.last_stats = None
+        if min_overlap is not None:
+            min_overlap_floor(min_overlap)  # (its checks, before anything is loaded)
+        self.min_overlap = min_overlap  # lag-points with fewer samples become NaN (apply_min_overlap); None: no floor
+        self.last_counts = None         # per-lag sample counts of the last sweep, shaped like its map
         self.last_sharding = None       # how the last sweep was spread over the GPUs (parallel.lag_sharding)
         # set by the jitter-correction session (jitter_correction/jitter_correction.py):
         self.shard_lags = True          # False: every rank runs whole sweeps (images, not lags, are spread over GPUs)
@@ -243,7 +296,12 @@ class Alignment:
                                 unit_lag=self.unit_lag, image_to_align_path=self.small_fov_to_correct,
                                 image_to_align_window=self.small_fov_window,
                                 reference_image_path=self.large_fov_known_pointing,
-                                reference_image_window=self.large_fov_window)
+                                reference_image_window=self.large_fov_window, **self._results_keywords())
+
+    def _results_keywords(self):
+        """What AlignmentResults is told beyond the reference's arguments: the sample counts, and that the best entry of
+        a `residus_masked` map is its minimum (`residus` keeps the reference's argmax)."""
+        return {"n_samples": self.last_counts, "best": "min" if self.method == "residus_masked" else "max"}
 
     def _wrap(self, results, return_type, restore_units):
         if return_type == "corr":
@@ -260,7 +318,7 @@ class Alignment:
                                 unit_lag=self.unit_lag_input, image_to_align_path=self.small_fov_to_correct,
                                 image_to_align_window=self.small_fov_window,
                                 reference_image_path=self.large_fov_known_pointing,
-                                reference_image_window=self.large_fov_window)
+                                reference_image_window=self.large_fov_window, **self._results_keywords())
 
     # ------------------------------------------------------------------------------------------------------------
     def _set_remove_fov_limits_to_nan(self, remove_fov_limits):
@@ -306,12 +364,7 @@ class Alignment:
     def _find_best_header_parameters(self, ang2pipi=True, fov_limits=None, remove_fov_limits=None):
         """alignment.py:613-797 on the GPU.  Returns float64 [n_crval1, n_crval2, n_cdelt1, n_cdelt2, n_crota,
         n_solar_r]; lag-points the library could not evaluate are NaN, never 0 (quirk Q9)."""
-        if self.method == "correlation":
-            method = _lib.METHOD_CORRELATION
-        elif self.method == "residus":
-            method = _lib.METHOD_RESIDUS  # alignment.py:544-547: no NaN mask, NaN unless every grid pixel overlaps
-        else:
-            raise NotImplementedError  # alignment.py:549
+        method = library_method(self.method)
         device = self.device
         rank, world = parallel.world_info()
         if not self.shard_lags:
@@ -439,6 +492,7 @@ class Alignment:
             getattr(h, "prepare_reference_" + kind)(self._large_pixels(), *args)
 
         out = np.full(lags.shape + (len(solar_rs),), np.nan)
+        counts = np.full(out.shape, np.nan)
         for kk, solar_r in enumerate(solar_rs):
             if self.coordinate_frame == "final_carrington":
                 grid = _lib.Grid(self.lonlims, self.latlims, self.shape, numpy_lat_trig=True)
@@ -480,15 +534,23 @@ class Alignment:
                     return h.sweep_helioprojective(t, self.hdr_small, my_lags, order=self.order, method=method,
                                                    cdelt_semantics=sem, lag_begin=lo, lag_end=hi)
             finite_pixels()
+            # (the sample counts of this rank's share are gathered the way its coefficients are)
             if mode == "points":
                 part = parallel.point_sharded_sweep(h, run, lags.size)
+                n_part = h.last_counts()  # (every rank finalises the reduced sums)
             elif mode in ("blocks", "combos"):
                 part = parallel.allgather_lag_blocks(run(), lags.shape, per_combo_launch=per_combo)
+                n_part = parallel.allgather_lag_blocks(h.last_counts(), lags.shape, per_combo_launch=per_combo)
             elif mode == "slices":
                 part = parallel.allgather_lag_slices(run(), lags.size).cpu().numpy()
+                n_part = parallel.allgather_lag_slices(h.last_counts(), lags.size).cpu().numpy()
             else:
                 part = run()
+                n_part = h.last_counts()
             out[..., kk] = np.asarray(part).reshape(lags.shape)
+            counts[..., kk] = np.asarray(n_part).reshape(lags.shape)
+        self.last_counts = counts
+        out = apply_min_overlap(out, counts, self.min_overlap)
         self.last_stats = h.last_stats()
         if hasattr(h, "drop_small_keepalive"):
             h.drop_small_keepalive()  # (every sweep has returned: the upload thread is done with the pixels)

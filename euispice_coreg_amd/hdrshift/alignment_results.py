@@ -29,13 +29,19 @@ class AlignmentResults:
 
     def __init__(self, corr, lag_crval1, lag_crval2, lag_cdelt1, lag_cdelt2, lag_crota, unit_lag,
                  image_to_align_path=None, image_to_align_window=None, reference_image_path=None,
-                 reference_image_window=None, fit=None):
+                 reference_image_window=None, fit=None, n_samples=None, best="max"):
         # fit: "native" (default; COREG_GAUSSIAN_FIT overrides) = csrc/fit.hpp, "scipy" = scipy.optimize.curve_fit
         fit = fit or os.environ.get("COREG_GAUSSIAN_FIT", "native")
         if fit not in ("native", "scipy"):
             raise ValueError("fit must be 'native' or 'scipy'")
         self.fit = fit
         self.fit_info = None
+        # best: "max" (a correlation: the reference's argmax) or "min" (a residus: `max_index` is the argmin, and the
+        # sub-lag fit runs on the flipped, rescaled map -- _fit_plane); n_samples: per-lag sample counts, kept as given
+        if best not in ("max", "min"):
+            raise ValueError("best must be 'max' or 'min'")
+        self.best = best
+        self.n_samples = n_samples
 
         def arr(v):
             return np.array([0.0]) if v is None else np.atleast_1d(np.asarray(v, dtype=np.float64))
@@ -44,7 +50,7 @@ class AlignmentResults:
                                                                                       lag_cdelt1, lag_cdelt2,
                                                                                       lag_crota))
         corr = np.asarray(corr)
-        self.max_index = np.unravel_index(np.nanargmax(corr), corr.shape)
+        self.max_index = np.unravel_index((np.nanargmin if best == "min" else np.nanargmax)(corr), corr.shape)
         self.corr = corr
         # the reference stores astropy Quantities here; plain arrays in `unit_lag` (crota in deg) without astropy
         self.parameters_alignment = {"lag_crval1": lag_crval1, "lag_crval2": lag_crval2, "lag_cdelt1": lag_cdelt1,
@@ -70,11 +76,23 @@ class AlignmentResults:
         self.shift_arcsec = (p["lag_crval1"][mi[0]], p["lag_crval2"][mi[1]], p["lag_cdelt1"][mi[2]],
                              p["lag_cdelt2"][mi[3]], p["lag_crota"][mi[4]])
 
+    def _fit_plane(self, plane):
+        """What the Gaussian is fitted to.  best="min": z = (zmax - score) / (zmax - zmin) over the plane's finite
+        entries -- the minimum becomes a peak of height 1, inside the fit's [0, 10] amplitude bound whatever the scale of
+        the score.  (A flat plane gives NaN: the fit's own finite-data check then falls back to the argmin.)"""
+        if self.best != "min":
+            return plane
+        plane = np.asarray(plane, dtype=np.float64)
+        finite = plane[np.isfinite(plane)]
+        zmax, zmin = finite.max(), finite.min()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return (zmax - plane) / (zmax - zmin)
+
     def _compute_shift(self, method="fitting_gaussian"):
         if method != "fitting_gaussian":
             raise NotImplementedError
         mi = self.max_index
-        corr2d = self.corr[:, :, mi[2], mi[3], mi[4]]
+        corr2d = self._fit_plane(self.corr[:, :, mi[2], mi[3], mi[4]])
         px, py = [mi[0]], [mi[1]]
         lenx, leny = corr2d.shape[0], corr2d.shape[1]
         for ii in (-2, -1, 0, 1, 2):

@@ -18,7 +18,7 @@ import numpy as np
 
 from .. import _lib
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
-from .alignment import Alignment
+from .alignment import Alignment, apply_min_overlap, library_method
 
 
 def _angstrom(v):
@@ -31,13 +31,14 @@ class AlignmentSpice(Alignment):
                  lag_cdelt1=None, lag_cdelt2=None, lag_crota=None, lag_solar_r=None, large_fov_window=-1,
                  small_fov_window=-1, parallelism=False, counts_cpu_max=40, display_progress_bar=False,
                  path_save_figure=None, wavelength_interval_to_sum="all", sub_fov_window="all", level=None,
-                 cdelt_semantics="intended", device=None, differential_rotation="reference"):
+                 cdelt_semantics="intended", device=None, differential_rotation="reference", min_overlap=None):
         super().__init__(large_fov_known_pointing=large_fov_known_pointing, small_fov_to_correct=small_fov_to_correct,
                          lag_crval1=lag_crval1, lag_crval2=lag_crval2, lag_cdelt1=lag_cdelt1, lag_cdelt2=lag_cdelt2,
                          lag_crota=lag_crota, display_progress_bar=display_progress_bar, lag_solar_r=lag_solar_r,
                          parallelism=parallelism, counts_cpu_max=counts_cpu_max, large_fov_window=large_fov_window,
                          small_fov_window=small_fov_window, path_save_figure=path_save_figure,
-                         cdelt_semantics=cdelt_semantics, device=device, differential_rotation=differential_rotation)
+                         cdelt_semantics=cdelt_semantics, device=device, differential_rotation=differential_rotation,
+                         min_overlap=min_overlap)
         self.sub_fov_window = sub_fov_window
         self.extend_pixel_size = None
         self.cut_from_center = None
@@ -239,13 +240,13 @@ class AlignementSpiceIterativeContextRaster(AlignmentSpice):
     def __init__(self, large_fov_list_paths, small_fov_to_correct, threshold_time, lag_crval1, lag_crval2, lag_cdelt1,
                  lag_cdelt2, lag_crota, small_fov_value_min=None, parallelism=False, small_fov_value_max=None,
                  counts_cpu_max=40, large_fov_window=-1, small_fov_window=-1, use_tqdm=False, path_save_figure=None,
-                 cdelt_semantics="intended", device=None):
+                 cdelt_semantics="intended", device=None, min_overlap=None):
         super().__init__(large_fov_known_pointing="No_specific_path", small_fov_to_correct=small_fov_to_correct,
                          lag_crval1=lag_crval1, lag_crval2=lag_crval2, lag_cdelt1=lag_cdelt1, lag_cdelt2=lag_cdelt2,
                          lag_crota=lag_crota, lag_solar_r=None, parallelism=parallelism, counts_cpu_max=counts_cpu_max,
                          large_fov_window=large_fov_window, small_fov_window=small_fov_window,
                          display_progress_bar=use_tqdm, path_save_figure=path_save_figure,
-                         cdelt_semantics=cdelt_semantics, device=device)
+                         cdelt_semantics=cdelt_semantics, device=device, min_overlap=min_overlap)
         self.small_fov_value_min = small_fov_value_min
         self.small_fov_value_max = small_fov_value_max
         self.step_figure = False
@@ -325,12 +326,7 @@ class AlignementSpiceIterativeContextRaster(AlignmentSpice):
         self._set_initial_header_values(True)
         if self.unit_lag != self.hdr_small["CUNIT1"]:
             raise ValueError("lag.unit and cUNIT are not the same")
-        if self.method == "correlation":
-            m = _lib.METHOD_CORRELATION
-        elif self.method == "residus":
-            m = _lib.METHOD_RESIDUS
-        else:
-            raise NotImplementedError
+        m = library_method(self.method)
         device = -1 if self.device is None else self.device
         h = _lib.shared_handle(device, self._handle_slot)
         h.reference_tag = None  # (the frames and the SPICE image replace whatever the handle held)
@@ -346,4 +342,6 @@ class AlignementSpiceIterativeContextRaster(AlignmentSpice):
                                cdelt_semantics=sem, vmin=self.small_fov_value_min, vmax=self.small_fov_value_max)
         self.last_stats = h.last_stats()
         results = np.asarray(corr).reshape(lags.shape + (1,))
+        self.last_counts = h.last_counts().reshape(results.shape)
+        results = apply_min_overlap(results, self.last_counts, self.min_overlap)
         return self._wrap(results, "AlignmentResults", restore_units=True)

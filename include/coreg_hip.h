@@ -37,6 +37,12 @@ extern "C" {
 
 #define COREG_METHOD_CORRELATION 0 /* alignment.py:522-542 */
 #define COREG_METHOD_RESIDUS 1     /* alignment.py:544-547 (no NaN mask, quirk Q8) */
+/* np.std(((A - B) / sqrt(A))[isfinite(A) & isfinite(B)]), ddof 0: the residus over the co-finite points (A the reference
+ * on the target grid, B the resampled image).  NaN, as numpy returns it, when no point is co-finite or when a masked term
+ * is not finite (A <= 0: the "poisoned term" rule).  The BEST lag-point is the MINIMUM; about 1 at photon noise.  Equal
+ * bit for bit to COREG_METHOD_RESIDUS wherever every grid point overlaps.  Never re-evaluated ("refine"), like residus.
+ * Meant to be read with the per-lag sample counts (coreg_last_counts). */
+#define COREG_METHOD_RESIDUS_MASKED 2
 
 /* CDELT lag semantics */
 #define COREG_CDELT_INTENDED 0  /* CDELTi += d, PC rebuilt with the new lambda (utils/Util.py:199-215) */
@@ -330,6 +336,14 @@ int coreg_set_pivots(coreg_handle* h, const double* pivots2);
 
 /* Waits for an in-flight device-output sweep (those return without synchronising the stream). */
 int coreg_last_stats(coreg_handle* h, coreg_stats* out);
+
+/* Per-lag sample counts of the last coreg_sweep_*, coreg_finalize_sums or coreg_sweep_context call on this handle, in
+ * the layout of its output (C-order slice [lag_begin, lag_end) of the lag set): for COREG_METHOD_CORRELATION the number
+ * of samples in the lag-point's six sums, for the two residus methods the number of finite terms; 0 where nothing
+ * overlapped, NaN where the lag-point was never evaluated (a shifted header without a map).  dst: that many doubles, on
+ * the host or (dst_on_device) on the handle's device.  Waits for the stream.  A grid share's sweep (option
+ * "shard_world" > 1) has no counts of its own: they come with coreg_finalize_sums. */
+int coreg_last_counts(coreg_handle* h, double* dst, int dst_on_device);
 
 /* Diagnostics.  counts6[0..3]: (tile, lag batch) visits of the sweep kernel's workgroups in the LAST launch of the last
  * sweep -- all; gathered from an LDS window; of those, "interior" (every sample inside the image: no bounds rule); of
@@ -626,6 +640,9 @@ int coreg_multi_sweep_carrington(coreg_multi* m, const coreg_wcs2d* hdr_small, c
 int coreg_multi_sweep_helioprojective(coreg_multi* m, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small,
                                       const coreg_lags* lags, int order, int method, int cdelt_semantics, double* corr_out);
 int coreg_multi_last_stats(coreg_multi* m, int k, coreg_stats* out);
+/* coreg_last_counts for the last coreg_multi_sweep_*: the whole map's counts (as many doubles as corr_out had), put
+ * together on the host from the devices' shares the way the coefficients' host-copy path does it (no collective). */
+int coreg_multi_last_counts(coreg_multi* m, double* dst_host);
 /* The partition a sweep over (n_crval1, n_crval2, n_inner = n_cdelt1 n_cdelt2 n_crota) lag-points gets on `world` GPUs
  * (host-only; checked against euispice_coreg_amd/parallel.py): mode as coreg_multi_last_mode; the GPUs form a
  * g_combo x (g1 x g2) grid: the inner combinations are dealt in g_combo contiguous runs, the (CRVAL1, CRVAL2) plane is
