@@ -291,6 +291,8 @@ SYMBOLS = [
     ("coreg_pixels_set_small", C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32]),
     ("coreg_pixels_shift_large", C.c_int, [_P, C.c_double, C.c_double]),
     ("coreg_pixels_sweep", C.c_int, [_P, C.POINTER(PixelsPlan), _P]),
+    ("coreg_pixels_sweep_method", C.c_int, [_P, C.POINTER(PixelsPlan), C.c_int, _P]),
+    ("coreg_pixels_last_counts", C.c_int, [_P, _P]),
     ("coreg_pixels_get_large_box", C.c_int, [_P, _P]),
     ("coreg_pixels_get_rotated", C.c_int, [_P, C.c_int32, _P]),
     ("coreg_pixels_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
@@ -723,7 +725,7 @@ class CoregHandle(_ImageIntake):
     def pixels_shift_large(self, dx, dy):
         self._chk(self._lib.coreg_pixels_shift_large(self._h, float(dx), float(dy)))
 
-    def pixels_sweep(self, plan):
+    def pixels_sweep(self, plan, method=METHOD_CORRELATION):
         dx = np.ascontiguousarray(plan["lag_dx"], dtype=np.int32)
         dy = np.ascontiguousarray(plan["lag_dy"], dtype=np.int32)
         rot = np.ascontiguousarray(plan["lag_drot_rad"], dtype=np.float64)
@@ -733,12 +735,18 @@ class CoregHandle(_ImageIntake):
                        int(plan["sub_shape"][0]), int(plan["sub_shape"][1]), int(plan["slc_small_ref"][0]),
                        int(plan["slc_small_ref"][1]), int(plan["xc"]), int(plan["yc"]))
         out = np.empty((len(dx), len(dy), len(rot)), dtype=np.float64)
-        rc = self._lib.coreg_pixels_sweep(self._h, C.byref(p), out.ctypes.data)
+        rc = self._lib.coreg_pixels_sweep_method(self._h, C.byref(p), int(method), out.ctypes.data)
         if rc == COREG_EINVAL:
             msg = self._lib.coreg_last_error(self._h).decode("utf-8", "replace")
             if msg.startswith("too large shift"):
                 raise ValueError(msg)
         self._chk(rc)
+        return out
+
+    def pixels_last_counts(self, shape):
+        """Per-lag sample counts of the last pixel-lag sweep, shaped like its cube (float64)."""
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self._lib.coreg_pixels_last_counts(self._h, out.ctypes.data))
         return out
 
     def pixels_get_large_box(self, shape):

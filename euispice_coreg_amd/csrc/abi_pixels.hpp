@@ -19,9 +19,18 @@ int coreg_pixels_shift_large(coreg_handle* h, double dx, double dy) {
     return pixels_shift_large(h, dx, dy);
 }
 
-int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* corr_out) {
+int coreg_pixels_sweep_method(coreg_handle* h, const coreg_pixels_plan* plan, int method, double* out) {
     if (!h) return COREG_EINVAL;
-    return pixels_sweep(h, plan, corr_out);
+    return pixels_sweep(h, plan, method, out);
+}
+
+int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* corr_out) {
+    return coreg_pixels_sweep_method(h, plan, COREG_METHOD_CORRELATION, corr_out);
+}
+
+int coreg_pixels_last_counts(coreg_handle* h, double* dst) {
+    if (!h) return COREG_EINVAL;
+    return pixels_last_counts(h, dst);
 }
 
 int coreg_pixels_get_large_box(coreg_handle* h, double* out) {

@@ -1,12 +1,13 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the integer pixel-lag sweep
 // of pxlshift.AlignmentPixels -- per-handle state, uploads, the displacement of the large image, the
-// sub-resolved box, the rotation planes and the two sweep passes (csrc/kernels_pixels.hpp).
+// sub-resolved box, the rotation planes and the two sweep passes of either score (csrc/kernels_pixels.hpp).
 #pragma once
 
 struct PixelsState {
-    DevBuf large, large_tmp, small, box, planes, sums, plan, corr;
+    DevBuf large, large_tmp, small, box, planes, sums, plan, corr, counts;
     int lW = 0, lH = 0, sW = 0, sH = 0;
     int bW = 0, bH = 0, n_rot = 0;  // what the last sweep left in `box` / `planes`
+    long long n_counts = 0;         // ... and in `counts`: lags of the last sweep, 0 once an image has changed
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
 };
@@ -36,7 +37,8 @@ void pixels_release(coreg_handle* h) {
         st = it->second;
         g_pixels.erase(it);
     }
-    DevBuf* bufs[] = {&st->large, &st->large_tmp, &st->small, &st->box, &st->planes, &st->sums, &st->plan, &st->corr};
+    DevBuf* bufs[] = {&st->large, &st->large_tmp, &st->small, &st->box, &st->planes, &st->sums, &st->plan, &st->corr,
+                      &st->counts};
     for (DevBuf* b : bufs) b->release();
     for (hipEvent_t e : st->ev)
         if (e) (void)hipEventDestroy(e);
@@ -80,6 +82,7 @@ int pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->bW = st->bH = 0;  // (the box of the last sweep is no longer this image's)
+    st->n_counts = 0;
     return pixels_upload(h, st->large, img, dtype, ny, nx, &st->lW, &st->lH);
 }
 
@@ -87,6 +90,7 @@ int pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->n_rot = 0;
+    st->n_counts = 0;
     return pixels_upload(h, st->small, img, dtype, ny, nx, &st->sW, &st->sH);
 }
 
@@ -97,6 +101,7 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     if (!(dx == dx) || !(dy == dy)) return fail(h, COREG_EINVAL, "pixels: the displacement is not a number");
     RETCHK(bind_device(h));
     st->bW = st->bH = 0;
+    st->n_counts = 0;
     const size_t n = (size_t)st->lW * st->lH;
     HIPCHK(st->large_tmp.reserve(n * sizeof(double)));
     PixResample a = {};
@@ -114,7 +119,13 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     return pixels_resample(h, PIX_AFFINE, a);
 }
 
-int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, double* corr_out) {
+int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, double* corr_out) {
+    if (method == COREG_METHOD_RESIDUS)
+        return fail(h, COREG_ENOTIMPL, "pixels: method residus is not implemented (the reference's pxlshift has no such score); "
+                                       "residus_masked is");
+    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS_MASKED)
+        return fail(h, COREG_EINVAL, "pixels: unknown method");
+    const bool resid = method == COREG_METHOD_RESIDUS_MASKED;
     PixelsState* st = pixels_state(h, false);
     if (!st || !st->large.p || !st->small.p) return fail(h, COREG_ESTATE, "pixels: the large and the small image must be set");
     if (!pl || !corr_out || !pl->lag_dx || !pl->lag_dy || !pl->lag_drot) return fail(h, COREG_EINVAL, "pixels: null pointer");
@@ -170,6 +181,8 @@ int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, double* corr_out)
     HIPCHK(st->planes.reserve((size_t)w * hh * pl->n_rot * sizeof(double)));
     HIPCHK(st->sums.reserve((size_t)n_lag * 6 * sizeof(double)));
     HIPCHK(st->corr.reserve((size_t)n_lag * sizeof(double)));
+    HIPCHK(st->counts.reserve((size_t)n_lag * sizeof(double)));
+    st->n_counts = 0;
     for (hipEvent_t& e : st->ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     st->timed = false;
@@ -235,21 +248,28 @@ int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, double* corr_out)
     const dim3 grid((unsigned)n_groups, (unsigned)pl->n_dy, (unsigned)pl->n_rot);
     s.sums0 = nullptr;
     s.sums = sums0;
-    hipLaunchKernelGGL(k_pixels_sweep<0>, grid, dim3(kPixThreads), 0, h->stream, s);
+    if (resid)
+        hipLaunchKernelGGL(k_pixels_sweep<kPixR0>, grid, dim3(kPixThreads), 0, h->stream, s);
+    else
+        hipLaunchKernelGGL(k_pixels_sweep<0>, grid, dim3(kPixThreads), 0, h->stream, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[2], h->stream));
     s.sums0 = sums0;
     s.sums = sums1;
-    hipLaunchKernelGGL(k_pixels_sweep<1>, grid, dim3(kPixThreads), 0, h->stream, s);
+    if (resid)
+        hipLaunchKernelGGL(k_pixels_sweep<kPixR1>, grid, dim3(kPixThreads), 0, h->stream, s);
+    else
+        hipLaunchKernelGGL(k_pixels_sweep<1>, grid, dim3(kPixThreads), 0, h->stream, s);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[3], h->stream));
     hipLaunchKernelGGL(k_pixels_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0,
-                       h->stream, (const double*)sums0, (const double*)sums1, pl->n_dx, pl->n_dy, pl->n_rot,
-                       st->corr.as<double>());
+                       h->stream, (const double*)sums0, (const double*)sums1, pl->n_dx, pl->n_dy, pl->n_rot, (int)resid,
+                       st->corr.as<double>(), st->counts.as<double>());
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_lag * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     st->timed = true;
+    st->n_counts = n_lag;
     return COREG_OK;
 }
 
@@ -286,4 +306,11 @@ int pixels_get_rotated(coreg_handle* h, int32_t k, double* out) {
     if (k < 0 || k >= st->n_rot) return fail(h, COREG_EINVAL, "pixels: rotation index out of range");
     const size_t n = (size_t)st->sW * st->sH;
     return pixels_read(h, st->planes.as<double>() + n * k, n, out);
+}
+
+// per-lag sample counts of the last sweep, laid out like its cube
+int pixels_last_counts(coreg_handle* h, double* out) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || st->n_counts < 1) return fail(h, COREG_ESTATE, "pixels: no sweep has run");
+    return pixels_read(h, st->counts.p, (size_t)st->n_counts, out);
 }

@@ -5,10 +5,16 @@
 //                             sample outside the image, and every value equal to the fill, becomes NaN
 //   k_pixels_sweep<PASS>      one workgroup per (rotation plane, dy, group of <= 16 dx lags within 16 columns): pass 0
 //                             leaves n, sum a, sum b of the kept pixels per lag, pass 1 the centred sums about the
-//                             means of pass 0.  No atomics, no accumulation across workgroups: the sums of a lag depend
+//                             means of pass 0.  Passes kPixR0 / kPixR1 are the same walk for residus_masked, the
+//                             np.std of d = (b - a) / sqrt(b) over isfinite(a) & isfinite(b) (b: the large image, the
+//                             reference): R0 leaves n of the finite terms, sum d and the number of kept terms that are
+//                             not finite (b <= 0: "poisoned", DESIGN Q23), R1 the squares about the mean of R0; the
+//                             band's sqrt(b) is taken once per staged box pixel, in a second LDS plane these two passes
+//                             alone declare.  No atomics, no accumulation across workgroups: the sums of a lag depend
 //                             on the lag alone, not on the group it runs in
-//   k_pixels_finalize         float32-rounded numerator / sqrt(product of the centred squares), NaN for an empty or flat
-//                             overlap
+//   k_pixels_finalize         correlation: float32-rounded numerator / sqrt(product of the centred squares), NaN for an
+//                             empty or flat overlap; residus_masked: sqrt(sum of squares / n), NaN for no finite term
+//                             or a poisoned one; either way the lag's sample count
 //
 // Reference arithmetic restated (paths relative to euispice_coreg/): pxlshift/alignment_pixels.py:38-55 (mask),
 // pxlshift/c_correlate.py:41-63 (Pearson, numerator stored as float32), :126-143 (sub-resolution), :72-81 +
@@ -21,6 +27,7 @@ constexpr int kPixThreads = 256;
 constexpr int kPixTile = 2048;    // small-image pixels staged per band (8 per thread)
 constexpr int kPixBandRows = 64;  // rows per band at most: bounds the G - 1 extra columns of the large rows
 constexpr int kPixLdsB = kPixTile + kPixBandRows * (kPixG - 1);
+constexpr int kPixR0 = 2, kPixR1 = 3;  // k_pixels_sweep<PASS>: the two passes of residus_masked (0 / 1: Pearson)
 
 enum { PIX_AFFINE = 0, PIX_POLAR = 1 };
 
@@ -92,7 +99,7 @@ struct PixSweep {
     const PixGroup* groups;
     const int* lag_dx;
     const int* lag_dy;
-    const double* sums0;   // pass 1 reads: [n_rot][n_dy][n_dx][3] = n, sum a, sum b
+    const double* sums0;   // pass 1 / R1 reads: [n_rot][n_dy][n_dx][3] = n, sum a, sum b / n finite, sum d, n poisoned
     double* sums;          // the pass's output, same layout
     int w, h, bW, bH, n_dx, n_dy, min_dx, min_dy;
     int cw, bh;            // band: columns [c0, c0 + cw) x rows [r0, r0 + bh), cw * bh <= kPixTile, bh <= kPixBandRows
@@ -101,7 +108,8 @@ struct PixSweep {
 template <int PASS>
 __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
     __shared__ double lds_a[kPixTile];
-    __shared__ double lds_b[kPixLdsB];
+    constexpr bool RESID = PASS >= kPixR0;
+    __shared__ double lds_b[(RESID ? 2 : 1) * kPixLdsB];  // residus passes: the roots of the box pixels behind them
     __shared__ double lds_red[kPixThreads / 64][3 * kPixG];
     const int tid = threadIdx.x;
     const PixGroup g = p.groups[blockIdx.x];
@@ -123,6 +131,10 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
             ma[s] = s0[1] / s0[0];
             mb[s] = s0[2] / s0[0];
         }
+        if (PASS == kPixR1 && used) {
+            const double* s0 = p.sums0 + 3 * (lag0 + s);
+            ma[s] = s0[1] / s0[0];  // mean of the finite terms
+        }
     }
     double acc0[kPixG], acc1[kPixG], acc2[kPixG];
 #pragma unroll
@@ -141,14 +153,22 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
             for (int q = tid; q < nr * ncb; q += kPixThreads) {
                 const int r = q / ncb, c = q - r * ncb;
                 const int bc = col_off + c0 + c;  // (columns past the box belong to unused slots only)
-                lds_b[q] = bc < p.bW ? p.box[(size_t)(row_off + r0 + r) * p.bW + bc] : 0.0;
+                if (!RESID) {
+                    lds_b[q] = bc < p.bW ? p.box[(size_t)(row_off + r0 + r) * p.bW + bc] : 0.0;
+                } else {
+                    // a pixel that is not finite, and a column past the box, is staged as NaN: never kept, never poisoned
+                    double b = bc < p.bW ? p.box[(size_t)(row_off + r0 + r) * p.bW + bc] : __builtin_nan("");
+                    if (!(fabs(b) < __builtin_inf())) b = __builtin_nan("");
+                    lds_b[q] = b;
+                    lds_b[kPixLdsB + q] = sqrt(b);
+                }
             }
             __syncthreads();
             for (int q = tid; q < nr * nc; q += kPixThreads) {
                 const int r = q / nc, c = q - r * nc;
                 const double a = lds_a[q];
                 const double* brow = lds_b + r * ncb + c;
-                const bool a_ok = a == a;
+                const bool a_ok = RESID ? fabs(a) < __builtin_inf() : a == a;
 #pragma unroll
                 for (int s = 0; s < kPixG; ++s) {
                     const double b = brow[off[s]];
@@ -157,11 +177,23 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
                         acc0[s] += keep ? 1.0 : 0.0;
                         acc1[s] += keep ? a : 0.0;
                         acc2[s] += keep ? b : 0.0;
-                    } else {
+                    } else if (PASS == 1) {
                         const double da = a - ma[s], db = b - mb[s];
                         acc0[s] += keep ? da * db : 0.0;
                         acc1[s] += keep ? da * da : 0.0;
                         acc2[s] += keep ? db * db : 0.0;
+                    } else {
+                        // IEEE division by the staged root; a kept term is finite unless b <= 0
+                        const double d = (b - a) / brow[kPixLdsB + off[s]];
+                        const bool fin = keep & (fabs(d) < __builtin_inf());
+                        if (PASS == kPixR0) {
+                            acc0[s] += fin ? 1.0 : 0.0;
+                            acc1[s] += fin ? d : 0.0;
+                            acc2[s] += (keep & !fin) ? 1.0 : 0.0;
+                        } else {
+                            const double dd = d - ma[s];
+                            acc0[s] += fin ? dd * dd : 0.0;
+                        }
                     }
                 }
             }
@@ -193,17 +225,26 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
     }
 }
 
-// corr[(i * n_dy + j) * n_rot + k] from the sums of lag (k, j, i)
+// corr[(i * n_dy + j) * n_rot + k] and counts[...] from the sums of lag (k, j, i); resid: the residus_masked score
 __global__ __launch_bounds__(kPixThreads) void k_pixels_finalize(const double* __restrict__ sums0, const double* __restrict__ sums1,
-                                                                  int n_dx, int n_dy, int n_rot, double* __restrict__ corr) {
+                                                                  int n_dx, int n_dy, int n_rot, int resid,
+                                                                  double* __restrict__ corr, double* __restrict__ counts) {
     const long long n = (long long)n_dx * n_dy * n_rot;
     const long long q = (long long)blockIdx.x * kPixThreads + threadIdx.x;
     if (q >= n) return;
     const int i = (int)(q % n_dx), j = (int)((q / n_dx) % n_dy), k = (int)(q / ((long long)n_dx * n_dy));
-    const double cnt = sums0[3 * q], num = sums1[3 * q], va = sums1[3 * q + 1], vb = sums1[3 * q + 2];
+    const double cnt = sums0[3 * q];
     double r = __builtin_nan("");
-    if (cnt > 0.0 && va != 0.0 && vb != 0.0) r = (double)(float)num / sqrt(va * vb);
-    corr[((long long)i * n_dy + j) * n_rot + k] = r;
+    if (!resid) {
+        const double num = sums1[3 * q], va = sums1[3 * q + 1], vb = sums1[3 * q + 2];
+        if (cnt > 0.0 && va != 0.0 && vb != 0.0) r = (double)(float)num / sqrt(va * vb);
+    } else {
+        // np.std of the kept terms: NaN when one of them is not finite (sums0's third entry counts those)
+        if (cnt > 0.0 && sums0[3 * q + 2] == 0.0) r = sqrt(sums1[3 * q] / cnt);
+    }
+    const long long o = ((long long)i * n_dy + j) * n_rot + k;
+    corr[o] = r;
+    counts[o] = cnt;
 }
 
 }  // namespace coreg

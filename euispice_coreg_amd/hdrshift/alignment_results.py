@@ -25,6 +25,73 @@ def twoD_Gaussian(xy, amplitude, xo, yo, sigma_x, sigma_y, offset):
     return g.ravel()
 
 
+def fit_plane(plane, best="max"):
+    """What the Gaussian is fitted to.  best="min": z = (zmax - score) / (zmax - zmin) over the plane's finite
+    entries -- the minimum becomes a peak of height 1, inside the fit's [0, 10] amplitude bound whatever the scale of
+    the score.  (A flat plane gives NaN: the fit's own finite-data check then falls back to the argmin.)"""
+    if best != "min":
+        return plane
+    plane = np.asarray(plane, dtype=np.float64)
+    finite = plane[np.isfinite(plane)]
+    zmax, zmin = finite.max(), finite.min()
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return (zmax - plane) / (zmax - zmin)
+
+
+def gaussian_sub_lag(plane, peak, best="max", fit="native"):
+    """The sub-lag position of the best entry `peak` = (i, j) of a 2-D score plane, in index units: the 2-D Gaussian
+    fit of AlignmentResults.py:218-289 on the entries around it (`fit_plane(plane, best)`; fit: "native" = csrc/fit.hpp,
+    "scipy" = scipy.optimize.curve_fit).  Shared by `AlignmentResults` and `pxlshift.PixelAlignmentResults`.
+    Returns ((x, y), fit_info); (None, fit_info) with a warning when the fit cannot run or fails -- the caller then
+    takes the best entry itself.  fit_info: {"status", "nfev"} of the native fit, None when it was not reached (a
+    RuntimeError for an exhausted fit carries it as its `fit_info`)."""
+    mi = peak
+    fit_info = None
+    corr2d = fit_plane(plane, best)
+    px, py = [mi[0]], [mi[1]]
+    lenx, leny = corr2d.shape[0], corr2d.shape[1]
+    for ii in (-2, -1, 0, 1, 2):
+        for jj in (-2, -1, 0, 1, 2):
+            x, y = mi[0] + ii, mi[1] + jj
+            # (sic) only index -1 is excluded, the peak sample is duplicated: AlignmentResults.py:230-239, quirk Q13
+            if (x != -1) and (x < lenx) and (y != -1) and (y < leny):
+                px.append(x)
+                py.append(y)
+    if len(px) < 4:
+        warnings.warn(" Cannot compute shift with Gaussian fitting: not enough points")
+        return None, fit_info
+    p0 = (np.float64(np.ravel(corr2d[mi[0], mi[1]])[0]), np.float64(mi[0]), np.float64(mi[1]), 1.0, 1.0, 0.9)
+    bounds = ([0.0, mi[0] - 5.0, mi[1] - 5.0, 0.0, 0.0, -10.0], [10.0, mi[0] + 5.0, mi[1] + 5.0, 1000.0, 1000.0, 10.0])
+    try:
+        A = (np.float64(px), np.float64(py))
+        # the un-excluded index -2 wraps around; on an axis shorter than 2 it is out of range and the reference
+        # dies with IndexError -- here that case falls back to the argmax like a failed fit does
+        B = np.float64(corr2d[px, py].ravel())
+        if fit == "scipy":
+            from scipy.optimize import curve_fit
+            popt, _ = curve_fit(f=twoD_Gaussian, xdata=A, ydata=B, p0=p0, bounds=bounds)
+        else:
+            # curve_fit's own checks, in its order: finite data (check_finite=True), p0 inside the bounds,
+            # finite residuals at p0 -- all ValueError, i.e. the reference's argmax fallback
+            if not (np.all(np.isfinite(B)) and np.all(np.isfinite(p0))):
+                raise ValueError("array must not contain infs or NaNs")
+            if not all(lo <= v <= hi for v, lo, hi in zip(p0, *bounds)):
+                raise ValueError("`x0` is infeasible.")
+            popt, status, nfev = _lib.fit_gaussian2d(A[0], A[1], B, p0, bounds[0], bounds[1])
+            fit_info = {"status": status, "nfev": nfev}
+            if status == -1:
+                raise ValueError("Residuals are not finite in the initial point.")
+            if status == 0:  # curve_fit: `if not res.success: raise RuntimeError` -- not caught by the reference
+                err = RuntimeError("Optimal parameters not found: The maximum number of function evaluations is "
+                                   "exceeded.")
+                err.fit_info = fit_info
+                raise err
+    except (ValueError, IndexError):
+        warnings.warn("Gaussian fitting failed, setting shift params as the pixel of the maximal correlation")
+        return None, fit_info
+    return (popt[1], popt[2]), fit_info
+
+
 class AlignmentResults:
 
     def __init__(self, corr, lag_crval1, lag_crval2, lag_cdelt1, lag_cdelt2, lag_crota, unit_lag,
@@ -37,7 +104,7 @@ class AlignmentResults:
         self.fit = fit
         self.fit_info = None
         # best: "max" (a correlation: the reference's argmax) or "min" (a residus: `max_index` is the argmin, and the
-        # sub-lag fit runs on the flipped, rescaled map -- _fit_plane); n_samples: per-lag sample counts, kept as given
+        # sub-lag fit runs on the flipped, rescaled map -- fit_plane); n_samples: per-lag sample counts, kept as given
         if best not in ("max", "min"):
             raise ValueError("best must be 'max' or 'min'")
         self.best = best
@@ -76,68 +143,24 @@ class AlignmentResults:
         self.shift_arcsec = (p["lag_crval1"][mi[0]], p["lag_crval2"][mi[1]], p["lag_cdelt1"][mi[2]],
                              p["lag_cdelt2"][mi[3]], p["lag_crota"][mi[4]])
 
-    def _fit_plane(self, plane):
-        """What the Gaussian is fitted to.  best="min": z = (zmax - score) / (zmax - zmin) over the plane's finite
-        entries -- the minimum becomes a peak of height 1, inside the fit's [0, 10] amplitude bound whatever the scale of
-        the score.  (A flat plane gives NaN: the fit's own finite-data check then falls back to the argmin.)"""
-        if self.best != "min":
-            return plane
-        plane = np.asarray(plane, dtype=np.float64)
-        finite = plane[np.isfinite(plane)]
-        zmax, zmin = finite.max(), finite.min()
-        with np.errstate(invalid="ignore", divide="ignore"):
-            return (zmax - plane) / (zmax - zmin)
-
     def _compute_shift(self, method="fitting_gaussian"):
         if method != "fitting_gaussian":
             raise NotImplementedError
         mi = self.max_index
-        corr2d = self._fit_plane(self.corr[:, :, mi[2], mi[3], mi[4]])
-        px, py = [mi[0]], [mi[1]]
-        lenx, leny = corr2d.shape[0], corr2d.shape[1]
-        for ii in (-2, -1, 0, 1, 2):
-            for jj in (-2, -1, 0, 1, 2):
-                x, y = mi[0] + ii, mi[1] + jj
-                # (sic) only index -1 is excluded, the peak sample is duplicated: AlignmentResults.py:230-239, quirk Q13
-                if (x != -1) and (x < lenx) and (y != -1) and (y < leny):
-                    px.append(x)
-                    py.append(y)
-        if len(px) < 4:
-            warnings.warn(" Cannot compute shift with Gaussian fitting: not enough points")
-            self._argmax_shift()
-            return None
-        p0 = (np.float64(np.ravel(corr2d[mi[0], mi[1]])[0]), np.float64(mi[0]), np.float64(mi[1]), 1.0, 1.0, 0.9)
-        bounds = ([0.0, mi[0] - 5.0, mi[1] - 5.0, 0.0, 0.0, -10.0], [10.0, mi[0] + 5.0, mi[1] + 5.0, 1000.0, 1000.0, 10.0])
         try:
-            A = (np.float64(px), np.float64(py))
-            # the un-excluded index -2 wraps around; on an axis shorter than 2 it is out of range and the reference
-            # dies with IndexError -- here that case falls back to the argmax like a failed fit does
-            B = np.float64(corr2d[px, py].ravel())
-            if self.fit == "scipy":
-                from scipy.optimize import curve_fit
-                popt, _ = curve_fit(f=twoD_Gaussian, xdata=A, ydata=B, p0=p0, bounds=bounds)
-            else:
-                # curve_fit's own checks, in its order: finite data (check_finite=True), p0 inside the bounds,
-                # finite residuals at p0 -- all ValueError, i.e. the reference's argmax fallback
-                if not (np.all(np.isfinite(B)) and np.all(np.isfinite(p0))):
-                    raise ValueError("array must not contain infs or NaNs")
-                if not all(lo <= v <= hi for v, lo, hi in zip(p0, *bounds)):
-                    raise ValueError("`x0` is infeasible.")
-                popt, status, nfev = _lib.fit_gaussian2d(A[0], A[1], B, p0, bounds[0], bounds[1])
-                self.fit_info = {"status": status, "nfev": nfev}
-                if status == -1:
-                    raise ValueError("Residuals are not finite in the initial point.")
-                if status == 0:  # curve_fit: `if not res.success: raise RuntimeError` -- not caught by the reference
-                    raise RuntimeError("Optimal parameters not found: The maximum number of function evaluations is "
-                                       "exceeded.")
-        except (ValueError, IndexError):
-            warnings.warn("Gaussian fitting failed, setting shift params as the pixel of the maximal correlation")
+            pos, info = gaussian_sub_lag(self.corr[:, :, mi[2], mi[3], mi[4]], (mi[0], mi[1]), self.best, self.fit)
+        except RuntimeError as e:
+            self.fit_info = getattr(e, "fit_info", self.fit_info)
+            raise
+        if info is not None:
+            self.fit_info = info
+        if pos is None:
             self._argmax_shift()
             return None
         p = self.parameters_alignment_arcsec
-        sx = np.interp(popt[1], np.arange(len(p["lag_crval1"])), p["lag_crval1"])
-        sy = np.interp(popt[2], np.arange(len(p["lag_crval2"])), p["lag_crval2"])
-        self.shift_pixels = (popt[1], popt[2], mi[2], mi[3], mi[4])
+        sx = np.interp(pos[0], np.arange(len(p["lag_crval1"])), p["lag_crval1"])
+        sy = np.interp(pos[1], np.arange(len(p["lag_crval2"])), p["lag_crval2"])
+        self.shift_pixels = (pos[0], pos[1], mi[2], mi[3], mi[4])
         self.shift_arcsec = (sx, sy, p["lag_cdelt1"][mi[2]], p["lag_cdelt2"][mi[3]], p["lag_crota"][mi[4]])
         return True
 

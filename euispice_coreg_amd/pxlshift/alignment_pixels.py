@@ -2,8 +2,14 @@
 `AlignmentPixels` -- drop-in for euispice_coreg.pxlshift.AlignmentPixels (pxlshift/alignment_pixels.py:14-157): the
 large image is brought to the small image's pixel size and the small image is slid over it in whole pixels, and
 rotated about its centre, one masked Pearson coefficient per (dx, dy, drot).  The whole lag cube is one library call
-(include/coreg_hip.h: coreg_pixels_sweep); what is not per-pixel work -- ratios, shapes, slice, bounds, the displacement
-of `shift_solar_rotation_dx_large` -- is `host_plan`, numpy only and callable without a GPU.
+(include/coreg_hip.h: coreg_pixels_sweep_method); what is not per-pixel work -- ratios, shapes, slice, bounds, the
+displacement of `shift_solar_rotation_dx_large`, the checks of `method` / `min_overlap` -- is `host_plan`, numpy only and
+callable without a GPU.
+
+Beyond the reference (the defaults return what it returns): `method="residus_masked"`, the np.std of
+(large - small) / sqrt(large) over the pixels finite in both images, best entry = minimum; `last_counts`, the samples
+behind every entry of the last cube; `min_overlap`, entries of fewer samples set to NaN (hdrshift.alignment
+.apply_min_overlap); `return_type="PixelAlignmentResults"` (pixel_alignment_results.py).
 
 Differences from the reference, all deliberate:
   * a second `find_best_parameters` call starts from the file's pixels again (the reference sub-resolves the already
@@ -17,7 +23,10 @@ from __future__ import annotations
 import numpy as np
 
 from .. import _lib
+from ..hdrshift.alignment import apply_min_overlap, library_method, min_overlap_floor
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
+
+_RETURN_TYPES = ("corr", "PixelAlignmentResults")
 
 
 def _integer_lags(v, name):
@@ -40,10 +49,13 @@ class AlignmentPixels:
         data, hdr = fits_io.read_image(small_fov_to_correct, window_small)
         self.hdr_small = fits_io.Header(hdr).copy()
         self.data_small = np.array(fits_io.native_pixels(data), dtype=np.float64)
+        self.large_fov_known_pointing, self.window_large = large_fov_known_pointing, window_large
+        self.small_fov_to_correct, self.window_small = small_fov_to_correct, window_small
         self.device = device
         self.slc_small_ref = None
         self.ratio_res_1 = self.ratio_res_2 = None
         self.last_timing = None
+        self.last_counts = None
 
     # ------------------------------------------------------------------------------------------------------------
     def _return_shift_large_fov_solar_rotation(self):
@@ -74,8 +86,15 @@ class AlignmentPixels:
             return float((d1 / hl["CDELT1"]) * np.cos(-theta)), float((d2 / hl["CDELT2"]) * np.sin(-theta))
         return float(d1 / hl["CDELT1"]), 0.0
 
-    def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False) -> dict:
+    def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
+                  method="correlation", min_overlap=None) -> dict:
         """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU)."""
+        method_code = library_method(method)
+        if method_code == _lib.METHOD_RESIDUS:
+            raise NotImplementedError("pxlshift has no unmasked 'residus' (the reference's pxlshift has no such score): "
+                                      "use 'residus_masked'")
+        if min_overlap is not None:
+            min_overlap_floor(min_overlap)  # (a fraction is taken of the sweep's largest count, once that is known)
         dx, dy = _integer_lags(lag_dx, "lag_dx"), _integer_lags(lag_dy, "lag_dy")
         drot = np.atleast_1d(np.asarray(lag_drot, dtype=np.float64))
         if drot.ndim != 1 or drot.size == 0:
@@ -100,14 +119,22 @@ class AlignmentPixels:
             raise ValueError("too large shift : outside FSI")
         plan = {"lag_dx": dx, "lag_dy": dy, "lag_drot": drot, "lag_drot_rad": drot_rad, "unit_rot": unit_rot,
                 "ratio_res_1": float(ratio1), "ratio_res_2": float(ratio2), "sub_shape": sub, "slc_small_ref": tuple(l),
-                "xc": round(w / 2), "yc": round(h / 2), "shift_large": None}
+                "xc": round(w / 2), "yc": round(h / 2), "shift_large": None, "method": method,
+                "method_code": method_code, "min_overlap": min_overlap}
         if shift_solar_rotation_dx_large:
             plan["shift_large"] = self._shift_large_fov_displacement()
         return plan
 
-    def find_best_parameters(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False):
-        """alignment_pixels.py:57-84: correlation cube [len(lag_dx), len(lag_dy), len(lag_drot)], float64."""
-        plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large)
+    def find_best_parameters(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
+                             method="correlation", min_overlap=None, return_type="corr"):
+        """alignment_pixels.py:57-84: correlation cube [len(lag_dx), len(lag_dy), len(lag_drot)], float64.
+        method: "correlation" (best = maximum) or "residus_masked" (best = minimum).  `self.last_counts`: the samples
+        behind every entry, shaped like the cube (before `min_overlap`).  min_overlap: None, a count >= 1 or a fraction
+        in (0, 1) of the sweep's largest count; entries of fewer samples become NaN, ValueError when none is left.
+        return_type: "corr" (the cube) or "PixelAlignmentResults"."""
+        if return_type not in _RETURN_TYPES:
+            raise ValueError(f"return_type must be one of {_RETURN_TYPES}")
+        plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap)
         self.lag_dx, self.lag_dy, self.lag_drot, self.unit_rot = lag_dx, lag_dy, lag_drot, unit_rot
         self.ratio_res_1, self.ratio_res_2 = plan["ratio_res_1"], plan["ratio_res_2"]
         l, (h, w) = plan["slc_small_ref"], self.data_small.shape
@@ -120,10 +147,18 @@ class AlignmentPixels:
             dx, dy = plan["shift_large"]
             hnd.pixels_shift_large(dx, dy)
             print(f"corrected solar rotation on FSI on CRVAL1: {dx=}, {dy=}")
-        corr = hnd.pixels_sweep(plan)
+        corr = hnd.pixels_sweep(plan, plan["method_code"])
         self.last_timing = hnd.pixels_last_timing()
+        self.last_counts = hnd.pixels_last_counts(corr.shape)
         self._last_plan = plan
-        return corr
+        corr = apply_min_overlap(corr, self.last_counts, min_overlap)
+        if return_type == "corr":
+            return corr
+        from .pixel_alignment_results import PixelAlignmentResults
+        return PixelAlignmentResults(corr, plan["lag_dx"], plan["lag_dy"], plan["lag_drot"], unit_rot=unit_rot,
+                                     method=method, n_samples=self.last_counts,
+                                     large_fov_path=self.large_fov_known_pointing, large_fov_window=self.window_large,
+                                     small_fov_path=self.small_fov_to_correct)
 
     # read-backs of the last call's device images (tests, inspection)
     def _large_box(self):
@@ -140,17 +175,28 @@ def align_pixels_shift(delta_pix1, delta_pix2, windows, large_fov_fits_path, lar
     """Util.AlignCommonUtil.align_pixels_shift (utils/Util.py:248-278): the header of the small image's window with
     CRVAL at the large image's centre plus (delta_pix1, delta_pix2) of its own pixels, CRPIX at its own centre.  As the
     reference, it returns the header of the last window of `windows`."""
+    mid = large_fov_centre(large_fov_fits_path, large_fov_window)
+    out = None
+    for win in windows:
+        out = fits_io.Header(fits_io.read_header(small_fov_path, win)).copy()
+        set_pixels_shift_cards(out, mid, delta_pix1, delta_pix2)
+    return out
+
+
+def large_fov_centre(large_fov_fits_path, large_fov_window):
+    """(longitude, latitude) [deg] of the centre of the large image's window (utils/Util.py:254-262)."""
     header_fsi = fits_io.Header(fits_io.read_header(large_fov_fits_path, large_fov_window))
     w_fsi = wcs_tan.TanWcs(header_fsi)
     naxis1, naxis2 = w_fsi.naxis
     lon_mid, lat_mid = w_fsi.pixel_to_world(np.array([(naxis1 - 1) / 2]), np.array([(naxis2 - 1) / 2]))
-    out = None
-    for win in windows:
-        out = fits_io.Header(fits_io.read_header(small_fov_path, win)).copy()
-        n1 = out["ZNAXIS1"] if "ZNAXIS1" in out else out["NAXIS1"]
-        n2 = out["ZNAXIS2"] if "ZNAXIS2" in out else out["NAXIS2"]
-        out["CRVAL1"] = float(hdrutil.convert(lon_mid[0], "deg", out["CUNIT1"])) + delta_pix1 * out["CDELT1"]
-        out["CRVAL2"] = float(hdrutil.convert(lat_mid[0], "deg", out["CUNIT2"])) + delta_pix2 * out["CDELT2"]
-        out["CRPIX1"] = (n1 + 1) / 2
-        out["CRPIX2"] = (n2 + 1) / 2
-    return out
+    return lon_mid[0], lat_mid[0]
+
+
+def set_pixels_shift_cards(out, mid, delta_pix1, delta_pix2):
+    """The four cards `align_pixels_shift` sets, in place (utils/Util.py:266-276)."""
+    n1 = out["ZNAXIS1"] if "ZNAXIS1" in out else out["NAXIS1"]
+    n2 = out["ZNAXIS2"] if "ZNAXIS2" in out else out["NAXIS2"]
+    out["CRVAL1"] = float(hdrutil.convert(mid[0], "deg", out["CUNIT1"])) + delta_pix1 * out["CDELT1"]
+    out["CRVAL2"] = float(hdrutil.convert(mid[1], "deg", out["CUNIT2"])) + delta_pix2 * out["CDELT2"]
+    out["CRPIX1"] = (n1 + 1) / 2
+    out["CRPIX2"] = (n2 + 1) / 2

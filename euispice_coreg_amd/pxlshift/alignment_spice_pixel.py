@@ -28,10 +28,13 @@ class AlignmentSpicePixel(AlignmentPixels):
         data, hdr = fits_io.read_image(fsi_path, fsi_window)
         self.hdr_large = fits_io.Header(hdr).copy()
         self.data_large = np.array(fits_io.native_pixels(data), dtype=np.float64)
+        self.large_fov_known_pointing, self.window_large = fsi_path, fsi_window
+        self.small_fov_to_correct, self.window_small = spice_path, spice_window
         self.device = device
         self.slc_small_ref = None
         self.ratio_res_1 = self.ratio_res_2 = None
         self.last_timing = None
+        self.last_counts = None
         self._extract_spice_data_header(level=level, index_amplitude=index_amplitude)
 
     def _extract_spice_data_header(self, level, index_amplitude=None):

@@ -544,7 +544,10 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  * image -- rotated about its centre by a polar round trip for drot != 0 (order 1, fill -32762 -> NaN), always from the
  * original -- is correlated with the window of the sub-resolved image at rows l0 + dy ..., columns l1 + dx ...: masked
  * Pearson coefficient about the means of the kept pixels, the numerator rounded to float32 before the division
- * (pxlshift/c_correlate.py:51-61), NaN for an empty or flat overlap.  Two deterministic passes (csrc/kernels_pixels.hpp);
+ * (pxlshift/c_correlate.py:51-61), NaN for an empty or flat overlap.  A second score, COREG_METHOD_RESIDUS_MASKED: with a
+ * the small image's pixel and b the sub-resolved large image's (the reference, as on the header-shift paths),
+ * np.std(d[isfinite(a) & isfinite(b)]) of d = (b - a) / sqrt(b), best entry = minimum; NaN when no point is kept or a kept
+ * term is not finite (b <= 0), 0.0 for one kept point.  Two deterministic passes per score (csrc/kernels_pixels.hpp);
  * the result of a lag does not depend on the other lags of the call.  All calls run on the handle's stream and return
  * with their work complete as far as the caller's memory is concerned.
  *   coreg_pixels_set_large / _set_small  host pixels [ny][nx], dtype COREG_F32 / COREG_F64; kept as float64
@@ -553,10 +556,18 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  *   coreg_pixels_sweep                   corr_out[n_dx][n_dy][n_rot], C order.  COREG_EINVAL with the reference's text
  *                                        "too large shift : outside FSI" when a lag's window leaves the sub-resolved image
  *                                        (checked for every lag before any GPU work)
+ *   coreg_pixels_sweep_method            the same with the score chosen: COREG_METHOD_CORRELATION (what coreg_pixels_sweep
+ *                                        runs) or COREG_METHOD_RESIDUS_MASKED; COREG_METHOD_RESIDUS is COREG_ENOTIMPL (the
+ *                                        reference's pxlshift has no such score), any other value COREG_EINVAL
+ *   coreg_pixels_last_counts             dst[n_dx][n_dy][n_rot] (host memory), the samples behind every entry of the last
+ *                                        sweep: the kept pixels for the correlation, the finite terms for residus_masked.
+ *                                        COREG_ESTATE before a sweep and once coreg_pixels_set_large / _set_small /
+ *                                        _shift_large has changed an image
  *   coreg_pixels_get_large_box           the part of the sub-resolved image the last sweep could read:
  *                                        [h + max dy - min dy][w + max dx - min dx] from (l0 + min dy, l1 + min dx) on
  *   coreg_pixels_get_rotated             plane k [h][w] of the last sweep
- *   coreg_pixels_last_timing             ms[3]: preparation (box + planes), pass 0, pass 1 of the last sweep (HIP events) */
+ *   coreg_pixels_last_timing             ms[3]: preparation (box + planes), first pass, second pass of the last sweep,
+ *                                        whichever score it ran (HIP events) */
 typedef struct coreg_pixels_plan {
     double ratio1, ratio2;    /* sample k of the sub-resolved image lies at x = k ratio1, y = k ratio2 of the large image:
                                  CDELTi(small, in the large image's unit) / CDELTi(large)                              */
@@ -572,6 +583,8 @@ int coreg_pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t 
 int coreg_pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, int32_t nx);
 int coreg_pixels_shift_large(coreg_handle* h, double dx, double dy);
 int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* corr_out);
+int coreg_pixels_sweep_method(coreg_handle* h, const coreg_pixels_plan* plan, int method, double* out);
+int coreg_pixels_last_counts(coreg_handle* h, double* dst);
 int coreg_pixels_get_large_box(coreg_handle* h, double* out);
 int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out);
 int coreg_pixels_last_timing(coreg_handle* h, double* ms);
