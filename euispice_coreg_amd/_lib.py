@@ -293,6 +293,8 @@ SYMBOLS = [
     ("coreg_pixels_sweep", C.c_int, [_P, C.POINTER(PixelsPlan), _P]),
     ("coreg_pixels_sweep_method", C.c_int, [_P, C.POINTER(PixelsPlan), C.c_int, _P]),
     ("coreg_pixels_last_counts", C.c_int, [_P, _P]),
+    ("coreg_pixels_sweep_tiles", C.c_int, [_P, C.POINTER(PixelsPlan), C.c_int, C.c_int32, C.c_int32, _P]),
+    ("coreg_pixels_last_tile_counts", C.c_int, [_P, _P]),
     ("coreg_pixels_get_large_box", C.c_int, [_P, _P]),
     ("coreg_pixels_get_rotated", C.c_int, [_P, C.c_int32, _P]),
     ("coreg_pixels_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
@@ -725,7 +727,7 @@ class CoregHandle(_ImageIntake):
     def pixels_shift_large(self, dx, dy):
         self._chk(self._lib.coreg_pixels_shift_large(self._h, float(dx), float(dy)))
 
-    def pixels_sweep(self, plan, method=METHOD_CORRELATION):
+    def _pixels_sweep(self, plan, method, tile_shape):
         dx = np.ascontiguousarray(plan["lag_dx"], dtype=np.int32)
         dy = np.ascontiguousarray(plan["lag_dy"], dtype=np.int32)
         rot = np.ascontiguousarray(plan["lag_drot_rad"], dtype=np.float64)
@@ -734,8 +736,17 @@ class CoregHandle(_ImageIntake):
                        rot.ctypes.data_as(C.POINTER(C.c_double)), len(dx), len(dy), len(rot),
                        int(plan["sub_shape"][0]), int(plan["sub_shape"][1]), int(plan["slc_small_ref"][0]),
                        int(plan["slc_small_ref"][1]), int(plan["xc"]), int(plan["yc"]))
-        out = np.empty((len(dx), len(dy), len(rot)), dtype=np.float64)
-        rc = self._lib.coreg_pixels_sweep_method(self._h, C.byref(p), int(method), out.ctypes.data)
+        if tile_shape is None:
+            out = np.empty((len(dx), len(dy), len(rot)), dtype=np.float64)
+            rc = self._lib.coreg_pixels_sweep_method(self._h, C.byref(p), int(method), out.ctypes.data)
+        else:
+            # (a tile shape the library refuses gives no grid: nothing is allocated for it)
+            th, tw = int(tile_shape[0]), int(tile_shape[1])
+            h, w = (int(v) for v in plan["small_shape"])
+            ok = 1 <= th <= h and 1 <= tw <= w and -(-h // th) * -(-w // tw) * len(rot) <= 65535
+            grid = (-(-h // th), -(-w // tw)) if ok else (0, 0)
+            out = np.empty(grid + (len(dx), len(dy), len(rot)), dtype=np.float64)
+            rc = self._lib.coreg_pixels_sweep_tiles(self._h, C.byref(p), int(method), th, tw, out.ctypes.data)
         if rc == COREG_EINVAL:
             msg = self._lib.coreg_last_error(self._h).decode("utf-8", "replace")
             if msg.startswith("too large shift"):
@@ -743,10 +754,23 @@ class CoregHandle(_ImageIntake):
         self._chk(rc)
         return out
 
+    def pixels_sweep(self, plan, method=METHOD_CORRELATION):
+        return self._pixels_sweep(plan, method, None)
+
+    def pixels_sweep_tiles(self, plan, method=METHOD_CORRELATION, tile_shape=None):
+        """The cube of every tile, [n_ty, n_tx, n_dx, n_dy, n_rot]; tile_shape: (rows, columns), default the plan's."""
+        return self._pixels_sweep(plan, method, plan["tile_shape"] if tile_shape is None else tile_shape)
+
     def pixels_last_counts(self, shape):
         """Per-lag sample counts of the last pixel-lag sweep, shaped like its cube (float64)."""
         out = np.empty(shape, dtype=np.float64)
         self._chk(self._lib.coreg_pixels_last_counts(self._h, out.ctypes.data))
+        return out
+
+    def pixels_last_tile_counts(self, shape):
+        """The same of the last tiled sweep, shaped like its cubes [n_ty, n_tx, n_dx, n_dy, n_rot]."""
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self._lib.coreg_pixels_last_tile_counts(self._h, out.ctypes.data))
         return out
 
     def pixels_get_large_box(self, shape):

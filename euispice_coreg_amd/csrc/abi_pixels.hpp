@@ -33,6 +33,17 @@ int coreg_pixels_last_counts(coreg_handle* h, double* dst) {
     return pixels_last_counts(h, dst);
 }
 
+int coreg_pixels_sweep_tiles(coreg_handle* h, const coreg_pixels_plan* plan, int method, int32_t tile_ny, int32_t tile_nx,
+                             double* out) {
+    if (!h) return COREG_EINVAL;
+    return pixels_sweep_tiles(h, plan, method, tile_ny, tile_nx, out);
+}
+
+int coreg_pixels_last_tile_counts(coreg_handle* h, double* dst) {
+    if (!h) return COREG_EINVAL;
+    return pixels_last_tile_counts(h, dst);
+}
+
 int coreg_pixels_get_large_box(coreg_handle* h, double* out) {
     if (!h) return COREG_EINVAL;
     return pixels_get_large_box(h, out);

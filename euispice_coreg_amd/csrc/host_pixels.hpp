@@ -7,7 +7,8 @@ struct PixelsState {
     DevBuf large, large_tmp, small, box, planes, sums, plan, corr, counts;
     int lW = 0, lH = 0, sW = 0, sH = 0;
     int bW = 0, bH = 0, n_rot = 0;  // what the last sweep left in `box` / `planes`
-    long long n_counts = 0;         // ... and in `counts`: lags of the last sweep, 0 once an image has changed
+    long long n_counts = 0;         // ... and in `counts`: lags of the last untiled sweep, 0 once an image has changed
+    long long n_tile_counts = 0;    //     or a tiled sweep has run; tiles x lags of the last tiled sweep, likewise
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
 };
@@ -82,7 +83,7 @@ int pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->bW = st->bH = 0;  // (the box of the last sweep is no longer this image's)
-    st->n_counts = 0;
+    st->n_counts = st->n_tile_counts = 0;
     return pixels_upload(h, st->large, img, dtype, ny, nx, &st->lW, &st->lH);
 }
 
@@ -90,7 +91,7 @@ int pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->n_rot = 0;
-    st->n_counts = 0;
+    st->n_counts = st->n_tile_counts = 0;
     return pixels_upload(h, st->small, img, dtype, ny, nx, &st->sW, &st->sH);
 }
 
@@ -101,7 +102,7 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     if (!(dx == dx) || !(dy == dy)) return fail(h, COREG_EINVAL, "pixels: the displacement is not a number");
     RETCHK(bind_device(h));
     st->bW = st->bH = 0;
-    st->n_counts = 0;
+    st->n_counts = st->n_tile_counts = 0;
     const size_t n = (size_t)st->lW * st->lH;
     HIPCHK(st->large_tmp.reserve(n * sizeof(double)));
     PixResample a = {};
@@ -119,7 +120,17 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     return pixels_resample(h, PIX_AFFINE, a);
 }
 
-int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, double* corr_out) {
+template <int PASS>
+static void pixels_launch_pass(coreg_handle* h, const dim3& grid, const PixSweep& s, const PixTiles* t) {
+    if (t)
+        hipLaunchKernelGGL(k_pixels_sweep_tiles<PASS>, grid, dim3(kPixThreads), 0, h->stream, s, *t);
+    else
+        hipLaunchKernelGGL(k_pixels_sweep<PASS>, grid, dim3(kPixThreads), 0, h->stream, s);
+}
+
+// The untiled sweep (tile == nullptr: one cube [n_dx][n_dy][n_rot]) and the tiled one (tile = {rows, columns} of a tile:
+// one such cube per tile, [n_ty][n_tx] of them): the same validation, box, rotation planes, groups and events.
+static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int method, const int32_t* tile, double* corr_out) {
     if (method == COREG_METHOD_RESIDUS)
         return fail(h, COREG_ENOTIMPL, "pixels: method residus is not implemented (the reference's pxlshift has no such score); "
                                        "residus_masked is");
@@ -136,6 +147,21 @@ int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, doubl
     const int w = st->sW, hh = st->sH;
     const long long n_lag = (long long)pl->n_dx * pl->n_dy * pl->n_rot;
     if (n_lag > (1ll << 28)) return fail(h, COREG_EINVAL, "pixels: too many lags");
+    PixTiles tl = {};
+    long long n_tiles = 1;
+    if (tile) {
+        if (tile[0] < 1 || tile[0] > hh || tile[1] < 1 || tile[1] > w)
+            return fail(h, COREG_EINVAL, "pixels: the tile shape must lie within [1, h] x [1, w] of the small image");
+        tl.th = tile[0];
+        tl.tw = tile[1];
+        tl.n_tx = (w + tl.tw - 1) / tl.tw;
+        n_tiles = (long long)((hh + tl.th - 1) / tl.th) * tl.n_tx;
+        if (n_tiles * pl->n_rot > 65535) return fail(h, COREG_EINVAL, "pixels: more than 65535 rotation planes x tiles");
+        if (n_tiles * n_lag > (1ll << 28)) return fail(h, COREG_EINVAL, "pixels: too many tiles x lags");
+        tl.n_tiles = (int)n_tiles;
+        tl.n_rot = pl->n_rot;
+    }
+    const long long n_out = n_tiles * n_lag;
     int min_dx = pl->lag_dx[0], max_dx = min_dx, min_dy = pl->lag_dy[0], max_dy = min_dy;
     for (int i = 0; i < pl->n_dx; ++i) {
         min_dx = std::min(min_dx, pl->lag_dx[i]);
@@ -179,10 +205,10 @@ int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, doubl
     HIPCHK(st->plan.reserve(blob.size()));
     HIPCHK(st->box.reserve((size_t)bW * bH * sizeof(double)));
     HIPCHK(st->planes.reserve((size_t)w * hh * pl->n_rot * sizeof(double)));
-    HIPCHK(st->sums.reserve((size_t)n_lag * 6 * sizeof(double)));
-    HIPCHK(st->corr.reserve((size_t)n_lag * sizeof(double)));
-    HIPCHK(st->counts.reserve((size_t)n_lag * sizeof(double)));
-    st->n_counts = 0;
+    HIPCHK(st->sums.reserve((size_t)n_out * 6 * sizeof(double)));
+    HIPCHK(st->corr.reserve((size_t)n_out * sizeof(double)));
+    HIPCHK(st->counts.reserve((size_t)n_out * sizeof(double)));
+    st->n_counts = st->n_tile_counts = 0;
     for (hipEvent_t& e : st->ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     st->timed = false;
@@ -241,36 +267,49 @@ int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, doubl
     s.n_dy = pl->n_dy;
     s.min_dx = min_dx;
     s.min_dy = min_dy;
-    s.cw = std::min(w, kPixTile);
-    s.bh = std::max(1, std::min(std::min(kPixBandRows, kPixTile / s.cw), hh));
+    // the band of the whole image, or of the nominal tile: one value for the launch
+    const int band_w = tile ? tl.tw : w, band_h = tile ? tl.th : hh;
+    s.cw = std::min(band_w, kPixTile);
+    s.bh = std::max(1, std::min(std::min(kPixBandRows, kPixTile / s.cw), band_h));
     double* sums0 = st->sums.as<double>();
-    double* sums1 = sums0 + 3 * n_lag;
-    const dim3 grid((unsigned)n_groups, (unsigned)pl->n_dy, (unsigned)pl->n_rot);
+    double* sums1 = sums0 + 3 * n_out;
+    const PixTiles* t = tile ? &tl : nullptr;
+    const dim3 grid((unsigned)n_groups, (unsigned)pl->n_dy, (unsigned)(pl->n_rot * n_tiles));
     s.sums0 = nullptr;
     s.sums = sums0;
     if (resid)
-        hipLaunchKernelGGL(k_pixels_sweep<kPixR0>, grid, dim3(kPixThreads), 0, h->stream, s);
+        pixels_launch_pass<kPixR0>(h, grid, s, t);
     else
-        hipLaunchKernelGGL(k_pixels_sweep<0>, grid, dim3(kPixThreads), 0, h->stream, s);
+        pixels_launch_pass<0>(h, grid, s, t);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[2], h->stream));
     s.sums0 = sums0;
     s.sums = sums1;
     if (resid)
-        hipLaunchKernelGGL(k_pixels_sweep<kPixR1>, grid, dim3(kPixThreads), 0, h->stream, s);
+        pixels_launch_pass<kPixR1>(h, grid, s, t);
     else
-        hipLaunchKernelGGL(k_pixels_sweep<1>, grid, dim3(kPixThreads), 0, h->stream, s);
+        pixels_launch_pass<1>(h, grid, s, t);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[3], h->stream));
-    hipLaunchKernelGGL(k_pixels_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads)), dim3(kPixThreads), 0,
-                       h->stream, (const double*)sums0, (const double*)sums1, pl->n_dx, pl->n_dy, pl->n_rot, (int)resid,
-                       st->corr.as<double>(), st->counts.as<double>());
+    hipLaunchKernelGGL(k_pixels_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads), (unsigned)n_tiles),
+                       dim3(kPixThreads), 0, h->stream, (const double*)sums0, (const double*)sums1, pl->n_dx, pl->n_dy, pl->n_rot,
+                       (int)resid, st->corr.as<double>(), st->counts.as<double>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_lag * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     st->timed = true;
-    st->n_counts = n_lag;
+    (tile ? st->n_tile_counts : st->n_counts) = n_out;
     return COREG_OK;
+}
+
+int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, double* corr_out) {
+    return pixels_sweep_run(h, pl, method, nullptr, corr_out);
+}
+
+// out[n_ty][n_tx][n_dx][n_dy][n_rot]: the cube of every tile of tile_ny x tile_nx small-image pixels (the last ones ragged)
+int pixels_sweep_tiles(coreg_handle* h, const coreg_pixels_plan* pl, int method, int32_t tile_ny, int32_t tile_nx, double* out) {
+    const int32_t tile[2] = {tile_ny, tile_nx};
+    return pixels_sweep_run(h, pl, method, tile, out);
 }
 
 int pixels_last_timing(coreg_handle* h, double* ms) {
@@ -311,6 +350,13 @@ int pixels_get_rotated(coreg_handle* h, int32_t k, double* out) {
 // per-lag sample counts of the last sweep, laid out like its cube
 int pixels_last_counts(coreg_handle* h, double* out) {
     PixelsState* st = pixels_state(h, false);
-    if (!st || st->n_counts < 1) return fail(h, COREG_ESTATE, "pixels: no sweep has run");
+    if (!st || st->n_counts < 1) return fail(h, COREG_ESTATE, "pixels: no untiled sweep has run since the images were set");
     return pixels_read(h, st->counts.p, (size_t)st->n_counts, out);
+}
+
+// the same of the last tiled sweep: [n_ty][n_tx][n_dx][n_dy][n_rot]
+int pixels_last_tile_counts(coreg_handle* h, double* out) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || st->n_tile_counts < 1) return fail(h, COREG_ESTATE, "pixels: no tiled sweep has run since the images were set");
+    return pixels_read(h, st->counts.p, (size_t)st->n_tile_counts, out);
 }

@@ -12,6 +12,9 @@
 //                             band's sqrt(b) is taken once per staged box pixel, in a second LDS plane these two passes
 //                             alone declare.  No atomics, no accumulation across workgroups: the sums of a lag depend
 //                             on the lag alone, not on the group it runs in
+//   k_pixels_sweep_tiles<PASS> the same four passes per tile of the small-image plane (the local shift field): one
+//                             workgroup per (group, dy, rotation plane x tile) walks the tile's rectangle alone; the body
+//                             is the one text of csrc/kernels_pixels_sweep_body.hpp, included in either kernel
 //   k_pixels_finalize         correlation: float32-rounded numerator / sqrt(product of the centred squares), NaN for an
 //                             empty or flat overlap; residus_masked: sqrt(sum of squares / n), NaN for no finite term
 //                             or a poisoned one; either way the lag's sample count
@@ -105,127 +108,30 @@ struct PixSweep {
     int cw, bh;            // band: columns [c0, c0 + cw) x rows [r0, r0 + bh), cw * bh <= kPixTile, bh <= kPixBandRows
 };
 
+// The tile grid of k_pixels_sweep_tiles: tile (ty, tx) is rows [ty th, min(h, (ty + 1) th)) x columns [tx tw, min(w, (tx + 1) tw))
+// of every plane (a rotated plane is rotated about the whole image's centre; a tile is a rectangle of it)
+struct PixTiles {
+    int th, tw, n_tx, n_tiles, n_rot;
+};
+
 template <int PASS>
 __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
-    __shared__ double lds_a[kPixTile];
-    constexpr bool RESID = PASS >= kPixR0;
-    __shared__ double lds_b[(RESID ? 2 : 1) * kPixLdsB];  // residus passes: the roots of the box pixels behind them
-    __shared__ double lds_red[kPixThreads / 64][3 * kPixG];
-    const int tid = threadIdx.x;
-    const PixGroup g = p.groups[blockIdx.x];
-    const int jy = blockIdx.y, kr = blockIdx.z;
-    const int row_off = p.lag_dy[jy] - p.min_dy;  // box row of the window's first row
-    const int col_off = g.dx_min - p.min_dx;      // box column of the group's first window's first column
-    const long long lag0 = ((long long)kr * p.n_dy + jy) * p.n_dx + g.first;
-    const double* plane = p.planes + (size_t)kr * p.w * p.h;
-
-    int off[kPixG];
-    double ma[kPixG], mb[kPixG];
-#pragma unroll
-    for (int s = 0; s < kPixG; ++s) {
-        const bool used = s < g.count;
-        off[s] = used ? p.lag_dx[g.first + s] - g.dx_min : 0;
-        ma[s] = mb[s] = 0.0;
-        if (PASS == 1 && used) {
-            const double* s0 = p.sums0 + 3 * (lag0 + s);
-            ma[s] = s0[1] / s0[0];
-            mb[s] = s0[2] / s0[0];
-        }
-        if (PASS == kPixR1 && used) {
-            const double* s0 = p.sums0 + 3 * (lag0 + s);
-            ma[s] = s0[1] / s0[0];  // mean of the finite terms
-        }
-    }
-    double acc0[kPixG], acc1[kPixG], acc2[kPixG];
-#pragma unroll
-    for (int s = 0; s < kPixG; ++s) acc0[s] = acc1[s] = acc2[s] = 0.0;
-
-    for (int r0 = 0; r0 < p.h; r0 += p.bh) {
-        const int nr = min(p.bh, p.h - r0);
-        for (int c0 = 0; c0 < p.w; c0 += p.cw) {
-            const int nc = min(p.cw, p.w - c0);
-            const int ncb = nc + kPixG - 1;
-            __syncthreads();  // the previous band has been read
-            for (int q = tid; q < nr * nc; q += kPixThreads) {
-                const int r = q / nc, c = q - r * nc;
-                lds_a[q] = plane[(size_t)(r0 + r) * p.w + c0 + c];
-            }
-            for (int q = tid; q < nr * ncb; q += kPixThreads) {
-                const int r = q / ncb, c = q - r * ncb;
-                const int bc = col_off + c0 + c;  // (columns past the box belong to unused slots only)
-                if (!RESID) {
-                    lds_b[q] = bc < p.bW ? p.box[(size_t)(row_off + r0 + r) * p.bW + bc] : 0.0;
-                } else {
-                    // a pixel that is not finite, and a column past the box, is staged as NaN: never kept, never poisoned
-                    double b = bc < p.bW ? p.box[(size_t)(row_off + r0 + r) * p.bW + bc] : __builtin_nan("");
-                    if (!(fabs(b) < __builtin_inf())) b = __builtin_nan("");
-                    lds_b[q] = b;
-                    lds_b[kPixLdsB + q] = sqrt(b);
-                }
-            }
-            __syncthreads();
-            for (int q = tid; q < nr * nc; q += kPixThreads) {
-                const int r = q / nc, c = q - r * nc;
-                const double a = lds_a[q];
-                const double* brow = lds_b + r * ncb + c;
-                const bool a_ok = RESID ? fabs(a) < __builtin_inf() : a == a;
-#pragma unroll
-                for (int s = 0; s < kPixG; ++s) {
-                    const double b = brow[off[s]];
-                    const bool keep = a_ok & (b == b);
-                    if (PASS == 0) {
-                        acc0[s] += keep ? 1.0 : 0.0;
-                        acc1[s] += keep ? a : 0.0;
-                        acc2[s] += keep ? b : 0.0;
-                    } else if (PASS == 1) {
-                        const double da = a - ma[s], db = b - mb[s];
-                        acc0[s] += keep ? da * db : 0.0;
-                        acc1[s] += keep ? da * da : 0.0;
-                        acc2[s] += keep ? db * db : 0.0;
-                    } else {
-                        // IEEE division by the staged root; a kept term is finite unless b <= 0
-                        const double d = (b - a) / brow[kPixLdsB + off[s]];
-                        const bool fin = keep & (fabs(d) < __builtin_inf());
-                        if (PASS == kPixR0) {
-                            acc0[s] += fin ? 1.0 : 0.0;
-                            acc1[s] += fin ? d : 0.0;
-                            acc2[s] += (keep & !fin) ? 1.0 : 0.0;
-                        } else {
-                            const double dd = d - ma[s];
-                            acc0[s] += fin ? dd * dd : 0.0;
-                        }
-                    }
-                }
-            }
-        }
-    }
-    // lanes of a wave, then the four waves in a fixed order
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int s = 0; s < kPixG; ++s) {
-        double v0 = acc0[s], v1 = acc1[s], v2 = acc2[s];
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) {
-            v0 += __shfl_down(v0, d, 64);
-            v1 += __shfl_down(v1, d, 64);
-            v2 += __shfl_down(v2, d, 64);
-        }
-        if (lane == 0) {
-            lds_red[wave][3 * s + 0] = v0;
-            lds_red[wave][3 * s + 1] = v1;
-            lds_red[wave][3 * s + 2] = v2;
-        }
-    }
-    __syncthreads();
-    if (tid < 3 * g.count) {
-        double v = lds_red[0][tid];
-#pragma unroll
-        for (int k = 1; k < kPixThreads / 64; ++k) v += lds_red[k][tid];
-        p.sums[3 * lag0 + tid] = v;
-    }
+    constexpr bool TILED = false;
+    const PixTiles t = {0, 0, 1, 1, 0};  // (never read: every use sits behind TILED)
+#include "kernels_pixels_sweep_body.hpp"
 }
 
-// corr[(i * n_dy + j) * n_rot + k] and counts[...] from the sums of lag (k, j, i); resid: the residus_masked score
+// The same walk per tile: one workgroup per (group of dx lags, dy, rotation plane x tile), blockIdx.z = kr * n_tiles + tile.
+// Sums [n_tiles][n_rot][n_dy][n_dx][3]; pass 1 / R1 centre about the tile's own means of pass 0 / R0.  The band (p.cw, p.bh)
+// is that of the nominal tile shape, one value for the launch; a tile's sums depend on the tile and the lag alone.
+template <int PASS>
+__global__ __launch_bounds__(kPixThreads) void k_pixels_sweep_tiles(PixSweep p, PixTiles t) {
+    constexpr bool TILED = true;
+#include "kernels_pixels_sweep_body.hpp"
+}
+
+// corr[(i * n_dy + j) * n_rot + k] and counts[...] from the sums of lag (k, j, i); resid: the residus_masked score.
+// gridDim.y tiles, each with sums and a cube of its own one after the other (1: the untiled sweep)
 __global__ __launch_bounds__(kPixThreads) void k_pixels_finalize(const double* __restrict__ sums0, const double* __restrict__ sums1,
                                                                   int n_dx, int n_dy, int n_rot, int resid,
                                                                   double* __restrict__ corr, double* __restrict__ counts) {
@@ -233,6 +139,11 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_finalize(const double* _
     const long long q = (long long)blockIdx.x * kPixThreads + threadIdx.x;
     if (q >= n) return;
     const int i = (int)(q % n_dx), j = (int)((q / n_dx) % n_dy), k = (int)(q / ((long long)n_dx * n_dy));
+    const long long tile0 = (long long)blockIdx.y * n;  // (a tiled sweep: one cube per tile, blockIdx.y the tile)
+    sums0 += 3 * tile0;
+    sums1 += 3 * tile0;
+    corr += tile0;
+    counts += tile0;
     const double cnt = sums0[3 * q];
     double r = __builtin_nan("");
     if (!resid) {

@@ -11,6 +11,10 @@ Beyond the reference (the defaults return what it returns): `method="residus_mas
 behind every entry of the last cube; `min_overlap`, entries of fewer samples set to NaN (hdrshift.alignment
 .apply_min_overlap); `return_type="PixelAlignmentResults"` (pixel_alignment_results.py).
 
+`find_local_shifts` (not in the reference either): the small image cut into tiles, one lag cube, count cube, best entry
+and sub-lag fit per tile (include/coreg_hip.h: coreg_pixels_sweep_tiles; local_shift_field.py) -- the drift across a
+raster whose columns were not taken at one pointing.
+
 Differences from the reference, all deliberate:
   * a second `find_best_parameters` call starts from the file's pixels again (the reference sub-resolves the already
     sub-resolved image);
@@ -27,6 +31,22 @@ from ..hdrshift.alignment import apply_min_overlap, library_method, min_overlap_
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
 
 _RETURN_TYPES = ("corr", "PixelAlignmentResults")
+
+
+def tile_grid(image_shape, tile_shape):
+    """(th, tw), (n_ty, n_tx) of the tiles of `tile_shape` = (rows, columns) on an image of `image_shape`: whole numbers,
+    1 <= th <= h, 1 <= tw <= w; the last tile of an axis is ragged when the shape does not divide it."""
+    try:
+        th, tw = tile_shape
+    except (TypeError, ValueError):
+        raise ValueError("tile_shape must be (rows, columns)") from None
+    for v in (th, tw):
+        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
+            raise ValueError("tile_shape must hold two integers")
+    h, w = image_shape
+    if not (1 <= th <= h and 1 <= tw <= w):
+        raise ValueError(f"tile_shape {(int(th), int(tw))} must lie within [1, {h}] x [1, {w}], the small image")
+    return (int(th), int(tw)), (-(-h // int(th)), -(-w // int(tw)))
 
 
 def _integer_lags(v, name):
@@ -87,8 +107,9 @@ class AlignmentPixels:
         return float(d1 / hl["CDELT1"]), 0.0
 
     def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
-                  method="correlation", min_overlap=None) -> dict:
-        """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU)."""
+                  method="correlation", min_overlap=None, tile_shape=None) -> dict:
+        """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU); with
+        `tile_shape` = (rows, columns), of a `find_local_shifts` call: the plan then holds the tile grid too."""
         method_code = library_method(method)
         if method_code == _lib.METHOD_RESIDUS:
             raise NotImplementedError("pxlshift has no unmasked 'residus' (the reference's pxlshift has no such score): "
@@ -120,7 +141,9 @@ class AlignmentPixels:
         plan = {"lag_dx": dx, "lag_dy": dy, "lag_drot": drot, "lag_drot_rad": drot_rad, "unit_rot": unit_rot,
                 "ratio_res_1": float(ratio1), "ratio_res_2": float(ratio2), "sub_shape": sub, "slc_small_ref": tuple(l),
                 "xc": round(w / 2), "yc": round(h / 2), "shift_large": None, "method": method,
-                "method_code": method_code, "min_overlap": min_overlap}
+                "method_code": method_code, "min_overlap": min_overlap, "small_shape": (h, w)}
+        if tile_shape is not None:
+            plan["tile_shape"], plan["tile_grid"] = tile_grid((h, w), tile_shape)
         if shift_solar_rotation_dx_large:
             plan["shift_large"] = self._shift_large_fov_displacement()
         return plan
@@ -159,6 +182,33 @@ class AlignmentPixels:
                                      method=method, n_samples=self.last_counts,
                                      large_fov_path=self.large_fov_known_pointing, large_fov_window=self.window_large,
                                      small_fov_path=self.small_fov_to_correct)
+
+    def find_local_shifts(self, lag_dx, lag_dy, lag_drot=(0.0,), tile_shape=None, unit_rot="degree",
+                          shift_solar_rotation_dx_large=False, method="correlation", min_overlap=None, min_fill=0.5,
+                          sub_lag=True):
+        """The local shift field: the small image is cut into tiles of `tile_shape` = (rows, columns) pixels (the last
+        ones ragged) and every tile gets the lag cube of `find_best_parameters` on its own rectangle -- a rotated plane
+        is still rotated about the whole image's centre -- with its sample counts, best entry and sub-lag fit.  Returns a
+        `LocalShiftField` (local_shift_field.py), which takes `min_overlap` (per tile), `min_fill` and `sub_lag`."""
+        if tile_shape is None:
+            raise ValueError("tile_shape = (rows, columns) is needed")
+        plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
+                              tile_shape=tile_shape)
+        hnd = _lib.shared_handle(-1 if self.device is None else self.device)
+        hnd.pixels_set_large(self.data_large)
+        hnd.pixels_set_small(self.data_small)
+        if plan["shift_large"] is not None:
+            dx, dy = plan["shift_large"]
+            hnd.pixels_shift_large(dx, dy)
+            print(f"corrected solar rotation on FSI on CRVAL1: {dx=}, {dy=}")
+        corr = hnd.pixels_sweep_tiles(plan, plan["method_code"])
+        self.last_timing = hnd.pixels_last_timing()
+        counts = hnd.pixels_last_tile_counts(corr.shape)
+        self._last_plan = plan
+        from .local_shift_field import LocalShiftField
+        return LocalShiftField(corr, counts, plan["lag_dx"], plan["lag_dy"], plan["lag_drot"], plan["tile_shape"],
+                               self.data_small.shape, unit_rot=unit_rot, method=method, min_overlap=min_overlap,
+                               min_fill=min_fill, sub_lag=sub_lag)
 
     # read-backs of the last call's device images (tests, inspection)
     def _large_box(self):

@@ -1,0 +1,122 @@
+"""
+`LocalShiftField` -- what `AlignmentPixels.find_local_shifts` returns: the small image cut into tiles, and per tile the
+cube of the integer pixel-lag sweep on the tile's own rectangle (`corr[n_ty, n_tx, n_dx, n_dy, n_rot]`), the sample
+count behind every entry (`n_samples`, taken before `min_overlap`), the best entry (maximum of a correlation, minimum of
+`residus_masked`) and its sub-lag position -- the one Gaussian fit `PixelAlignmentResults` runs
+(`hdrshift.alignment_results.gaussian_sub_lag`), on the tile's (dx, dy) plane at its best rotation, the best entry
+itself where the fit cannot run or fails.
+
+A tile is `valid` when its largest count reaches `min_fill` times its pixel count and a finite entry is left after
+`min_overlap` (a count, or a fraction of that tile's own largest count: `hdrshift.alignment.apply_min_overlap` per
+tile).  An invalid tile raises nothing: its shifts, score and rotation are NaN and its `best_index` is -1.  Only a field
+without any valid tile raises ValueError.
+
+From the valid tiles: `median_shift` and `scatter` (1.4826 x the median absolute deviation) of dx and dy -- an empirical
+error bar on a global shift -- and `drift()`, the least-squares planes of dx and dy over the tile centres: the drift
+across a raster.  There is no FITS card for a tile-dependent correction; nothing is written.
+"""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+
+from ..hdrshift.alignment import apply_min_overlap, min_overlap_floor
+from ..hdrshift.alignment_results import gaussian_sub_lag
+from .alignment_pixels import tile_grid
+from .pixel_alignment_results import _BEST
+
+
+class LocalShiftField:
+
+    def __init__(self, corr, n_samples, lag_dx, lag_dy, lag_drot, tile_shape, image_shape, unit_rot="degree",
+                 method="correlation", min_overlap=None, min_fill=0.5, sub_lag=True, fit=None):
+        if method not in _BEST:
+            raise NotImplementedError
+        fit = fit or os.environ.get("COREG_GAUSSIAN_FIT", "native")
+        if fit not in ("native", "scipy"):
+            raise ValueError("fit must be 'native' or 'scipy'")
+        if min_overlap is not None:
+            min_overlap_floor(min_overlap)  # (a value that is neither a count nor a fraction raises here, not per tile)
+        if not 0.0 <= min_fill <= 1.0:
+            raise ValueError("min_fill must lie in [0, 1]")
+        self.fit, self.method, self.best, self.unit_rot = fit, method, _BEST[method], unit_rot
+        self.min_overlap, self.min_fill, self.sub_lag = min_overlap, float(min_fill), bool(sub_lag)
+        self.lag_dx, self.lag_dy, self.lag_drot = (np.atleast_1d(np.asarray(v)) for v in (lag_dx, lag_dy, lag_drot))
+        self.image_shape = (int(image_shape[0]), int(image_shape[1]))
+        self.tile_shape, grid = tile_grid(self.image_shape, tile_shape)
+        corr, n_samples = np.asarray(corr, dtype=np.float64), np.asarray(n_samples, dtype=np.float64)
+        if corr.shape != grid + (len(self.lag_dx), len(self.lag_dy), len(self.lag_drot)) or n_samples.shape != corr.shape:
+            raise ValueError("corr and n_samples must be shaped [n_ty, n_tx, len(lag_dx), len(lag_dy), len(lag_drot)]")
+        self.n_samples = n_samples
+        self.corr = np.full(corr.shape, np.nan)  # (after min_overlap; an emptied tile is all NaN)
+        (h, w), (th, tw) = self.image_shape, self.tile_shape
+        self.tile_slices = [[(slice(ty * th, min(h, (ty + 1) * th)), slice(tx * tw, min(w, (tx + 1) * tw)))
+                             for tx in range(grid[1])] for ty in range(grid[0])]
+        # (x, y) of every tile's centre in small-image pixels
+        self.tile_centres = np.array([[((c.start + c.stop - 1) / 2, (r.start + r.stop - 1) / 2) for r, c in row]
+                                      for row in self.tile_slices], dtype=np.float64)
+        self.valid = np.zeros(grid, dtype=bool)
+        self.fitted = np.zeros(grid, dtype=bool)
+        self.best_index = np.full(grid + (3,), -1, dtype=np.int64)
+        self.best_score, self.shift_dx, self.shift_dy, self.drot = (np.full(grid, np.nan) for _ in range(4))
+        for ty in range(grid[0]):
+            for tx in range(grid[1]):
+                self._tile(ty, tx, corr[ty, tx])
+        if not self.valid.any():
+            raise ValueError("no valid tile: none holds min_fill of its pixels at any lag with a finite entry left")
+
+    def _tile(self, ty, tx, cube):
+        counts = self.n_samples[ty, tx]
+        try:
+            cube = apply_min_overlap(cube, counts, self.min_overlap)
+        except ValueError:  # (the floor leaves no entry of this tile)
+            return
+        self.corr[ty, tx] = cube
+        r, c = self.tile_slices[ty][tx]
+        n_pix = (r.stop - r.start) * (c.stop - c.start)
+        if not (np.isfinite(cube).any() and np.nanmax(counts) >= self.min_fill * n_pix):
+            return
+        mi = np.unravel_index((np.nanargmin if self.best == "min" else np.nanargmax)(cube), cube.shape)
+        pos = None
+        if self.sub_lag:
+            pos, _ = gaussian_sub_lag(cube[:, :, mi[2]], (mi[0], mi[1]), self.best, self.fit)
+        x, y = (mi[0], mi[1]) if pos is None else (pos[0], pos[1])
+        self.valid[ty, tx] = True
+        self.fitted[ty, tx] = pos is not None
+        self.best_index[ty, tx] = mi
+        self.best_score[ty, tx] = cube[mi]
+        self.shift_dx[ty, tx] = np.interp(x, np.arange(len(self.lag_dx)), self.lag_dx)
+        self.shift_dy[ty, tx] = np.interp(y, np.arange(len(self.lag_dy)), self.lag_dy)
+        self.drot[ty, tx] = self.lag_drot[mi[2]]
+
+    @property
+    def median_shift(self):
+        """(dx, dy): the medians over the valid tiles."""
+        return float(np.median(self.shift_dx[self.valid])), float(np.median(self.shift_dy[self.valid]))
+
+    @property
+    def scatter(self):
+        """(dx, dy): 1.4826 x the median absolute deviation over the valid tiles (sigma of a normal scatter)."""
+        return tuple(float(1.4826 * np.median(np.abs(v[self.valid] - np.median(v[self.valid]))))
+                     for v in (self.shift_dx, self.shift_dy))
+
+    def drift(self):
+        """[[a0, a1, a2], [b0, b1, b2]]: the least-squares planes dx = a0 + a1 xc + a2 yc, dy = b0 + b1 xc + b2 yc over
+        the centres (xc, yc) of the valid tiles.  ValueError with fewer than three valid tiles or collinear centres."""
+        xy = self.tile_centres[self.valid]
+        if len(xy) < 3:
+            raise ValueError("drift needs at least three valid tiles")
+        M = np.column_stack([np.ones(len(xy)), xy[:, 0], xy[:, 1]])
+        if np.linalg.matrix_rank(M) < 3:
+            raise ValueError("drift needs tile centres that are not collinear")
+        sol = np.linalg.lstsq(M, np.column_stack([self.shift_dx[self.valid], self.shift_dy[self.valid]]), rcond=None)[0]
+        return sol.T.copy()
+
+    def __str__(self):
+        (mx, my), (sx, sy) = self.median_shift, self.scatter
+        return (f"\n Local shifts : {int(self.valid.sum())} valid of {self.valid.size} tiles of {self.tile_shape[0]} x "
+                f"{self.tile_shape[1]} pixels \n dx = {mx} +- {sx} pixels \n dy = {my} +- {sy} pixels "
+                f"\n ({self.method}, best = {self.best})")
+
+    __repr__ = __str__

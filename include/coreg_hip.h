@@ -563,6 +563,19 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  *                                        sweep: the kept pixels for the correlation, the finite terms for residus_masked.
  *                                        COREG_ESTATE before a sweep and once coreg_pixels_set_large / _set_small /
  *                                        _shift_large has changed an image
+ *   coreg_pixels_sweep_tiles             the local shift field: the small image is cut into tiles of tile_ny x tile_nx pixels
+ *                                        (1 <= tile_ny <= h, 1 <= tile_nx <= w; n_ty = ceil(h / tile_ny), n_tx likewise, the
+ *                                        last tiles ragged) and every tile gets the cube of coreg_pixels_sweep_method on its
+ *                                        own rectangle of window and plane -- a rotated plane is still rotated about the whole
+ *                                        image's centre: out[n_ty][n_tx][n_dx][n_dy][n_rot], C order, the means and the
+ *                                        scores those of the tile's own kept pixels.  A tile of the whole image gives the
+ *                                        bits of the untiled call.  method and plan as coreg_pixels_sweep_method;
+ *                                        COREG_EINVAL also for a tile shape outside the image, n_rot * n_tiles > 65535 or
+ *                                        n_tiles * n_dx * n_dy * n_rot > 2^28
+ *   coreg_pixels_last_tile_counts        dst[n_ty][n_tx][n_dx][n_dy][n_rot], the samples behind every entry of the last tiled
+ *                                        sweep (over a lag they sum to the untiled count).  The two count calls answer for the
+ *                                        last sweep only: COREG_ESTATE from this one after an untiled sweep or a changed
+ *                                        image, from coreg_pixels_last_counts after a tiled sweep
  *   coreg_pixels_get_large_box           the part of the sub-resolved image the last sweep could read:
  *                                        [h + max dy - min dy][w + max dx - min dx] from (l0 + min dy, l1 + min dx) on
  *   coreg_pixels_get_rotated             plane k [h][w] of the last sweep
@@ -585,6 +598,9 @@ int coreg_pixels_shift_large(coreg_handle* h, double dx, double dy);
 int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* corr_out);
 int coreg_pixels_sweep_method(coreg_handle* h, const coreg_pixels_plan* plan, int method, double* out);
 int coreg_pixels_last_counts(coreg_handle* h, double* dst);
+int coreg_pixels_sweep_tiles(coreg_handle* h, const coreg_pixels_plan* plan, int method, int32_t tile_ny, int32_t tile_nx,
+                             double* out);
+int coreg_pixels_last_tile_counts(coreg_handle* h, double* dst);
 int coreg_pixels_get_large_box(coreg_handle* h, double* out);
 int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out);
 int coreg_pixels_last_timing(coreg_handle* h, double* ms);
