@@ -86,6 +86,14 @@ class PixelsPlan(C.Structure):
                 ("l0", C.c_int32), ("l1", C.c_int32), ("xc", C.c_int32), ("yc", C.c_int32)]
 
 
+class PixelsField(C.Structure):
+    """coreg_pixels_field (include/coreg_hip.h)."""
+    _fields_ = [("n_ty", C.c_int32), ("n_tx", C.c_int32), ("tile_ny", C.c_int32), ("tile_nx", C.c_int32),
+                ("interpolation", C.c_int32), ("ys", C.POINTER(C.c_double)), ("xs", C.POINTER(C.c_double)),
+                ("u", C.POINTER(C.c_double)), ("v", C.POINTER(C.c_double)), ("row_offset", C.c_double),
+                ("col_offset", C.c_double)]
+
+
 def _is_tiled(img):
     """utils.fits_io.CompressedImage that the GPU can decode as it is (duck-typed)."""
     return hasattr(img, "tile_nbytes") and hasattr(img, "ztile") and getattr(img, "on_gpu", False)
@@ -298,6 +306,9 @@ SYMBOLS = [
     ("coreg_pixels_get_large_box", C.c_int, [_P, _P]),
     ("coreg_pixels_get_rotated", C.c_int, [_P, C.c_int32, _P]),
     ("coreg_pixels_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
+    ("coreg_pixels_destretch", C.c_int,
+     [_P, _P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PixelsField), _P, _P]),
+    ("coreg_pixels_destretch_last_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     # all GPUs of the node from one process
     ("coreg_device_count", C.c_int, []),
     ("coreg_physical_device_count", C.c_int, []),
@@ -787,6 +798,31 @@ class CoregHandle(_ImageIntake):
         ms = (C.c_double * 3)()
         self._chk(self._lib.coreg_pixels_last_timing(self._h, ms))
         return {"prepare_ms": ms[0], "pass0_ms": ms[1], "pass1_ms": ms[2]}
+
+    def pixels_destretch(self, cube, ys, xs, u, v, tile_shape, interpolation=0, row_offset=0.0, col_offset=0.0,
+                         return_displacement=False):
+        """coreg_pixels_destretch: `cube` [n_planes, ny, nx] float32 / float64 resampled by the field of nodes `u`, `v`
+        [n_ty, n_tx] at the centres `ys`, `xs`; the result in the type and shape of `cube`, with the displacement
+        [2, ny, nx] (u, v) when asked for."""
+        cube = np.ascontiguousarray(cube)
+        if cube.ndim != 3 or cube.dtype not in (np.float32, np.float64):
+            raise ValueError("destretch takes a 3-D float32/float64 array [n_planes, ny, nx]")
+        ys, xs, u, v = (np.ascontiguousarray(a, dtype=np.float64) for a in (ys, xs, u, v))
+        if ys.ndim != 1 or xs.ndim != 1 or u.shape != (len(ys), len(xs)) or v.shape != u.shape:
+            raise ValueError("the field needs ys [n_ty], xs [n_tx] and u, v [n_ty, n_tx]")
+        f = PixelsField(len(ys), len(xs), int(tile_shape[0]), int(tile_shape[1]), int(interpolation), _dptr(ys), _dptr(xs),
+                        _dptr(u), _dptr(v), float(row_offset), float(col_offset))
+        out = np.empty_like(cube)
+        disp = np.empty((2,) + cube.shape[1:], dtype=np.float64) if return_displacement else None
+        self._chk(self._lib.coreg_pixels_destretch(
+            self._h, cube.ctypes.data, COREG_F32 if cube.dtype == np.float32 else COREG_F64, cube.shape[0], cube.shape[1],
+            cube.shape[2], C.byref(f), out.ctypes.data, None if disp is None else disp.ctypes.data))
+        return (out, disp) if return_displacement else out
+
+    def pixels_destretch_last_ms(self) -> float:
+        ms = C.c_double(0.0)
+        self._chk(self._lib.coreg_pixels_destretch_last_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def set_point_shard(self, rank, world):
         self.set_option("shard_world", int(world))

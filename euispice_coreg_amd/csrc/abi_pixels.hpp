@@ -59,4 +59,15 @@ int coreg_pixels_last_timing(coreg_handle* h, double* ms) {
     return pixels_last_timing(h, ms);
 }
 
+int coreg_pixels_destretch(coreg_handle* h, const void* cube, int dtype, int32_t n_planes, int32_t ny, int32_t nx,
+                           const coreg_pixels_field* f, void* out, double* displacement) {
+    if (!h) return COREG_EINVAL;
+    return pixels_destretch(h, cube, dtype, n_planes, ny, nx, f, out, displacement);
+}
+
+int coreg_pixels_destretch_last_ms(coreg_handle* h, double* ms) {
+    if (!h) return COREG_EINVAL;
+    return pixels_destretch_last_ms(h, ms);
+}
+
 }  // extern "C"

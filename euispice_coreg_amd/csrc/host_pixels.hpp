@@ -11,6 +11,10 @@ struct PixelsState {
     long long n_tile_counts = 0;    //     or a tiled sweep has run; tiles x lags of the last tiled sweep, likewise
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
+    // coreg_pixels_destretch: buffers, events and time of its own (the sweep's images, counts and events are not touched)
+    DevBuf ds_src, ds_dst, ds_disp, ds_nodes;
+    hipEvent_t ds_ev[2] = {nullptr, nullptr};
+    bool ds_timed = false;
 };
 
 namespace {
@@ -39,9 +43,11 @@ void pixels_release(coreg_handle* h) {
         g_pixels.erase(it);
     }
     DevBuf* bufs[] = {&st->large, &st->large_tmp, &st->small, &st->box, &st->planes, &st->sums, &st->plan, &st->corr,
-                      &st->counts};
+                      &st->counts, &st->ds_src, &st->ds_dst, &st->ds_disp, &st->ds_nodes};
     for (DevBuf* b : bufs) b->release();
     for (hipEvent_t e : st->ev)
+        if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : st->ds_ev)
         if (e) (void)hipEventDestroy(e);
     delete st;
 }
@@ -359,4 +365,95 @@ int pixels_last_tile_counts(coreg_handle* h, double* out) {
     PixelsState* st = pixels_state(h, false);
     if (!st || st->n_tile_counts < 1) return fail(h, COREG_ESTATE, "pixels: no tiled sweep has run since the images were set");
     return pixels_read(h, st->counts.p, (size_t)st->n_tile_counts, out);
+}
+
+// The destretch of a cube [n_planes][ny][nx] by a local shift field (csrc/pixels_field.hpp, k_pixels_destretch): every
+// argument is checked before any GPU work; the cube goes up as stored and comes back in its own type.
+int pixels_destretch(coreg_handle* h, const void* cube, int dtype, int32_t n_planes, int32_t ny, int32_t nx,
+                     const coreg_pixels_field* f, void* out, double* displacement) {
+    if (!cube || !out || !f || !f->ys || !f->xs || !f->u || !f->v) return fail(h, COREG_EINVAL, "destretch: null pointer");
+    if (dtype != COREG_F32 && dtype != COREG_F64) return fail(h, COREG_EINVAL, "destretch: dtype must be COREG_F32 or COREG_F64");
+    if (n_planes < 1 || ny < 1 || nx < 1) return fail(h, COREG_EINVAL, "destretch: empty cube");
+    if (too_many(ny, nx) || too_many((long long)ny * nx, n_planes))
+        return fail(h, COREG_EINVAL, "destretch: more than 2^31 - 1 elements (cut the cube along its planes)");
+    if (f->interpolation != PIX_FIELD_BILINEAR && f->interpolation != PIX_FIELD_NEAREST)
+        return fail(h, COREG_EINVAL, "destretch: unknown interpolation (0 bilinear, 1 nearest)");
+    if (f->n_ty < 1 || f->n_tx < 1 || f->tile_ny < 1 || f->tile_nx < 1 || too_many(f->n_ty, f->n_tx))
+        return fail(h, COREG_EINVAL, "destretch: the field needs at least one node per axis and a positive tile shape");
+    if (!std::isfinite(f->row_offset) || !std::isfinite(f->col_offset))
+        return fail(h, COREG_EINVAL, "destretch: an offset is not finite");
+    const int naxis[2] = {f->n_ty, f->n_tx};
+    const double* axis[2] = {f->ys, f->xs};
+    for (int a = 0; a < 2; ++a)
+        for (int k = 0; k < naxis[a]; ++k)
+            if (!std::isfinite(axis[a][k]) || (k > 0 && !(axis[a][k] > axis[a][k - 1])))
+                return fail(h, COREG_EINVAL, "destretch: node coordinates must be finite and strictly increasing");
+    const size_t n_nodes = (size_t)f->n_ty * f->n_tx;
+    for (size_t k = 0; k < n_nodes; ++k)
+        if (!std::isfinite(f->u[k]) || !std::isfinite(f->v[k])) return fail(h, COREG_EINVAL, "destretch: a node is not finite");
+    PixelsState* st = pixels_state(h, true);
+    if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
+    RETCHK(bind_device(h));
+    const size_t n_pix = (size_t)ny * nx, n = n_pix * (size_t)n_planes;
+    const size_t bytes = n * (dtype == COREG_F32 ? sizeof(float) : sizeof(double));
+    // the nodes on the device: ys, xs, u, v one after the other
+    std::vector<double> nodes;
+    nodes.reserve(f->n_ty + f->n_tx + 2 * n_nodes);
+    nodes.insert(nodes.end(), f->ys, f->ys + f->n_ty);
+    nodes.insert(nodes.end(), f->xs, f->xs + f->n_tx);
+    nodes.insert(nodes.end(), f->u, f->u + n_nodes);
+    nodes.insert(nodes.end(), f->v, f->v + n_nodes);
+    HIPCHK(st->ds_nodes.reserve(nodes.size() * sizeof(double)));
+    HIPCHK(st->ds_src.reserve(bytes));
+    HIPCHK(st->ds_dst.reserve(bytes));
+    if (displacement) HIPCHK(st->ds_disp.reserve(2 * n_pix * sizeof(double)));
+    for (hipEvent_t& e : st->ds_ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    st->ds_timed = false;
+    HIPCHK(hipMemcpyAsync(st->ds_nodes.p, nodes.data(), nodes.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(st->ds_src.p, cube, bytes, hipMemcpyHostToDevice, h->stream));
+    PixDestretch a = {};
+    a.src = st->ds_src.p;
+    a.dst = st->ds_dst.p;
+    a.disp = displacement ? st->ds_disp.as<double>() : nullptr;
+    a.f.n_ty = f->n_ty;
+    a.f.n_tx = f->n_tx;
+    a.f.th = f->tile_ny;
+    a.f.tw = f->tile_nx;
+    a.f.interp = f->interpolation;
+    a.f.ys = st->ds_nodes.as<double>();
+    a.f.xs = a.f.ys + f->n_ty;
+    a.f.u = a.f.xs + f->n_tx;
+    a.f.v = a.f.u + n_nodes;
+    a.f.row_offset = f->row_offset;
+    a.f.col_offset = f->col_offset;
+    a.nx = nx;
+    a.ny = ny;
+    a.n_planes = n_planes;
+    const long long chunks = ((long long)n_planes + kPixDsPlanes - 1) / kPixDsPlanes;
+    const dim3 grid((unsigned)((n_pix + kPixThreads - 1) / kPixThreads), (unsigned)std::min<long long>(chunks, 65535));
+    HIPCHK(hipEventRecord(st->ds_ev[0], h->stream));
+    if (dtype == COREG_F32)
+        hipLaunchKernelGGL(k_pixels_destretch<float>, grid, dim3(kPixThreads), 0, h->stream, a);
+    else
+        hipLaunchKernelGGL(k_pixels_destretch<double>, grid, dim3(kPixThreads), 0, h->stream, a);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(st->ds_ev[1], h->stream));
+    HIPCHK(hipMemcpyAsync(out, st->ds_dst.p, bytes, hipMemcpyDeviceToHost, h->stream));
+    if (displacement)
+        HIPCHK(hipMemcpyAsync(displacement, st->ds_disp.p, 2 * n_pix * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    st->ds_timed = true;
+    return COREG_OK;
+}
+
+int pixels_destretch_last_ms(coreg_handle* h, double* ms) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || !st->ds_timed) return fail(h, COREG_ESTATE, "destretch: no destretch has run");
+    if (!ms) return fail(h, COREG_EINVAL, "destretch: null pointer");
+    RETCHK(bind_device(h));
+    float t = 0.f;
+    HIPCHK(hipEventElapsedTime(&t, st->ds_ev[0], st->ds_ev[1]));
+    *ms = (double)t;
+    return COREG_OK;
 }

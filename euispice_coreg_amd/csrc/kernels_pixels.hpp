@@ -18,11 +18,15 @@
 //   k_pixels_finalize         correlation: float32-rounded numerator / sqrt(product of the centred squares), NaN for an
 //                             empty or flat overlap; residus_masked: sqrt(sum of squares / n), NaN for no finite term
 //                             or a poisoned one; either way the lag's sample count
+//   k_pixels_destretch<T>     the resample of a cube [n_planes][ny][nx] of stored type T (float / double) by a local shift
+//                             field (csrc/pixels_field.hpp): one thread per output pixel forms
+//                             the displacement, the taps and the weights once and walks a chunk of planes with them
 //
 // Reference arithmetic restated (paths relative to euispice_coreg/): pxlshift/alignment_pixels.py:38-55 (mask),
 // pxlshift/c_correlate.py:41-63 (Pearson, numerator stored as float32), :126-143 (sub-resolution), :72-81 +
 // utils/matrix_transform.py:78-106 (polar round trip), :86-107 (displacement of the large image).
 #pragma once
+#include "pixels_field.hpp"
 namespace coreg {
 
 constexpr int kPixG = 16;         // dx lags per workgroup, all within kPixG columns of the group's first
@@ -156,6 +160,46 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_finalize(const double* _
     const long long o = ((long long)i * n_dy + j) * n_rot + k;
     corr[o] = r;
     counts[o] = cnt;
+}
+
+// Destretch: dst[p][Y][X] = order-1 sample of src[p] at (Y - v, X - u), (u, v) the field's displacement at (Y, X); no
+// sample (NaN) outside the plane.  blockIdx.x deals runs of kPixThreads output pixels (consecutive along X: the stores and,
+// the displacement being smooth, the tap rows are coalesced), blockIdx.y chunks of kPixDsPlanes planes (the last one
+// short; a grid stride when there are more chunks than gridDim.y).  The node arrays are a few hundred doubles at most
+// and are read through the cache.  disp: nullptr or [2][ny][nx], (u, v) of every pixel, stored by the first chunk.
+constexpr int kPixDsPlanes = 8;
+
+struct PixDestretch {
+    const void* src;  // [n_planes][ny][nx] of T
+    void* dst;        // the same
+    double* disp;
+    PixField f;
+    int nx, ny, n_planes;
+};
+
+template <class T>
+__global__ __launch_bounds__(kPixThreads) void k_pixels_destretch(PixDestretch p) {
+#pragma clang fp contract(off)
+    const long long n = (long long)p.nx * p.ny;
+    const long long q = (long long)blockIdx.x * kPixThreads + threadIdx.x;
+    if (q >= n) return;
+    const int Y = (int)(q / p.nx), X = (int)(q - (long long)Y * p.nx);
+    double u, v;
+    field_displacement(p.f, (double)X, (double)Y, &u, &v);
+    if (p.disp && blockIdx.y == 0) {
+        p.disp[q] = u;
+        p.disp[n + q] = v;
+    }
+    const PixTaps t = field_taps(p.nx, p.ny, (double)X - u, (double)Y - v);
+    const T* __restrict__ src = (const T*)p.src;
+    T* __restrict__ dst = (T*)p.dst;
+    for (long long p0 = (long long)blockIdx.y * kPixDsPlanes; p0 < p.n_planes; p0 += (long long)gridDim.y * kPixDsPlanes) {
+        const int np = (int)(p.n_planes - p0 < kPixDsPlanes ? p.n_planes - p0 : kPixDsPlanes);
+        for (int k = 0; k < np; ++k) {
+            const size_t o = (size_t)(p0 + k) * (size_t)n;
+            dst[o + q] = t.inside ? (T)field_sample(src + o, p.nx, t) : (T)__builtin_nan("");
+        }
+    }
 }
 
 }  // namespace coreg

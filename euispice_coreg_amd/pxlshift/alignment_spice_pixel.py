@@ -3,13 +3,16 @@
 (pxlshift/alignment_spice_pixel.py:9-101): the small image is a SPICE L2 window summed over wavelength between the
 slit edges, with a 2-D header in degrees whose CDELT1 is shortened by the apparent solar rotation during one raster
 step; the sweep is `AlignmentPixels.find_best_parameters`.  Level-3 input raises NotImplementedError.
+
+Beyond the reference: `row_offset`, the first row of the L2 window that the small image holds, and
+`write_destretched_fits`, the L2 file with the planes of the chosen windows resampled by a `LocalShiftField`.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from ..utils import fits_io, header as hdrutil, spice_header
-from .alignment_pixels import AlignmentPixels
+from .alignment_pixels import AlignmentPixels, large_fov_centre, set_pixels_shift_cards
 
 
 class AlignmentSpicePixel(AlignmentPixels):
@@ -70,9 +73,41 @@ class AlignmentSpicePixel(AlignmentPixels):
         self.hdr_small = spice_header.celestial_header(hdr)
         ylen = cube.shape[2]
         ylim = max(ymin, ylen - ymax - 1)
+        self.row_offset = int(ylim)  # row 0 of the small image is row `row_offset` of the window
         # (a reduction over the outer axis adds the planes one after another, as the reference's nansum does)
         self.data_small = np.nansum(np.asarray(cube[0][:, ylim:(ylen - ylim), :], dtype=np.float64), axis=0)
         self.hdr_small["CRPIX1"] = (self.data_small.shape[1] + 1) / 2
         self.hdr_small["CRPIX2"] = (self.data_small.shape[0] + 1) / 2
         self.hdr_small["NAXIS1"] = self.data_small.shape[1]
         self.hdr_small["NAXIS2"] = self.data_small.shape[0]
+
+    def write_destretched_fits(self, field, windows, path_out, reference=None):
+        """Write every HDU of the L2 file to `path_out`; in the windows named in `windows` (EXTNAME, index or index from
+        the end, as `write_corrected_fits` selects them) every plane of `cube[0]` is destretched by `field` (a
+        `LocalShiftField` of this object's `find_local_shifts`) about the rigid shift `reference` = (rx, ry), default the
+        field's `median_shift`, and the header gets the four cards of `align_pixels_shift` at that shift plus DSTRETCH
+        (True), DSTR_DX and DSTR_DY (the reference, pixels).  ValueError for a window whose (ny, nx) is not that of the
+        window the field was measured on, and when no window is selected."""
+        rx, ry = field._reference(reference)
+        want = (field.image_shape[0] + 2 * self.row_offset, field.image_shape[1])
+        hdus = fits_io.read_all(self.spice_path)
+        mid = None
+        out, n = [], len(hdus)
+        for ii, (data, hdr) in enumerate(hdus):
+            if not ((hdr.get("EXTNAME", "nothing98695") in windows) or (ii in windows) or ((ii - n) in windows)):
+                out.append((data, hdr))
+                continue
+            if data is None or np.ndim(data) != 4 or tuple(np.shape(data)[2:]) != want:
+                raise ValueError(f"window {ii}: a cube [time, wavelength, {want[0]}, {want[1]}] is needed, the shape of "
+                                 "the window the field was measured on")
+            if mid is None:
+                mid = large_fov_centre(self.fsi_path, self.fsi_window)
+            data = np.array(data)
+            data[0] = field.destretch(data[0], reference=(rx, ry), row_offset=self.row_offset, device=self.device)
+            hdr = fits_io.Header(hdr).copy()
+            set_pixels_shift_cards(hdr, mid, rx, ry)
+            hdr["DSTRETCH"], hdr["DSTR_DX"], hdr["DSTR_DY"] = True, float(rx), float(ry)
+            out.append((data, hdr))
+        if mid is None:
+            raise ValueError("has not corrected any window.")
+        fits_io.write_images(path_out, out)

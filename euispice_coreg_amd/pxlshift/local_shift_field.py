@@ -13,7 +13,12 @@ without any valid tile raises ValueError.
 
 From the valid tiles: `median_shift` and `scatter` (1.4826 x the median absolute deviation) of dx and dy -- an empirical
 error bar on a global shift -- and `drift()`, the least-squares planes of dx and dy over the tile centres: the drift
-across a raster.  There is no FITS card for a tile-dependent correction; nothing is written.
+across a raster.
+
+There is no FITS card for a tile-dependent correction: the field is applied to the pixels instead.  `node_shifts` gives
+the field as node values at the tile centres (host only); `destretch` resamples an image, or a stack of planes, by it
+(include/coreg_hip.h: coreg_pixels_destretch, the rule is stated there), so that the result lies on its own grid at one
+rigid shift, the `reference`; `AlignmentSpicePixel.write_destretched_fits` writes the planes of SPICE windows so corrected.
 """
 from __future__ import annotations
 
@@ -25,6 +30,11 @@ from ..hdrshift.alignment import apply_min_overlap, min_overlap_floor
 from ..hdrshift.alignment_results import gaussian_sub_lag
 from .alignment_pixels import tile_grid
 from .pixel_alignment_results import _BEST
+
+
+_FILLS = ("plane", "median", "zero")
+_INTERPOLATIONS = ("bilinear", "nearest")  # (the library's codes: 0, 1)
+MAX_ELEMENTS = 2 ** 31 - 1  # of one coreg_pixels_destretch call
 
 
 class LocalShiftField:
@@ -112,6 +122,92 @@ class LocalShiftField:
             raise ValueError("drift needs tile centres that are not collinear")
         sol = np.linalg.lstsq(M, np.column_stack([self.shift_dx[self.valid], self.shift_dy[self.valid]]), rcond=None)[0]
         return sol.T.copy()
+
+    # ------------------------------------------------------------------------------------------------- destretch
+    def _reference(self, reference):
+        if reference is None:
+            return self.median_shift
+        try:
+            rx, ry = (float(r) for r in reference)
+        except (TypeError, ValueError):
+            raise ValueError("reference must be None or a pair (rx, ry) of pixels") from None
+        if not (np.isfinite(rx) and np.isfinite(ry)):
+            raise ValueError("reference must be finite")
+        return rx, ry
+
+    def node_shifts(self, reference=None, fill="plane"):
+        """(u, v), each [n_ty, n_tx]: the shifts of the tiles about the rigid shift `reference` = (rx, ry), default
+        `median_shift` -- u = dx - rx, v = dy - ry -- the node values of the field at `tile_centres`.  An invalid tile
+        is filled: "plane" (the `drift()` planes at the tile's centre; "median" where `drift()` raises), "median"
+        (`median_shift`) or "zero" (the reference itself: no displacement).  ValueError for a node that is still not
+        finite.  Host only."""
+        if fill not in _FILLS:
+            raise ValueError(f"fill must be one of {_FILLS}")
+        rx, ry = self._reference(reference)
+        dx, dy = self.shift_dx.copy(), self.shift_dy.copy()
+        bad = ~self.valid
+        if bad.any():
+            plane = None
+            if fill == "plane":
+                try:
+                    plane = self.drift()
+                except ValueError:
+                    fill = "median"
+            if plane is not None:
+                xc, yc = self.tile_centres[..., 0], self.tile_centres[..., 1]
+                dx[bad] = (plane[0, 0] + plane[0, 1] * xc + plane[0, 2] * yc)[bad]
+                dy[bad] = (plane[1, 0] + plane[1, 1] * xc + plane[1, 2] * yc)[bad]
+            elif fill == "median":
+                dx[bad], dy[bad] = self.median_shift
+            else:
+                dx[bad], dy[bad] = rx, ry
+        u, v = dx - rx, dy - ry
+        if not (np.isfinite(u).all() and np.isfinite(v).all()):
+            raise ValueError("a node of the field is not finite")
+        return u, v
+
+    def destretch(self, data, reference=None, interpolation="bilinear", fill="plane", row_offset=0, col_offset=0,
+                  return_displacement=False, device=None):
+        """`data` resampled by the field so that it lies on its own grid at the rigid shift `reference` (default
+        `median_shift`): D(Y, X) = S(Y - v(Y, X), X - u(Y, X)), order 1, NaN where the sample leaves the image, with
+        (u, v) the `node_shifts(reference, fill)` interpolated to the output pixel -- "bilinear" between the tile centres
+        and constant beyond the outer ones, or "nearest", the value of the pixel's tile.  The rule is written out in
+        include/coreg_hip.h (coreg_pixels_destretch); the best rotations of the tiles are not applied.
+
+        data: [h, w] or any stack [..., ny, nx] of float32 / float64, every plane resampled alike (a big-endian view of a
+        FITS data unit is converted on the host; the result is in native byte order).  Pixel (Y, X) of a plane has field
+        coordinate (Y - row_offset, X - col_offset): for planes taller or wider than the image the field was measured on.
+        Returns an array of the shape and type of `data`; with return_displacement, also the displacement [2, ny, nx]
+        = (u, v) of every output pixel."""
+        if interpolation not in _INTERPOLATIONS:
+            raise ValueError(f"interpolation must be one of {_INTERPOLATIONS}")
+        u, v = self.node_shifts(reference, fill)
+        a = np.asarray(data)
+        if a.dtype.kind != "f" or a.dtype.itemsize not in (4, 8):
+            raise TypeError("destretch takes float32 or float64 data")
+        if a.ndim < 2 or a.size == 0:
+            raise ValueError("destretch takes an image [h, w] or a stack [..., ny, nx]")
+        row_offset, col_offset = float(row_offset), float(col_offset)
+        if not (np.isfinite(row_offset) and np.isfinite(col_offset)):
+            raise ValueError("row_offset and col_offset must be finite")
+        native = a.dtype.newbyteorder("=")
+        ny, nx = a.shape[-2:]
+        planes = a.reshape((-1, ny, nx))
+        from .. import _lib
+        hnd = _lib.shared_handle(-1 if device is None else device)
+        xs, ys = self.tile_centres[0, :, 0], self.tile_centres[:, 0, 1]
+        out = np.empty(planes.shape, dtype=native)
+        disp = None
+        step = max(1, MAX_ELEMENTS // (ny * nx))  # planes per call: the library takes 2^31 - 1 elements at most
+        for p0 in range(0, len(planes), step):
+            part = np.ascontiguousarray(planes[p0:p0 + step], dtype=native)
+            got = hnd.pixels_destretch(part, ys, xs, u, v, self.tile_shape, _INTERPOLATIONS.index(interpolation),
+                                       row_offset, col_offset, return_displacement=return_displacement and p0 == 0)
+            if return_displacement and p0 == 0:
+                got, disp = got
+            out[p0:p0 + step] = got
+        out = out.reshape(a.shape)
+        return (out, disp) if return_displacement else out
 
     def __str__(self):
         (mx, my), (sx, sy) = self.median_shift, self.scatter

@@ -580,7 +580,31 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  *                                        [h + max dy - min dy][w + max dx - min dx] from (l0 + min dy, l1 + min dx) on
  *   coreg_pixels_get_rotated             plane k [h][w] of the last sweep
  *   coreg_pixels_last_timing             ms[3]: preparation (box + planes), first pass, second pass of the last sweep,
- *                                        whichever score it ran (HIP events) */
+ *                                        whichever score it ran (HIP events)
+ *   coreg_pixels_destretch               the resample of a cube by a local shift field (pxlshift.LocalShiftField.destretch):
+ *                                        see the rule below.  cube and out: host memory [n_planes][ny][nx] of dtype
+ *                                        COREG_F32 / COREG_F64, out in the type and shape of cube; displacement: NULL or
+ *                                        host memory [2][ny][nx], (u, v) of every output pixel.  The call neither reads nor
+ *                                        changes the sweep's state (resident images, last counts, coreg_pixels_last_timing).
+ *                                        COREG_EINVAL with a message: node coordinates that are not finite and strictly
+ *                                        increasing, a node or an offset that is not finite, an unknown interpolation, an
+ *                                        empty shape, more than 2^31 - 1 elements (cut the cube along its planes)
+ *   coreg_pixels_destretch_last_ms       the kernel time of the last coreg_pixels_destretch (HIP events)
+ *
+ * The destretch rule.  A tile's shift (dx, dy) means: small pixel (y, x) lies on sub-resolved large pixel
+ * (l0 + y + dy, l1 + x + dx).  With a rigid reference shift (rx, ry), the nodes u = dx - rx, v = dy - ry at the tile
+ * centres (xs[n_tx], ys[n_ty], strictly increasing), the destretched image lies on the image's own grid at the rigid
+ * shift:  D(Y, X) = S(Y - v(Y, X), X - u(Y, X)).  The field is evaluated at the output pixel (the error, |grad field| |u|,
+ * is of second order and not iterated away), at field coordinate (X', Y') = (X - col_offset, Y - row_offset), float64,
+ * no contraction, in this order:
+ *   bilinear (0)  i the largest index with xs[i] <= X', clamped to [0, n_tx - 2]; fx = (X' - xs[i]) / (xs[i+1] - xs[i])
+ *                 clamped to [0, 1]; j, fy likewise from ys;
+ *                 u = (u00 (1 - fx) + u01 fx) (1 - fy) + (u10 (1 - fx) + u11 fx) fy, v likewise.  An axis of one node is
+ *                 constant; outside the outer centres the field is held constant
+ *   nearest (1)   the node of tile (clamp(floor(Y' / tile_ny), 0, n_ty - 1), clamp(floor(X' / tile_nx), 0, n_tx - 1))
+ * The sample is the order-1 rule of the sweep's resamples: taps row by row, (pixel * wy) * wx, summed from 0 in float64
+ * and rounded once to the cube's type; a coordinate < 0 or > n - 1 gives NaN; a NaN propagates through any tap, weight 0
+ * included; a coordinate exactly n - 1 takes the mirrored tap n - 2. */
 typedef struct coreg_pixels_plan {
     double ratio1, ratio2;    /* sample k of the sub-resolved image lies at x = k ratio1, y = k ratio2 of the large image:
                                  CDELTi(small, in the large image's unit) / CDELTi(large)                              */
@@ -604,6 +628,14 @@ int coreg_pixels_last_tile_counts(coreg_handle* h, double* dst);
 int coreg_pixels_get_large_box(coreg_handle* h, double* out);
 int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out);
 int coreg_pixels_last_timing(coreg_handle* h, double* ms);
+typedef struct coreg_pixels_field {
+    int32_t n_ty, n_tx, tile_ny, tile_nx, interpolation;   /* 0 bilinear, 1 nearest */
+    const double *ys, *xs, *u, *v;                         /* [n_ty], [n_tx], [n_ty][n_tx] x 2 */
+    double row_offset, col_offset;
+} coreg_pixels_field;
+int coreg_pixels_destretch(coreg_handle* h, const void* cube, int dtype, int32_t n_planes, int32_t ny, int32_t nx,
+                           const coreg_pixels_field* f, void* out, double* displacement /* NULL or [2][ny][nx] */);
+int coreg_pixels_destretch_last_ms(coreg_handle* h, double* ms);
 
 /* ---- All GPUs of the node from ONE process ------------------------------------------------------------------------
  * The reference's `Alignment(..., parallelism=True, counts_cpu_max=N)` uses the whole machine from a plain
