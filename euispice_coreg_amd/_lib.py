@@ -20,6 +20,7 @@ COREG_EINVAL, COREG_EHIP, COREG_ESTATE, COREG_ENOTIMPL, COREG_ENOMEM = -1, -2, -
 COREG_F32, COREG_F64 = 0, 1
 PROJ_TAN, PROJ_CAR = 0, 1
 METHOD_CORRELATION, METHOD_RESIDUS, METHOD_RESIDUS_MASKED = 0, 1, 2
+METHOD_MUTUAL_INFORMATION = 3  # (the pixel-lag sweep only: coreg_pixels_set_bins)
 CDELT_INTENDED, CDELT_REFERENCE = 0, 1
 
 
@@ -300,6 +301,7 @@ SYMBOLS = [
     ("coreg_pixels_shift_large", C.c_int, [_P, C.c_double, C.c_double]),
     ("coreg_pixels_sweep", C.c_int, [_P, C.POINTER(PixelsPlan), _P]),
     ("coreg_pixels_sweep_method", C.c_int, [_P, C.POINTER(PixelsPlan), C.c_int, _P]),
+    ("coreg_pixels_set_bins", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_pixels_last_counts", C.c_int, [_P, _P]),
     ("coreg_pixels_sweep_tiles", C.c_int, [_P, C.POINTER(PixelsPlan), C.c_int, C.c_int32, C.c_int32, _P]),
     ("coreg_pixels_last_tile_counts", C.c_int, [_P, _P]),
@@ -738,7 +740,16 @@ class CoregHandle(_ImageIntake):
     def pixels_shift_large(self, dx, dy):
         self._chk(self._lib.coreg_pixels_shift_large(self._h, float(dx), float(dy)))
 
+    def pixels_set_bins(self, edges_small, edges_large):
+        """coreg_pixels_set_bins: the edge lists of METHOD_MUTUAL_INFORMATION (1 to 31 finite, strictly increasing float64
+        entries each); they stay with the handle until set again."""
+        es = np.ascontiguousarray(edges_small, dtype=np.float64).ravel()
+        el = np.ascontiguousarray(edges_large, dtype=np.float64).ravel()
+        self._chk(self._lib.coreg_pixels_set_bins(self._h, es.ctypes.data, len(es), el.ctypes.data, len(el)))
+
     def _pixels_sweep(self, plan, method, tile_shape):
+        if int(method) == METHOD_MUTUAL_INFORMATION and plan.get("bins") is not None:
+            self.pixels_set_bins(*plan["bins"])
         dx = np.ascontiguousarray(plan["lag_dx"], dtype=np.int32)
         dy = np.ascontiguousarray(plan["lag_dy"], dtype=np.int32)
         rot = np.ascontiguousarray(plan["lag_drot_rad"], dtype=np.float64)

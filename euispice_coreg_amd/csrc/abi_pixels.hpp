@@ -28,6 +28,12 @@ int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* c
     return coreg_pixels_sweep_method(h, plan, COREG_METHOD_CORRELATION, corr_out);
 }
 
+int coreg_pixels_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small, const double* edges_large,
+                          int32_t n_large) {
+    if (!h) return COREG_EINVAL;
+    return pixels_set_bins(h, edges_small, n_small, edges_large, n_large);
+}
+
 int coreg_pixels_last_counts(coreg_handle* h, double* dst) {
     if (!h) return COREG_EINVAL;
     return pixels_last_counts(h, dst);

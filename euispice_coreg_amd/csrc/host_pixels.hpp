@@ -15,6 +15,10 @@ struct PixelsState {
     DevBuf ds_src, ds_dst, ds_disp, ds_nodes;
     hipEvent_t ds_ev[2] = {nullptr, nullptr};
     bool ds_timed = false;
+    // coreg_pixels_set_bins: the edge lists of COREG_METHOD_MUTUAL_INFORMATION, kept until set again
+    std::vector<double> edges_small, edges_large;
+    // the dynamic LDS each k_pixels_mi instantiation ([tiled][wide]) has been allowed on this handle's device so far
+    size_t mi_lds[2][2] = {{0, 0}, {0, 0}};
 };
 
 namespace {
@@ -126,6 +130,17 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     return pixels_resample(h, PIX_AFFINE, a);
 }
 
+// the edge lists of the mutual-information score (csrc/pixels_bins.hpp: 1 to 31 entries, finite, strictly increasing)
+int pixels_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small, const double* edges_large, int32_t n_large) {
+    if (!bins_edges_ok(edges_small, n_small) || !bins_edges_ok(edges_large, n_large))
+        return fail(h, COREG_EINVAL, "pixels: an edge list needs 1 to 31 finite, strictly increasing entries");
+    PixelsState* st = pixels_state(h, true);
+    if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
+    st->edges_small.assign(edges_small, edges_small + n_small);
+    st->edges_large.assign(edges_large, edges_large + n_large);
+    return COREG_OK;
+}
+
 template <int PASS>
 static void pixels_launch_pass(coreg_handle* h, const dim3& grid, const PixSweep& s, const PixTiles* t) {
     if (t)
@@ -134,16 +149,35 @@ static void pixels_launch_pass(coreg_handle* h, const dim3& grid, const PixSweep
         hipLaunchKernelGGL(k_pixels_sweep<PASS>, grid, dim3(kPixThreads), 0, h->stream, s);
 }
 
+// The histograms at 32 x 32 bins are 64 KiB of dynamic LDS beside the kernel's static 13.5 KiB: more than the 64 KiB a
+// workgroup has on CDNA1-3.  gfx950 gives a workgroup up to 160 KiB; the kernel is allowed what it needs, once per
+// instantiation and again only when a later sweep needs more (`allowed`: PixelsState::mi_lds).
+static_assert((size_t)kPixG * kPixMaxBins * kPixMaxBins * sizeof(uint32_t) + 16 * 1024 <= 160 * 1024,
+              "k_pixels_mi: histograms and staging must fit the 160 KiB of LDS of a gfx950 workgroup");
+
+template <bool TILED, int THREADS>
+static int pixels_launch_mi(coreg_handle* h, const dim3& grid, size_t dyn, size_t* allowed, const PixSweep& s, const PixTiles& t,
+                            const PixBins& b) {
+    if (dyn > *allowed) {
+        HIPCHK(hipFuncSetAttribute((const void*)k_pixels_mi<TILED, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+        *allowed = dyn;
+    }
+    hipLaunchKernelGGL((k_pixels_mi<TILED, THREADS>), grid, dim3(THREADS), dyn, h->stream, s, t, b);
+    return COREG_OK;
+}
+
 // The untiled sweep (tile == nullptr: one cube [n_dx][n_dy][n_rot]) and the tiled one (tile = {rows, columns} of a tile:
 // one such cube per tile, [n_ty][n_tx] of them): the same validation, box, rotation planes, groups and events.
 static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int method, const int32_t* tile, double* corr_out) {
     if (method == COREG_METHOD_RESIDUS)
         return fail(h, COREG_ENOTIMPL, "pixels: method residus is not implemented (the reference's pxlshift has no such score); "
                                        "residus_masked is");
-    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS_MASKED)
+    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS_MASKED && method != COREG_METHOD_MUTUAL_INFORMATION)
         return fail(h, COREG_EINVAL, "pixels: unknown method");
-    const bool resid = method == COREG_METHOD_RESIDUS_MASKED;
+    const bool resid = method == COREG_METHOD_RESIDUS_MASKED, mi = method == COREG_METHOD_MUTUAL_INFORMATION;
     PixelsState* st = pixels_state(h, false);
+    if (mi && (!st || st->edges_small.empty() || st->edges_large.empty()))
+        return fail(h, COREG_ESTATE, "pixels: mutual information needs its bins (coreg_pixels_set_bins)");
     if (!st || !st->large.p || !st->small.p) return fail(h, COREG_ESTATE, "pixels: the large and the small image must be set");
     if (!pl || !corr_out || !pl->lag_dx || !pl->lag_dy || !pl->lag_drot) return fail(h, COREG_EINVAL, "pixels: null pointer");
     if (pl->n_dx < 1 || pl->n_dy < 1 || pl->n_rot < 1) return fail(h, COREG_EINVAL, "pixels: empty lag axis");
@@ -204,14 +238,22 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
     const size_t n_groups = groups.size();
     // plan on the device: groups, dx, dy
     const size_t off_dx = n_groups * sizeof(PixGroup), off_dy = off_dx + (size_t)pl->n_dx * sizeof(int);
-    std::vector<unsigned char> blob(off_dy + (size_t)pl->n_dy * sizeof(int));
+    // (mutual information: the two edge lists behind them, on a multiple of 8 bytes)
+    const size_t off_es = (off_dy + (size_t)pl->n_dy * sizeof(int) + 7) / 8 * 8;
+    const size_t off_el = off_es + (mi ? st->edges_small.size() : 0) * sizeof(double);
+    std::vector<unsigned char> blob(mi ? off_el + st->edges_large.size() * sizeof(double)
+                                       : off_dy + (size_t)pl->n_dy * sizeof(int));
     std::memcpy(blob.data(), groups.data(), off_dx);
     std::memcpy(blob.data() + off_dx, pl->lag_dx, (size_t)pl->n_dx * sizeof(int));
     std::memcpy(blob.data() + off_dy, pl->lag_dy, (size_t)pl->n_dy * sizeof(int));
+    if (mi) {
+        std::memcpy(blob.data() + off_es, st->edges_small.data(), st->edges_small.size() * sizeof(double));
+        std::memcpy(blob.data() + off_el, st->edges_large.data(), st->edges_large.size() * sizeof(double));
+    }
     HIPCHK(st->plan.reserve(blob.size()));
     HIPCHK(st->box.reserve((size_t)bW * bH * sizeof(double)));
     HIPCHK(st->planes.reserve((size_t)w * hh * pl->n_rot * sizeof(double)));
-    HIPCHK(st->sums.reserve((size_t)n_out * 6 * sizeof(double)));
+    if (!mi) HIPCHK(st->sums.reserve((size_t)n_out * 6 * sizeof(double)));
     HIPCHK(st->corr.reserve((size_t)n_out * sizeof(double)));
     HIPCHK(st->counts.reserve((size_t)n_out * sizeof(double)));
     st->n_counts = st->n_tile_counts = 0;
@@ -277,10 +319,36 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
     const int band_w = tile ? tl.tw : w, band_h = tile ? tl.th : hh;
     s.cw = std::min(band_w, kPixTile);
     s.bh = std::max(1, std::min(std::min(kPixBandRows, kPixTile / s.cw), band_h));
-    double* sums0 = st->sums.as<double>();
-    double* sums1 = sums0 + 3 * n_out;
     const PixTiles* t = tile ? &tl : nullptr;
     const dim3 grid((unsigned)n_groups, (unsigned)pl->n_dy, (unsigned)(pl->n_rot * n_tiles));
+    if (mi) {
+        // one pass: histograms, score and counts (csrc/kernels_pixels_mi.hpp); the last two events bracket nothing
+        PixBins b = {};
+        b.edges_small = (const double*)((const unsigned char*)st->plan.p + off_es);
+        b.edges_large = (const double*)((const unsigned char*)st->plan.p + off_el);
+        b.n_small = (int)st->edges_small.size();
+        b.n_large = (int)st->edges_large.size();
+        b.corr = st->corr.as<double>();
+        b.counts = st->counts.as<double>();
+        b.n_rot = pl->n_rot;
+        const size_t dyn = (size_t)kPixG * (b.n_small + 1) * (b.n_large + 1) * sizeof(uint32_t);
+        const bool wide = dyn > kPixMiWideBytes;
+        size_t* allowed = &st->mi_lds[t ? 1 : 0][wide ? 1 : 0];
+        RETCHK(t ? (wide ? pixels_launch_mi<true, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b)
+                         : pixels_launch_mi<true, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b))
+                 : (wide ? pixels_launch_mi<false, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b)
+                         : pixels_launch_mi<false, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b)));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(st->ev[2], h->stream));
+        HIPCHK(hipEventRecord(st->ev[3], h->stream));
+        HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        st->timed = true;
+        (tile ? st->n_tile_counts : st->n_counts) = n_out;
+        return COREG_OK;
+    }
+    double* sums0 = st->sums.as<double>();
+    double* sums1 = sums0 + 3 * n_out;
     s.sums0 = nullptr;
     s.sums = sums0;
     if (resid)

@@ -28,3 +28,4 @@
 #include "kernels_finalize.hpp"  // k_finalize, k_refine_list, k_refine
 #include "kernels_context.hpp"   // iterative-context sweep (per-lag synthetic rasters)
 #include "kernels_pixels.hpp"    // integer pixel-lag sweep (pxlshift): resample, two-pass sweep, finalize
+#include "kernels_pixels_mi.hpp" // ... its mutual-information score: joint histograms in LDS, one pass

@@ -11,6 +11,10 @@ Beyond the reference (the defaults return what it returns): `method="residus_mas
 behind every entry of the last cube; `min_overlap`, entries of fewer samples set to NaN (hdrshift.alignment
 .apply_min_overlap); `return_type="PixelAlignmentResults"` (pixel_alignment_results.py).
 
+`method="mutual_information"` (not in the reference either): the mutual information, in nats, of the joint histogram of
+the two images over `bins` -- the score for two instruments whose intensities are not linearly related; best entry =
+maximum, the count of an entry the pairs in its histogram (`quantile_edges`, `check_edges`).
+
 `find_local_shifts` (not in the reference either): the small image cut into tiles, one lag cube, count cube, best entry
 and sub-lag fit per tile (include/coreg_hip.h: coreg_pixels_sweep_tiles; local_shift_field.py) -- the drift across a
 raster whose columns were not taken at one pointing.
@@ -31,6 +35,43 @@ from ..hdrshift.alignment import apply_min_overlap, library_method, min_overlap_
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
 
 _RETURN_TYPES = ("corr", "PixelAlignmentResults")
+MUTUAL_INFORMATION = "mutual_information"  # a method of the pixel-lag sweep only: hdrshift's `library_method` has none
+DEFAULT_BINS, MAX_BINS = 16, 32
+
+
+def quantile_edges(pixels, n_bins):
+    """The default edges of `n_bins` bins for an image: `np.unique` of the quantiles k / n_bins, k = 1 ... n_bins - 1, of
+    its finite pixels (ties collapse to fewer bins; a constant image leaves one edge).  ValueError without a finite
+    pixel."""
+    v = np.asarray(pixels, dtype=np.float64)
+    v = v[np.isfinite(v)]
+    if v.size == 0:
+        raise ValueError("bins: an image without a finite pixel has no quantiles")
+    return np.unique(np.quantile(v, np.arange(1, n_bins) / n_bins))
+
+
+def check_edges(edges, name):
+    """An edge list as the library takes it: 1-D float64, 1 to 31 entries, finite, strictly increasing."""
+    try:
+        e = np.array(edges, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise ValueError(f"bins: {name} must be a list of numbers") from None
+    if e.ndim != 1 or not 1 <= e.size <= MAX_BINS - 1:
+        raise ValueError(f"bins: {name} must hold 1 to {MAX_BINS - 1} edges")
+    if not np.all(np.isfinite(e)) or not np.all(np.diff(e) > 0):
+        raise ValueError(f"bins: {name} must be finite and strictly increasing")
+    return e
+
+
+def zero_lag_window(large_shape, small_shape, origin, ratio1, ratio2):
+    """(row slice, column slice) of the large image under the small image at lag (0, 0): rows floor(l0 ratio2) ...
+    ceil((l0 + h - 1) ratio2), columns likewise with l1, w, ratio1, both ends included, clipped to the image."""
+    out = []
+    for n, size, l, ratio in ((large_shape[0], small_shape[0], origin[0], ratio2),
+                              (large_shape[1], small_shape[1], origin[1], ratio1)):
+        lo, hi = int(np.floor(l * ratio)), int(np.ceil((l + size - 1) * ratio))
+        out.append(slice(max(lo, 0), min(hi, n - 1) + 1))
+    return tuple(out)
 
 
 def tile_grid(image_shape, tile_shape):
@@ -107,10 +148,19 @@ class AlignmentPixels:
         return float(d1 / hl["CDELT1"]), 0.0
 
     def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
-                  method="correlation", min_overlap=None, tile_shape=None) -> dict:
+                  method="correlation", min_overlap=None, tile_shape=None, bins=None) -> dict:
         """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU); with
-        `tile_shape` = (rows, columns), of a `find_local_shifts` call: the plan then holds the tile grid too."""
-        method_code = library_method(method)
+        `tile_shape` = (rows, columns), of a `find_local_shifts` call: the plan then holds the tile grid too.
+        `bins` (method "mutual_information" only, ValueError with any other): an integer 2 <= B <= 32 (default 16) --
+        `quantile_edges` of the small image and of the large image's pixels under the zero-lag window
+        (`zero_lag_window`), so the edges do not depend on the lags -- or a pair (edges_small, edges_large) as
+        `check_edges` takes them; the plan holds the pair as `plan["bins"]`."""
+        if method == MUTUAL_INFORMATION:
+            method_code = _lib.METHOD_MUTUAL_INFORMATION
+        else:
+            method_code = library_method(method)
+            if bins is not None:
+                raise ValueError("bins belongs to method='mutual_information'")
         if method_code == _lib.METHOD_RESIDUS:
             raise NotImplementedError("pxlshift has no unmasked 'residus' (the reference's pxlshift has no such score): "
                                       "use 'residus_masked'")
@@ -142,22 +192,42 @@ class AlignmentPixels:
                 "ratio_res_1": float(ratio1), "ratio_res_2": float(ratio2), "sub_shape": sub, "slc_small_ref": tuple(l),
                 "xc": round(w / 2), "yc": round(h / 2), "shift_large": None, "method": method,
                 "method_code": method_code, "min_overlap": min_overlap, "small_shape": (h, w)}
+        if method == MUTUAL_INFORMATION:
+            plan["bins"] = self._bin_edges(DEFAULT_BINS if bins is None else bins, plan)
         if tile_shape is not None:
             plan["tile_shape"], plan["tile_grid"] = tile_grid((h, w), tile_shape)
         if shift_solar_rotation_dx_large:
             plan["shift_large"] = self._shift_large_fov_displacement()
         return plan
 
+    def _bin_edges(self, bins, plan):
+        """(edges_small, edges_large) of a `bins` argument (see `host_plan`)."""
+        if isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_)):
+            if not 2 <= bins <= MAX_BINS:
+                raise ValueError(f"bins as a number must lie in [2, {MAX_BINS}]")
+            win = zero_lag_window(self.data_large.shape, self.data_small.shape, plan["slc_small_ref"],
+                                  plan["ratio_res_1"], plan["ratio_res_2"])
+            return quantile_edges(self.data_small, int(bins)), quantile_edges(self.data_large[win], int(bins))
+        if isinstance(bins, (bool, np.bool_, float, np.floating, str)):
+            raise ValueError("bins must be an integer or a pair (edges_small, edges_large)")
+        try:
+            es, el = bins
+        except (TypeError, ValueError):
+            raise ValueError("bins must be an integer or a pair (edges_small, edges_large)") from None
+        return check_edges(es, "edges_small"), check_edges(el, "edges_large")
+
     def find_best_parameters(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
-                             method="correlation", min_overlap=None, return_type="corr"):
+                             method="correlation", min_overlap=None, return_type="corr", bins=None):
         """alignment_pixels.py:57-84: correlation cube [len(lag_dx), len(lag_dy), len(lag_drot)], float64.
-        method: "correlation" (best = maximum) or "residus_masked" (best = minimum).  `self.last_counts`: the samples
+        method: "correlation" (best = maximum), "residus_masked" (best = minimum) or "mutual_information" (best =
+        maximum; `bins` as `host_plan` takes it).  `self.last_counts`: the samples
         behind every entry, shaped like the cube (before `min_overlap`).  min_overlap: None, a count >= 1 or a fraction
         in (0, 1) of the sweep's largest count; entries of fewer samples become NaN, ValueError when none is left.
         return_type: "corr" (the cube) or "PixelAlignmentResults"."""
         if return_type not in _RETURN_TYPES:
             raise ValueError(f"return_type must be one of {_RETURN_TYPES}")
-        plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap)
+        plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
+                              bins=bins)
         self.lag_dx, self.lag_dy, self.lag_drot, self.unit_rot = lag_dx, lag_dy, lag_drot, unit_rot
         self.ratio_res_1, self.ratio_res_2 = plan["ratio_res_1"], plan["ratio_res_2"]
         l, (h, w) = plan["slc_small_ref"], self.data_small.shape
@@ -185,7 +255,7 @@ class AlignmentPixels:
 
     def find_local_shifts(self, lag_dx, lag_dy, lag_drot=(0.0,), tile_shape=None, unit_rot="degree",
                           shift_solar_rotation_dx_large=False, method="correlation", min_overlap=None, min_fill=0.5,
-                          sub_lag=True):
+                          sub_lag=True, bins=None):
         """The local shift field: the small image is cut into tiles of `tile_shape` = (rows, columns) pixels (the last
         ones ragged) and every tile gets the lag cube of `find_best_parameters` on its own rectangle -- a rotated plane
         is still rotated about the whole image's centre -- with its sample counts, best entry and sub-lag fit.  Returns a
@@ -193,7 +263,7 @@ class AlignmentPixels:
         if tile_shape is None:
             raise ValueError("tile_shape = (rows, columns) is needed")
         plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
-                              tile_shape=tile_shape)
+                              tile_shape=tile_shape, bins=bins)
         hnd = _lib.shared_handle(-1 if self.device is None else self.device)
         hnd.pixels_set_large(self.data_large)
         hnd.pixels_set_small(self.data_small)

@@ -1,9 +1,9 @@
 """
 `LocalShiftField` -- what `AlignmentPixels.find_local_shifts` returns: the small image cut into tiles, and per tile the
 cube of the integer pixel-lag sweep on the tile's own rectangle (`corr[n_ty, n_tx, n_dx, n_dy, n_rot]`), the sample
-count behind every entry (`n_samples`, taken before `min_overlap`), the best entry (maximum of a correlation, minimum of
-`residus_masked`) and its sub-lag position -- the one Gaussian fit `PixelAlignmentResults` runs
-(`hdrshift.alignment_results.gaussian_sub_lag`), on the tile's (dx, dy) plane at its best rotation, the best entry
+count behind every entry (`n_samples`, taken before `min_overlap`), the best entry (maximum of a correlation or of
+`mutual_information`, minimum of `residus_masked`) and its sub-lag position -- the one Gaussian fit
+`PixelAlignmentResults` runs (`hdrshift.alignment_results.gaussian_sub_lag`), on the tile's (dx, dy) plane at its best rotation, the best entry
 itself where the fit cannot run or fails.
 
 A tile is `valid` when its largest count reaches `min_fill` times its pixel count and a finite entry is left after

@@ -1,8 +1,8 @@
 """
 `PixelAlignmentResults` -- what `AlignmentPixels.find_best_parameters(..., return_type="PixelAlignmentResults")` returns:
 the cube of the integer pixel-lag sweep with its lag axes, the sample count behind every entry, the best entry
-(maximum of a correlation, minimum of `residus_masked`) and its sub-lag position on the (dx, dy) plane of the best
-rotation -- the Gaussian fit `hdrshift.AlignmentResults` runs (`hdrshift.alignment_results.gaussian_sub_lag`: quirk Q13's
+(maximum of a correlation or of `mutual_information`, minimum of `residus_masked`) and its sub-lag position on the
+(dx, dy) plane of the best rotation -- the Gaussian fit `hdrshift.AlignmentResults` runs (`hdrshift.alignment_results.gaussian_sub_lag`: quirk Q13's
 neighbours, start, bounds, native / scipy, the flipped rescaled plane for a minimum, the fall-back to the best entry).
 The shift goes into a header through `align_pixels_shift`, which takes fractional pixels; the best rotation is
 reported (`drot`), not written: `align_pixels_shift` has no rotation, as in the reference.
@@ -17,7 +17,7 @@ from ..hdrshift.alignment_results import gaussian_sub_lag
 from ..utils import fits_io
 from .alignment_pixels import align_pixels_shift, large_fov_centre, set_pixels_shift_cards
 
-_BEST = {"correlation": "max", "residus_masked": "min"}
+_BEST = {"correlation": "max", "residus_masked": "min", "mutual_information": "max"}
 
 
 class PixelAlignmentResults:

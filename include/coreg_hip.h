@@ -43,6 +43,10 @@ extern "C" {
  * bit for bit to COREG_METHOD_RESIDUS wherever every grid point overlaps.  Never re-evaluated ("refine"), like residus.
  * Meant to be read with the per-lag sample counts (coreg_last_counts). */
 #define COREG_METHOD_RESIDUS_MASKED 2
+/* Mutual information of the joint histogram of the two images over given bins, in nats; best entry = maximum.  A score of
+ * the integer pixel-lag sweep only (coreg_pixels_set_bins, coreg_pixels_sweep_method, coreg_pixels_sweep_tiles below); the
+ * header-shift sweeps refuse it like any unknown method. */
+#define COREG_METHOD_MUTUAL_INFORMATION 3
 
 /* CDELT lag semantics */
 #define COREG_CDELT_INTENDED 0  /* CDELTi += d, PC rebuilt with the new lambda (utils/Util.py:199-215) */
@@ -547,8 +551,15 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  * (pxlshift/c_correlate.py:51-61), NaN for an empty or flat overlap.  A second score, COREG_METHOD_RESIDUS_MASKED: with a
  * the small image's pixel and b the sub-resolved large image's (the reference, as on the header-shift paths),
  * np.std(d[isfinite(a) & isfinite(b)]) of d = (b - a) / sqrt(b), best entry = minimum; NaN when no point is kept or a kept
- * term is not finite (b <= 0), 0.0 for one kept point.  Two deterministic passes per score (csrc/kernels_pixels.hpp);
- * the result of a lag does not depend on the other lags of the call.  All calls run on the handle's stream and return
+ * term is not finite (b <= 0), 0.0 for one kept point.  Two deterministic passes per score (csrc/kernels_pixels.hpp).
+ * A third score, COREG_METHOD_MUTUAL_INFORMATION, for images whose intensities are not linearly related: over the pairs
+ * with neither a nor b NaN (an infinite pixel is kept), bin(v) = the number of edges e <= v of the image's own edge list
+ * (np.searchsorted(edges, v, side="right"): comparisons only), n_ij the count of pairs in cell (bin(a), bin(b)), r_i, c_j
+ * and n its row sums, column sums and total: MI = sum over n_ij > 0 of (n_ij / n) log((n_ij n) / (r_i c_j)), float64,
+ * natural logarithm (nats), the terms of a row added in the order of j and the rows in the order of i (csrc/pixels_bins.hpp);
+ * best entry = maximum; NaN for n = 0, 0.0 when the pairs fill one row or one column; the count of an entry is n.  One
+ * pass, integer histograms in LDS (csrc/kernels_pixels_mi.hpp).
+ * The result of a lag does not depend on the other lags of the call.  All calls run on the handle's stream and return
  * with their work complete as far as the caller's memory is concerned.
  *   coreg_pixels_set_large / _set_small  host pixels [ny][nx], dtype COREG_F32 / COREG_F64; kept as float64
  *   coreg_pixels_shift_large             alignment_pixels.py:86-107 on the resident large image, at file resolution: an
@@ -558,9 +569,17 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  *                                        (checked for every lag before any GPU work)
  *   coreg_pixels_sweep_method            the same with the score chosen: COREG_METHOD_CORRELATION (what coreg_pixels_sweep
  *                                        runs) or COREG_METHOD_RESIDUS_MASKED; COREG_METHOD_RESIDUS is COREG_ENOTIMPL (the
- *                                        reference's pxlshift has no such score), any other value COREG_EINVAL
+ *                                        reference's pxlshift has no such score), any other value COREG_EINVAL;
+ *                                        COREG_METHOD_MUTUAL_INFORMATION once coreg_pixels_set_bins has been called,
+ *                                        COREG_ESTATE before
+ *   coreg_pixels_set_bins                the edge lists of COREG_METHOD_MUTUAL_INFORMATION: edges_small[n_small] for the
+ *                                        small image's pixels, edges_large[n_large] for the sub-resolved large image's;
+ *                                        each 1 to 31 entries, finite, strictly increasing (n + 1 bins), else COREG_EINVAL
+ *                                        and the lists set before stay.  State of the handle: they hold for every later
+ *                                        sweep until set again, whatever images are set
  *   coreg_pixels_last_counts             dst[n_dx][n_dy][n_rot] (host memory), the samples behind every entry of the last
- *                                        sweep: the kept pixels for the correlation, the finite terms for residus_masked.
+ *                                        sweep: the kept pixels for the correlation, the finite terms for residus_masked,
+ *                                        the pairs in the histogram for mutual information.
  *                                        COREG_ESTATE before a sweep and once coreg_pixels_set_large / _set_small /
  *                                        _shift_large has changed an image
  *   coreg_pixels_sweep_tiles             the local shift field: the small image is cut into tiles of tile_ny x tile_nx pixels
@@ -580,7 +599,8 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  *                                        [h + max dy - min dy][w + max dx - min dx] from (l0 + min dy, l1 + min dx) on
  *   coreg_pixels_get_rotated             plane k [h][w] of the last sweep
  *   coreg_pixels_last_timing             ms[3]: preparation (box + planes), first pass, second pass of the last sweep,
- *                                        whichever score it ran (HIP events)
+ *                                        whichever score it ran (HIP events); mutual information has one pass, the first:
+ *                                        the third figure is the time between two events with nothing between them
  *   coreg_pixels_destretch               the resample of a cube by a local shift field (pxlshift.LocalShiftField.destretch):
  *                                        see the rule below.  cube and out: host memory [n_planes][ny][nx] of dtype
  *                                        COREG_F32 / COREG_F64, out in the type and shape of cube; displacement: NULL or
@@ -621,6 +641,8 @@ int coreg_pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t 
 int coreg_pixels_shift_large(coreg_handle* h, double dx, double dy);
 int coreg_pixels_sweep(coreg_handle* h, const coreg_pixels_plan* plan, double* corr_out);
 int coreg_pixels_sweep_method(coreg_handle* h, const coreg_pixels_plan* plan, int method, double* out);
+int coreg_pixels_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small, const double* edges_large,
+                          int32_t n_large);
 int coreg_pixels_last_counts(coreg_handle* h, double* dst);
 int coreg_pixels_sweep_tiles(coreg_handle* h, const coreg_pixels_plan* plan, int method, int32_t tile_ny, int32_t tile_nx,
                              double* out);
