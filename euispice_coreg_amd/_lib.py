@@ -305,6 +305,9 @@ SYMBOLS = [
     ("coreg_pixels_last_counts", C.c_int, [_P, _P]),
     ("coreg_pixels_sweep_tiles", C.c_int, [_P, C.POINTER(PixelsPlan), C.c_int, C.c_int32, C.c_int32, _P]),
     ("coreg_pixels_last_tile_counts", C.c_int, [_P, _P]),
+    ("coreg_pixels_sweep_windows", C.c_int,
+     [_P, C.POINTER(PixelsPlan), C.c_int, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
+    ("coreg_pixels_last_tile_weights", C.c_int, [_P, _P]),
     ("coreg_pixels_get_large_box", C.c_int, [_P, _P]),
     ("coreg_pixels_get_rotated", C.c_int, [_P, C.c_int32, _P]),
     ("coreg_pixels_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
@@ -747,7 +750,7 @@ class CoregHandle(_ImageIntake):
         el = np.ascontiguousarray(edges_large, dtype=np.float64).ravel()
         self._chk(self._lib.coreg_pixels_set_bins(self._h, es.ctypes.data, len(es), el.ctypes.data, len(el)))
 
-    def _pixels_sweep(self, plan, method, tile_shape):
+    def _pixels_sweep(self, plan, method, tile_shape, tile_step=None, window=None):
         if int(method) == METHOD_MUTUAL_INFORMATION and plan.get("bins") is not None:
             self.pixels_set_bins(*plan["bins"])
         dx = np.ascontiguousarray(plan["lag_dx"], dtype=np.int32)
@@ -765,10 +768,28 @@ class CoregHandle(_ImageIntake):
             # (a tile shape the library refuses gives no grid: nothing is allocated for it)
             th, tw = int(tile_shape[0]), int(tile_shape[1])
             h, w = (int(v) for v in plan["small_shape"])
-            ok = 1 <= th <= h and 1 <= tw <= w and -(-h // th) * -(-w // tw) * len(rot) <= 65535
-            grid = (-(-h // th), -(-w // tw)) if ok else (0, 0)
-            out = np.empty(grid + (len(dx), len(dy), len(rot)), dtype=np.float64)
-            rc = self._lib.coreg_pixels_sweep_tiles(self._h, C.byref(p), int(method), th, tw, out.ctypes.data)
+            if tile_step is None and window is None:
+                ok = 1 <= th <= h and 1 <= tw <= w and -(-h // th) * -(-w // tw) * len(rot) <= 65535
+                grid = (-(-h // th), -(-w // tw)) if ok else (0, 0)
+                out = np.empty(grid + (len(dx), len(dy), len(rot)), dtype=np.float64)
+                rc = self._lib.coreg_pixels_sweep_tiles(self._h, C.byref(p), int(method), th, tw, out.ctypes.data)
+            else:
+                sy, sx = (th, tw) if tile_step is None else (int(tile_step[0]), int(tile_step[1]))
+                ok = 1 <= th <= h and 1 <= tw <= w and 1 <= sy <= th and 1 <= sx <= tw
+                grid = (-(-(h - th) // sy) + 1, -(-(w - tw) // sx) + 1) if ok else (0, 0)
+                if grid[0] * grid[1] * len(rot) > 65535:
+                    grid = (0, 0)
+                wy = wx = None
+                if window is not None:
+                    # (tables of another length than the tile are the caller's error: the library reads th and tw entries)
+                    wy = np.ascontiguousarray(window[0], dtype=np.float64)
+                    wx = np.ascontiguousarray(window[1], dtype=np.float64)
+                    if wy.shape != (th,) or wx.shape != (tw,):
+                        raise ValueError("the weight tables must hold tile rows and tile columns entries")
+                out = np.empty(grid + (len(dx), len(dy), len(rot)), dtype=np.float64)
+                rc = self._lib.coreg_pixels_sweep_windows(self._h, C.byref(p), int(method), th, tw, sy, sx,
+                                                          None if wy is None else wy.ctypes.data,
+                                                          None if wx is None else wx.ctypes.data, out.ctypes.data)
         if rc == COREG_EINVAL:
             msg = self._lib.coreg_last_error(self._h).decode("utf-8", "replace")
             if msg.startswith("too large shift"):
@@ -780,8 +801,20 @@ class CoregHandle(_ImageIntake):
         return self._pixels_sweep(plan, method, None)
 
     def pixels_sweep_tiles(self, plan, method=METHOD_CORRELATION, tile_shape=None):
-        """The cube of every tile, [n_ty, n_tx, n_dx, n_dy, n_rot]; tile_shape: (rows, columns), default the plan's."""
-        return self._pixels_sweep(plan, method, plan["tile_shape"] if tile_shape is None else tile_shape)
+        """The cube of every tile, [n_ty, n_tx, n_dx, n_dy, n_rot]; tile_shape: (rows, columns), default the plan's.  A plan
+        whose `tile_step` is not its tile shape, or that holds weight tables (`window`), goes to
+        coreg_pixels_sweep_windows; any other is the coreg_pixels_sweep_tiles call it has always been."""
+        ts = plan["tile_shape"] if tile_shape is None else tile_shape
+        step, window = plan.get("tile_step"), plan.get("window")
+        if step is not None and tuple(int(v) for v in step) == tuple(int(v) for v in plan["tile_shape"]):
+            step = None
+        return self._pixels_sweep(plan, method, ts, step, window)
+
+    def pixels_sweep_windows(self, plan, method=METHOD_CORRELATION, tile_shape=None, tile_step=None, window=None):
+        """coreg_pixels_sweep_windows with every argument given: tile_shape and tile_step (rows, columns), default the
+        plan's shape and the shape itself; window: None or the weight tables (wy, wx)."""
+        ts = plan["tile_shape"] if tile_shape is None else tile_shape
+        return self._pixels_sweep(plan, method, ts, ts if tile_step is None else tile_step, window)
 
     def pixels_last_counts(self, shape):
         """Per-lag sample counts of the last pixel-lag sweep, shaped like its cube (float64)."""
@@ -793,6 +826,13 @@ class CoregHandle(_ImageIntake):
         """The same of the last tiled sweep, shaped like its cubes [n_ty, n_tx, n_dx, n_dy, n_rot]."""
         out = np.empty(shape, dtype=np.float64)
         self._chk(self._lib.coreg_pixels_last_tile_counts(self._h, out.ctypes.data))
+        return out
+
+    def pixels_last_tile_weights(self, shape):
+        """The sums of weights W behind every entry of the last tiled sweep, shaped like its cubes; COREG_ESTATE unless
+        that sweep was apodized."""
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self._lib.coreg_pixels_last_tile_weights(self._h, out.ctypes.data))
         return out
 
     def pixels_get_large_box(self, shape):

@@ -50,6 +50,17 @@ int coreg_pixels_last_tile_counts(coreg_handle* h, double* dst) {
     return pixels_last_tile_counts(h, dst);
 }
 
+int coreg_pixels_sweep_windows(coreg_handle* h, const coreg_pixels_plan* plan, int method, int32_t tile_ny, int32_t tile_nx,
+                               int32_t step_ny, int32_t step_nx, const double* wy, const double* wx, double* out) {
+    if (!h) return COREG_EINVAL;
+    return pixels_sweep_windows(h, plan, method, tile_ny, tile_nx, step_ny, step_nx, wy, wx, out);
+}
+
+int coreg_pixels_last_tile_weights(coreg_handle* h, double* dst) {
+    if (!h) return COREG_EINVAL;
+    return pixels_last_tile_weights(h, dst);
+}
+
 int coreg_pixels_get_large_box(coreg_handle* h, double* out) {
     if (!h) return COREG_EINVAL;
     return pixels_get_large_box(h, out);

@@ -4,11 +4,12 @@
 #pragma once
 
 struct PixelsState {
-    DevBuf large, large_tmp, small, box, planes, sums, plan, corr, counts;
+    DevBuf large, large_tmp, small, box, planes, sums, plan, corr, counts, weights;
     int lW = 0, lH = 0, sW = 0, sH = 0;
     int bW = 0, bH = 0, n_rot = 0;  // what the last sweep left in `box` / `planes`
     long long n_counts = 0;         // ... and in `counts`: lags of the last untiled sweep, 0 once an image has changed
     long long n_tile_counts = 0;    //     or a tiled sweep has run; tiles x lags of the last tiled sweep, likewise
+    long long n_tile_weights = 0;   // ... and in `weights`: windows x lags of the last sweep when it was apodized, else 0
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
     // coreg_pixels_destretch: buffers, events and time of its own (the sweep's images, counts and events are not touched)
@@ -47,7 +48,7 @@ void pixels_release(coreg_handle* h) {
         g_pixels.erase(it);
     }
     DevBuf* bufs[] = {&st->large, &st->large_tmp, &st->small, &st->box, &st->planes, &st->sums, &st->plan, &st->corr,
-                      &st->counts, &st->ds_src, &st->ds_dst, &st->ds_disp, &st->ds_nodes};
+                      &st->counts, &st->weights, &st->ds_src, &st->ds_dst, &st->ds_disp, &st->ds_nodes};
     for (DevBuf* b : bufs) b->release();
     for (hipEvent_t e : st->ev)
         if (e) (void)hipEventDestroy(e);
@@ -93,7 +94,7 @@ int pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->bW = st->bH = 0;  // (the box of the last sweep is no longer this image's)
-    st->n_counts = st->n_tile_counts = 0;
+    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
     return pixels_upload(h, st->large, img, dtype, ny, nx, &st->lW, &st->lH);
 }
 
@@ -101,7 +102,7 @@ int pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->n_rot = 0;
-    st->n_counts = st->n_tile_counts = 0;
+    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
     return pixels_upload(h, st->small, img, dtype, ny, nx, &st->sW, &st->sH);
 }
 
@@ -112,7 +113,7 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     if (!(dx == dx) || !(dy == dy)) return fail(h, COREG_EINVAL, "pixels: the displacement is not a number");
     RETCHK(bind_device(h));
     st->bW = st->bH = 0;
-    st->n_counts = st->n_tile_counts = 0;
+    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
     const size_t n = (size_t)st->lW * st->lH;
     HIPCHK(st->large_tmp.reserve(n * sizeof(double)));
     PixResample a = {};
@@ -142,9 +143,9 @@ int pixels_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small,
 }
 
 template <int PASS>
-static void pixels_launch_pass(coreg_handle* h, const dim3& grid, const PixSweep& s, const PixTiles* t) {
+static void pixels_launch_pass(coreg_handle* h, const dim3& grid, const PixSweep& s, const PixTiles* t, const PixStep& step) {
     if (t)
-        hipLaunchKernelGGL(k_pixels_sweep_tiles<PASS>, grid, dim3(kPixThreads), 0, h->stream, s, *t);
+        hipLaunchKernelGGL(k_pixels_sweep_tiles<PASS>, grid, dim3(kPixThreads), 0, h->stream, s, *t, step);
     else
         hipLaunchKernelGGL(k_pixels_sweep<PASS>, grid, dim3(kPixThreads), 0, h->stream, s);
 }
@@ -157,24 +158,35 @@ static_assert((size_t)kPixG * kPixMaxBins * kPixMaxBins * sizeof(uint32_t) + 16 
 
 template <bool TILED, int THREADS>
 static int pixels_launch_mi(coreg_handle* h, const dim3& grid, size_t dyn, size_t* allowed, const PixSweep& s, const PixTiles& t,
-                            const PixBins& b) {
+                            const PixBins& b, const PixStep& step) {
     if (dyn > *allowed) {
         HIPCHK(hipFuncSetAttribute((const void*)k_pixels_mi<TILED, THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
         *allowed = dyn;
     }
-    hipLaunchKernelGGL((k_pixels_mi<TILED, THREADS>), grid, dim3(THREADS), dyn, h->stream, s, t, b);
+    hipLaunchKernelGGL((k_pixels_mi<TILED, THREADS>), grid, dim3(THREADS), dyn, h->stream, s, t, b, step);
     return COREG_OK;
 }
 
+// windows along an axis of n pixels: one when the window covers it, else ceil((n - size) / step) + 1 (step = size:
+// ceil(n / size), the disjoint tiles)
+static long long pixels_windows(int n, int size, int step) { return n <= size ? 1 : ((long long)n - size + step - 1) / step + 1; }
+
 // The untiled sweep (tile == nullptr: one cube [n_dx][n_dy][n_rot]) and the tiled one (tile = {rows, columns} of a tile:
-// one such cube per tile, [n_ty][n_tx] of them): the same validation, box, rotation planes, groups and events.
-static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int method, const int32_t* tile, double* corr_out) {
+// one such cube per tile, [n_ty][n_tx] of them): the same validation, box, rotation planes, groups and events.  step:
+// nullptr (the tile shape: disjoint tiles) or {rows, columns} between the origins of neighbouring tiles.  wy, wx: both
+// nullptr, or the weight tables [tile rows], [tile columns] of an apodized sweep (the correlation only: k_pixels_lct).
+static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int method, const int32_t* tile, const int32_t* step,
+                            const double* wy, const double* wx, double* corr_out) {
     if (method == COREG_METHOD_RESIDUS)
         return fail(h, COREG_ENOTIMPL, "pixels: method residus is not implemented (the reference's pxlshift has no such score); "
                                        "residus_masked is");
     if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS_MASKED && method != COREG_METHOD_MUTUAL_INFORMATION)
         return fail(h, COREG_EINVAL, "pixels: unknown method");
     const bool resid = method == COREG_METHOD_RESIDUS_MASKED, mi = method == COREG_METHOD_MUTUAL_INFORMATION;
+    const bool lct = wy || wx;
+    if (lct && (!wy || !wx || !tile)) return fail(h, COREG_EINVAL, "pixels: an apodized sweep needs both weight tables and a tile");
+    if (lct && method != COREG_METHOD_CORRELATION)
+        return fail(h, COREG_EINVAL, "pixels: weight tables belong to the correlation (no weighted residus_masked or histogram)");
     PixelsState* st = pixels_state(h, false);
     if (mi && (!st || st->edges_small.empty() || st->edges_large.empty()))
         return fail(h, COREG_ESTATE, "pixels: mutual information needs its bins (coreg_pixels_set_bins)");
@@ -188,14 +200,38 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
     const long long n_lag = (long long)pl->n_dx * pl->n_dy * pl->n_rot;
     if (n_lag > (1ll << 28)) return fail(h, COREG_EINVAL, "pixels: too many lags");
     PixTiles tl = {};
+    PixStep ts = {0, 0};
     long long n_tiles = 1;
     if (tile) {
         if (tile[0] < 1 || tile[0] > hh || tile[1] < 1 || tile[1] > w)
             return fail(h, COREG_EINVAL, "pixels: the tile shape must lie within [1, h] x [1, w] of the small image");
         tl.th = tile[0];
         tl.tw = tile[1];
-        tl.n_tx = (w + tl.tw - 1) / tl.tw;
-        n_tiles = (long long)((hh + tl.th - 1) / tl.th) * tl.n_tx;
+        if (step) {
+            if (step[0] < 1 || step[0] > tl.th || step[1] < 1 || step[1] > tl.tw)
+                return fail(h, COREG_EINVAL, "pixels: the tile step must lie within [1, tile rows] x [1, tile columns]");
+            ts.sy = step[0];
+            ts.sx = step[1];
+        } else {
+            ts.sy = tl.th;
+            ts.sx = tl.tw;
+        }
+        if (lct) {
+            const double* tab[2] = {wy, wx};
+            const int len[2] = {tl.th, tl.tw};
+            for (int a = 0; a < 2; ++a) {
+                bool any = false;
+                for (int k = 0; k < len[a]; ++k) {
+                    if (!std::isfinite(tab[a][k]) || tab[a][k] < 0.0)
+                        return fail(h, COREG_EINVAL, "pixels: a weight is negative or not finite");
+                    any = any || tab[a][k] > 0.0;
+                }
+                if (!any) return fail(h, COREG_EINVAL, "pixels: a weight table without a positive entry");
+            }
+        }
+        const long long n_tx = pixels_windows(w, tl.tw, ts.sx);
+        n_tiles = pixels_windows(hh, tl.th, ts.sy) * n_tx;  // (either factor at most the axis: no overflow)
+        tl.n_tx = (int)n_tx;
         if (n_tiles * pl->n_rot > 65535) return fail(h, COREG_EINVAL, "pixels: more than 65535 rotation planes x tiles");
         if (n_tiles * n_lag > (1ll << 28)) return fail(h, COREG_EINVAL, "pixels: too many tiles x lags");
         tl.n_tiles = (int)n_tiles;
@@ -241,8 +277,11 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
     // (mutual information: the two edge lists behind them, on a multiple of 8 bytes)
     const size_t off_es = (off_dy + (size_t)pl->n_dy * sizeof(int) + 7) / 8 * 8;
     const size_t off_el = off_es + (mi ? st->edges_small.size() : 0) * sizeof(double);
+    // (an apodized sweep: the two weight tables there instead)
+    const size_t off_wx = off_es + (lct ? (size_t)tl.th : 0) * sizeof(double);
     std::vector<unsigned char> blob(mi ? off_el + st->edges_large.size() * sizeof(double)
-                                       : off_dy + (size_t)pl->n_dy * sizeof(int));
+                                    : lct ? off_wx + (size_t)tl.tw * sizeof(double)
+                                          : off_dy + (size_t)pl->n_dy * sizeof(int));
     std::memcpy(blob.data(), groups.data(), off_dx);
     std::memcpy(blob.data() + off_dx, pl->lag_dx, (size_t)pl->n_dx * sizeof(int));
     std::memcpy(blob.data() + off_dy, pl->lag_dy, (size_t)pl->n_dy * sizeof(int));
@@ -250,13 +289,18 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
         std::memcpy(blob.data() + off_es, st->edges_small.data(), st->edges_small.size() * sizeof(double));
         std::memcpy(blob.data() + off_el, st->edges_large.data(), st->edges_large.size() * sizeof(double));
     }
+    if (lct) {
+        std::memcpy(blob.data() + off_es, wy, (size_t)tl.th * sizeof(double));
+        std::memcpy(blob.data() + off_wx, wx, (size_t)tl.tw * sizeof(double));
+    }
     HIPCHK(st->plan.reserve(blob.size()));
     HIPCHK(st->box.reserve((size_t)bW * bH * sizeof(double)));
     HIPCHK(st->planes.reserve((size_t)w * hh * pl->n_rot * sizeof(double)));
-    if (!mi) HIPCHK(st->sums.reserve((size_t)n_out * 6 * sizeof(double)));
+    if (!mi) HIPCHK(st->sums.reserve((size_t)n_out * (lct ? 7 : 6) * sizeof(double)));
+    if (lct) HIPCHK(st->weights.reserve((size_t)n_out * sizeof(double)));
     HIPCHK(st->corr.reserve((size_t)n_out * sizeof(double)));
     HIPCHK(st->counts.reserve((size_t)n_out * sizeof(double)));
-    st->n_counts = st->n_tile_counts = 0;
+    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
     for (hipEvent_t& e : st->ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     st->timed = false;
@@ -334,10 +378,10 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
         const size_t dyn = (size_t)kPixG * (b.n_small + 1) * (b.n_large + 1) * sizeof(uint32_t);
         const bool wide = dyn > kPixMiWideBytes;
         size_t* allowed = &st->mi_lds[t ? 1 : 0][wide ? 1 : 0];
-        RETCHK(t ? (wide ? pixels_launch_mi<true, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b)
-                         : pixels_launch_mi<true, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b))
-                 : (wide ? pixels_launch_mi<false, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b)
-                         : pixels_launch_mi<false, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b)));
+        RETCHK(t ? (wide ? pixels_launch_mi<true, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b, ts)
+                         : pixels_launch_mi<true, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b, ts))
+                 : (wide ? pixels_launch_mi<false, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b, ts)
+                         : pixels_launch_mi<false, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b, ts)));
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(st->ev[2], h->stream));
         HIPCHK(hipEventRecord(st->ev[3], h->stream));
@@ -348,21 +392,46 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
         return COREG_OK;
     }
     double* sums0 = st->sums.as<double>();
+    if (lct) {
+        // the apodized windows: four sums, then three (csrc/kernels_pixels_lct.hpp), and a finalize step of their own
+        const PixWindow win = {(const double*)((const unsigned char*)st->plan.p + off_es),
+                               (const double*)((const unsigned char*)st->plan.p + off_wx)};
+        double* lsums1 = sums0 + 4 * n_out;
+        s.sums0 = nullptr;
+        s.sums = sums0;
+        hipLaunchKernelGGL(k_pixels_lct<0>, grid, dim3(kPixThreads), 0, h->stream, s, tl, ts, win);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(st->ev[2], h->stream));
+        s.sums0 = sums0;
+        s.sums = lsums1;
+        hipLaunchKernelGGL(k_pixels_lct<1>, grid, dim3(kPixThreads), 0, h->stream, s, tl, ts, win);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(st->ev[3], h->stream));
+        hipLaunchKernelGGL(k_pixels_lct_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads), (unsigned)n_tiles),
+                           dim3(kPixThreads), 0, h->stream, (const double*)sums0, (const double*)lsums1, pl->n_dx, pl->n_dy,
+                           pl->n_rot, st->corr.as<double>(), st->counts.as<double>(), st->weights.as<double>());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        st->timed = true;
+        st->n_tile_counts = st->n_tile_weights = n_out;
+        return COREG_OK;
+    }
     double* sums1 = sums0 + 3 * n_out;
     s.sums0 = nullptr;
     s.sums = sums0;
     if (resid)
-        pixels_launch_pass<kPixR0>(h, grid, s, t);
+        pixels_launch_pass<kPixR0>(h, grid, s, t, ts);
     else
-        pixels_launch_pass<0>(h, grid, s, t);
+        pixels_launch_pass<0>(h, grid, s, t, ts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[2], h->stream));
     s.sums0 = sums0;
     s.sums = sums1;
     if (resid)
-        pixels_launch_pass<kPixR1>(h, grid, s, t);
+        pixels_launch_pass<kPixR1>(h, grid, s, t, ts);
     else
-        pixels_launch_pass<1>(h, grid, s, t);
+        pixels_launch_pass<1>(h, grid, s, t, ts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[3], h->stream));
     hipLaunchKernelGGL(k_pixels_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads), (unsigned)n_tiles),
@@ -377,13 +446,22 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
 }
 
 int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, double* corr_out) {
-    return pixels_sweep_run(h, pl, method, nullptr, corr_out);
+    return pixels_sweep_run(h, pl, method, nullptr, nullptr, nullptr, nullptr, corr_out);
 }
 
 // out[n_ty][n_tx][n_dx][n_dy][n_rot]: the cube of every tile of tile_ny x tile_nx small-image pixels (the last ones ragged)
 int pixels_sweep_tiles(coreg_handle* h, const coreg_pixels_plan* pl, int method, int32_t tile_ny, int32_t tile_nx, double* out) {
     const int32_t tile[2] = {tile_ny, tile_nx};
-    return pixels_sweep_run(h, pl, method, tile, out);
+    return pixels_sweep_run(h, pl, method, tile, nullptr, nullptr, nullptr, out);
+}
+
+// The same on a grid of windows: their origins step_ny x step_nx apart (1 <= step <= tile: they overlap, n_ty = 1 when
+// h <= tile_ny, else ceil((h - tile_ny) / step_ny) + 1), and, with the tables wy[tile_ny], wx[tile_nx], every pixel weighted by
+// wy[row in the window] * wx[column in the window] (the correlation only)
+int pixels_sweep_windows(coreg_handle* h, const coreg_pixels_plan* pl, int method, int32_t tile_ny, int32_t tile_nx,
+                         int32_t step_ny, int32_t step_nx, const double* wy, const double* wx, double* out) {
+    const int32_t tile[2] = {tile_ny, tile_nx}, step[2] = {step_ny, step_nx};
+    return pixels_sweep_run(h, pl, method, tile, step, wy, wx, out);
 }
 
 int pixels_last_timing(coreg_handle* h, double* ms) {
@@ -433,6 +511,14 @@ int pixels_last_tile_counts(coreg_handle* h, double* out) {
     PixelsState* st = pixels_state(h, false);
     if (!st || st->n_tile_counts < 1) return fail(h, COREG_ESTATE, "pixels: no tiled sweep has run since the images were set");
     return pixels_read(h, st->counts.p, (size_t)st->n_tile_counts, out);
+}
+
+// the sums of weights W of the last tiled sweep when it was apodized, laid out like its cubes
+int pixels_last_tile_weights(coreg_handle* h, double* out) {
+    PixelsState* st = pixels_state(h, false);
+    if (!st || st->n_tile_weights < 1)
+        return fail(h, COREG_ESTATE, "pixels: the last sweep since the images were set was not an apodized one");
+    return pixels_read(h, st->weights.p, (size_t)st->n_tile_weights, out);
 }
 
 // The destretch of a cube [n_planes][ny][nx] by a local shift field (csrc/pixels_field.hpp, k_pixels_destretch): every

@@ -29,3 +29,4 @@
 #include "kernels_context.hpp"   // iterative-context sweep (per-lag synthetic rasters)
 #include "kernels_pixels.hpp"    // integer pixel-lag sweep (pxlshift): resample, two-pass sweep, finalize
 #include "kernels_pixels_mi.hpp" // ... its mutual-information score: joint histograms in LDS, one pass
+#include "kernels_pixels_lct.hpp" // ... its apodized windows: weighted Pearson sums, two passes

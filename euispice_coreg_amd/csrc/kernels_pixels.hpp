@@ -14,7 +14,8 @@
 //                             on the lag alone, not on the group it runs in
 //   k_pixels_sweep_tiles<PASS> the same four passes per tile of the small-image plane (the local shift field): one
 //                             workgroup per (group, dy, rotation plane x tile) walks the tile's rectangle alone; the body
-//                             is the one text of csrc/kernels_pixels_sweep_body.hpp, included in either kernel
+//                             is the one text of csrc/kernels_pixels_sweep_body.hpp, included in either kernel.  The
+//                             tiles may overlap: their origins are multiples of a step (PixStep), the tile shape or less
 //   k_pixels_finalize         correlation: float32-rounded numerator / sqrt(product of the centred squares), NaN for an
 //                             empty or flat overlap; residus_masked: sqrt(sum of squares / n), NaN for no finite term
 //                             or a poisoned one; either way the lag's sample count
@@ -112,16 +113,24 @@ struct PixSweep {
     int cw, bh;            // band: columns [c0, c0 + cw) x rows [r0, r0 + bh), cw * bh <= kPixTile, bh <= kPixBandRows
 };
 
-// The tile grid of k_pixels_sweep_tiles: tile (ty, tx) is rows [ty th, min(h, (ty + 1) th)) x columns [tx tw, min(w, (tx + 1) tw))
-// of every plane (a rotated plane is rotated about the whole image's centre; a tile is a rectangle of it)
+// The window grid of k_pixels_sweep_tiles: tile (ty, tx) is rows [ty sy, min(h, ty sy + th)) x columns [tx sx, min(w, tx sx + tw))
+// of every plane (a rotated plane is rotated about the whole image's centre; a tile is a rectangle of it).  (sy, sx) = (th,
+// tw): disjoint tiles; a smaller step: windows that overlap
 struct PixTiles {
     int th, tw, n_tx, n_tiles, n_rot;
+};
+
+// The step of the grid, 1 <= sy <= th, 1 <= sx <= tw: the last argument of the kernels that can be tiled, not a part of
+// PixTiles, so that the untiled k_pixels_mi finds its arguments where it found them before the step existed
+struct PixStep {
+    int sy, sx;
 };
 
 template <int PASS>
 __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
     constexpr bool TILED = false;
     const PixTiles t = {0, 0, 1, 1, 0};  // (never read: every use sits behind TILED)
+    const PixStep st = {0, 0};           // (likewise)
 #include "kernels_pixels_sweep_body.hpp"
 }
 
@@ -129,7 +138,7 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_sweep(PixSweep p) {
 // Sums [n_tiles][n_rot][n_dy][n_dx][3]; pass 1 / R1 centre about the tile's own means of pass 0 / R0.  The band (p.cw, p.bh)
 // is that of the nominal tile shape, one value for the launch; a tile's sums depend on the tile and the lag alone.
 template <int PASS>
-__global__ __launch_bounds__(kPixThreads) void k_pixels_sweep_tiles(PixSweep p, PixTiles t) {
+__global__ __launch_bounds__(kPixThreads) void k_pixels_sweep_tiles(PixSweep p, PixTiles t, PixStep st) {
     constexpr bool TILED = true;
 #include "kernels_pixels_sweep_body.hpp"
 }

@@ -14,6 +14,8 @@
 //                        fixed order of pixels_bins.hpp and stores corr and counts itself: no histogram goes to memory,
 //                        k_pixels_finalize is not involved.
 //                        A lag's result depends on the lag (and the tile) alone, not on its slot or group.
+//                        TILED: the tile's origin is (ty sy, tx sx) of the last argument, the step of the window grid
+//                        (csrc/kernels_pixels.hpp: PixStep; the tile shape itself for disjoint tiles).
 //
 // LDS: the histograms are dynamic, kPixG * na * nb * 4 bytes (na, nb the bin counts: 64 KiB at 32 x 32, 16 KiB at 16 x 16);
 // the staged bytes, edges, margins and row sums are static (about 13.5 KiB).
@@ -37,7 +39,7 @@ struct PixBins {
 };
 
 template <bool TILED, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_pixels_mi(PixSweep p, PixTiles t, PixBins b) {
+__global__ __launch_bounds__(THREADS) void k_pixels_mi(PixSweep p, PixTiles t, PixBins b, PixStep st) {
     extern __shared__ uint32_t lds_hist[];  // [na * nb][kPixG]
     __shared__ double lds_edges[2][kPixMaxEdges];
     __shared__ unsigned char lds_a[kPixTile];
@@ -51,8 +53,8 @@ __global__ __launch_bounds__(THREADS) void k_pixels_mi(PixSweep p, PixTiles t, P
     const int col_off = g.dx_min - p.min_dx;      // box column of the group's first window's first column
     const int tile = TILED ? (int)blockIdx.z - kr * t.n_tiles : 0;
     const int ty = TILED ? tile / t.n_tx : 0, tx = TILED ? tile - ty * t.n_tx : 0;
-    const int r_lo = TILED ? ty * t.th : 0, r_hi = TILED ? min(p.h, r_lo + t.th) : p.h;
-    const int c_lo = TILED ? tx * t.tw : 0, c_hi = TILED ? min(p.w, c_lo + t.tw) : p.w;
+    const int r_lo = TILED ? ty * st.sy : 0, r_hi = TILED ? min(p.h, r_lo + t.th) : p.h;
+    const int c_lo = TILED ? tx * st.sx : 0, c_hi = TILED ? min(p.w, c_lo + t.tw) : p.w;
     const double* plane = p.planes + (size_t)kr * p.w * p.h;
     const int na = b.n_small + 1, nb = b.n_large + 1, n_cells = na * nb;
 

@@ -1,11 +1,12 @@
 // The body of k_pixels_sweep<PASS> and of k_pixels_sweep_tiles<PASS> (csrc/kernels_pixels.hpp), included inside either
 // kernel -- not a header of its own: the text is shared, so that the untiled kernels keep, instruction for instruction,
 // the code they had before the tiled ones existed (a device function called from both does not leave them so).  In scope:
-// PASS, `constexpr bool TILED`, `PixSweep p`, `PixTiles t` (TILED = false: never read).
+// PASS, `constexpr bool TILED`, `PixSweep p`, `PixTiles t`, `PixStep st` (TILED = false: never read).
 //
 // The walk of one workgroup over rows [r_lo, r_hi) x columns [c_lo, c_hi) of its plane.  TILED = false: the whole plane of
-// blockIdx.z.  TILED = true: blockIdx.z = plane * n_tiles + tile, the bounds are the tile's, uniform over the workgroup, and
-// the sums go to the tile's own block [n_rot][n_dy][n_dx][3].
+// blockIdx.z.  TILED = true: blockIdx.z = plane * n_tiles + tile, the bounds are the tile's -- its origin (ty sy, tx sx), the
+// step of the window grid (the tile shape itself for disjoint tiles) -- uniform over the workgroup, and the sums go to the
+// tile's own block [n_rot][n_dy][n_dx][3].
     __shared__ double lds_a[kPixTile];
     constexpr bool RESID = PASS >= kPixR0;
     __shared__ double lds_b[(RESID ? 2 : 1) * kPixLdsB];  // residus passes: the roots of the box pixels behind them
@@ -18,8 +19,8 @@
     const int tile = TILED ? (int)blockIdx.z - kr * t.n_tiles : 0;
     const long long lag0 = (((long long)tile * (TILED ? t.n_rot : 0) + kr) * p.n_dy + jy) * p.n_dx + g.first;
     const int ty = TILED ? tile / t.n_tx : 0, tx = TILED ? tile - ty * t.n_tx : 0;
-    const int r_lo = TILED ? ty * t.th : 0, r_hi = TILED ? min(p.h, r_lo + t.th) : p.h;
-    const int c_lo = TILED ? tx * t.tw : 0, c_hi = TILED ? min(p.w, c_lo + t.tw) : p.w;
+    const int r_lo = TILED ? ty * st.sy : 0, r_hi = TILED ? min(p.h, r_lo + t.th) : p.h;
+    const int c_lo = TILED ? tx * st.sx : 0, c_hi = TILED ? min(p.w, c_lo + t.tw) : p.w;
     const double* plane = p.planes + (size_t)kr * p.w * p.h;
 
     int off[kPixG];

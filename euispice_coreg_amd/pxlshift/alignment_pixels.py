@@ -17,7 +17,9 @@ maximum, the count of an entry the pairs in its histogram (`quantile_edges`, `ch
 
 `find_local_shifts` (not in the reference either): the small image cut into tiles, one lag cube, count cube, best entry
 and sub-lag fit per tile (include/coreg_hip.h: coreg_pixels_sweep_tiles; local_shift_field.py) -- the drift across a
-raster whose columns were not taken at one pointing.
+raster whose columns were not taken at one pointing.  With `tile_step` the tiles become windows that slide by less than
+their size, with `apodization` every window is weighted by a smooth bell: local correlation tracking
+(coreg_pixels_sweep_windows).
 
 Differences from the reference, all deliberate:
   * a second `find_best_parameters` call starts from the file's pixels again (the reference sub-resolves the already
@@ -74,20 +76,89 @@ def zero_lag_window(large_shape, small_shape, origin, ratio1, ratio2):
     return tuple(out)
 
 
-def tile_grid(image_shape, tile_shape):
-    """(th, tw), (n_ty, n_tx) of the tiles of `tile_shape` = (rows, columns) on an image of `image_shape`: whole numbers,
-    1 <= th <= h, 1 <= tw <= w; the last tile of an axis is ragged when the shape does not divide it."""
+def _pair_of_integers(v, name):
     try:
-        th, tw = tile_shape
+        a, b = v
     except (TypeError, ValueError):
-        raise ValueError("tile_shape must be (rows, columns)") from None
-    for v in (th, tw):
-        if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)):
-            raise ValueError("tile_shape must hold two integers")
+        raise ValueError(f"{name} must be (rows, columns)") from None
+    for x in (a, b):
+        if isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)):
+            raise ValueError(f"{name} must hold two integers")
+    return int(a), int(b)
+
+
+def tile_grid(image_shape, tile_shape, tile_step=None):
+    """(th, tw), (n_ty, n_tx) of the tiles of `tile_shape` = (rows, columns) on an image of `image_shape`: whole numbers,
+    1 <= th <= h, 1 <= tw <= w; the last tile of an axis is ragged when the shape does not divide it.
+    tile_step = (sy, sx), 1 <= sy <= th, 1 <= sx <= tw (a larger step would leave gaps), default the tile shape: tile ty
+    covers rows [ty sy, min(h, ty sy + th)), and an axis holds one tile when h <= th, else ceil((h - th) / sy) + 1 -- every
+    pixel is covered, no tile lies inside its neighbour (`window_slices`)."""
+    th, tw = _pair_of_integers(tile_shape, "tile_shape")
     h, w = image_shape
     if not (1 <= th <= h and 1 <= tw <= w):
-        raise ValueError(f"tile_shape {(int(th), int(tw))} must lie within [1, {h}] x [1, {w}], the small image")
-    return (int(th), int(tw)), (-(-h // int(th)), -(-w // int(tw)))
+        raise ValueError(f"tile_shape {(th, tw)} must lie within [1, {h}] x [1, {w}], the small image")
+    if tile_step is None:
+        return (th, tw), (-(-h // th), -(-w // tw))
+    sy, sx = check_tile_step((th, tw), tile_step)
+    return (th, tw), tuple(1 if n <= t else -(-(n - t) // s) + 1 for n, t, s in ((h, th, sy), (w, tw, sx)))
+
+
+def check_tile_step(tile_shape, tile_step):
+    """(sy, sx) of a `tile_step` argument: None is the tile shape; else two whole numbers within [1, th] x [1, tw]."""
+    if tile_step is None:
+        return int(tile_shape[0]), int(tile_shape[1])
+    sy, sx = _pair_of_integers(tile_step, "tile_step")
+    if not (1 <= sy <= tile_shape[0] and 1 <= sx <= tile_shape[1]):
+        raise ValueError(f"tile_step {(sy, sx)} must lie within [1, {tile_shape[0]}] x [1, {tile_shape[1]}], the tile shape")
+    return sy, sx
+
+
+def window_slices(image_shape, tile_shape, tile_step=None):
+    """[n_ty][n_tx] of (row slice, column slice): the rectangles of `tile_grid`."""
+    (th, tw), (n_ty, n_tx) = tile_grid(image_shape, tile_shape, tile_step)
+    sy, sx = check_tile_step((th, tw), tile_step)
+    h, w = image_shape
+    return [[(slice(ty * sy, min(h, ty * sy + th)), slice(tx * sx, min(w, tx * sx + tw))) for tx in range(n_tx)]
+            for ty in range(n_ty)]
+
+
+def gaussian_window(n, sigma):
+    """The Gaussian weight table of `n` pixels about the centre (n - 1) / 2: exp(-0.5 ((r - (n - 1) / 2) / sigma)^2)."""
+    r = np.arange(n, dtype=np.float64)
+    return np.exp(-0.5 * ((r - (n - 1) / 2) / sigma) ** 2)
+
+
+def apodization_tables(apodization, tile_shape):
+    """(wy, wx), float64 tables of th and tw weights, of an `apodization` argument; None for None.  "gaussian": sigma =
+    (th / 4, tw / 4); a pair of positive finite numbers: (sigma_y, sigma_x) in pixels (`gaussian_window`); a pair of 1-D
+    arrays of th and tw entries, finite, >= 0, each with a positive entry: the tables themselves.  Pixel (r, c) of a
+    window has the weight wy[r] * wx[c]."""
+    if apodization is None:
+        return None
+    th, tw = tile_shape
+    err = ValueError('apodization must be None, "gaussian", a pair (sigma_y, sigma_x) of positive numbers or a pair of '
+                     f"tables of {th} and {tw} weights, finite, >= 0, each with a positive entry")
+    if isinstance(apodization, str):
+        if apodization != "gaussian":
+            raise err
+        apodization = (th / 4, tw / 4)
+    try:
+        ay, ax = apodization
+        ay, ax = np.asarray(ay, dtype=np.float64), np.asarray(ax, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise err from None
+    if any(isinstance(v, (bool, np.bool_)) for v in apodization):
+        raise err
+    if ay.ndim == 0 and ax.ndim == 0:
+        if not (np.isfinite(ay) and np.isfinite(ax) and ay > 0 and ax > 0):
+            raise err
+        return gaussian_window(th, float(ay)), gaussian_window(tw, float(ax))
+    if ay.shape != (th,) or ax.shape != (tw,):
+        raise err
+    for t in (ay, ax):
+        if not (np.all(np.isfinite(t)) and np.all(t >= 0) and np.any(t > 0)):
+            raise err
+    return np.ascontiguousarray(ay).copy(), np.ascontiguousarray(ax).copy()
 
 
 def _integer_lags(v, name):
@@ -148,13 +219,17 @@ class AlignmentPixels:
         return float(d1 / hl["CDELT1"]), 0.0
 
     def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
-                  method="correlation", min_overlap=None, tile_shape=None, bins=None) -> dict:
+                  method="correlation", min_overlap=None, tile_shape=None, bins=None, tile_step=None,
+                  apodization=None) -> dict:
         """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU); with
         `tile_shape` = (rows, columns), of a `find_local_shifts` call: the plan then holds the tile grid too.
         `bins` (method "mutual_information" only, ValueError with any other): an integer 2 <= B <= 32 (default 16) --
         `quantile_edges` of the small image and of the large image's pixels under the zero-lag window
         (`zero_lag_window`), so the edges do not depend on the lags -- or a pair (edges_small, edges_large) as
-        `check_edges` takes them; the plan holds the pair as `plan["bins"]`."""
+        `check_edges` takes them; the plan holds the pair as `plan["bins"]`.
+        `tile_step` (with `tile_shape`; `tile_grid`): the plan holds it next to the shape and the grid.  `apodization` (with
+        `tile_shape`, method "correlation" only, ValueError with any other; `apodization_tables`): the plan holds the two
+        weight tables as `plan["window"]` = (wy, wx), None without."""
         if method == MUTUAL_INFORMATION:
             method_code = _lib.METHOD_MUTUAL_INFORMATION
         else:
@@ -194,8 +269,15 @@ class AlignmentPixels:
                 "method_code": method_code, "min_overlap": min_overlap, "small_shape": (h, w)}
         if method == MUTUAL_INFORMATION:
             plan["bins"] = self._bin_edges(DEFAULT_BINS if bins is None else bins, plan)
-        if tile_shape is not None:
-            plan["tile_shape"], plan["tile_grid"] = tile_grid((h, w), tile_shape)
+        if tile_shape is None:
+            if tile_step is not None or apodization is not None:
+                raise ValueError("tile_step and apodization belong to a tile_shape")
+        else:
+            plan["tile_shape"], plan["tile_grid"] = tile_grid((h, w), tile_shape, tile_step)
+            plan["tile_step"] = check_tile_step(plan["tile_shape"], tile_step)
+            if apodization is not None and method != "correlation":
+                raise ValueError("apodization belongs to method='correlation' (no weighted residus_masked or histogram)")
+            plan["window"] = apodization_tables(apodization, plan["tile_shape"])
         if shift_solar_rotation_dx_large:
             plan["shift_large"] = self._shift_large_fov_displacement()
         return plan
@@ -255,15 +337,23 @@ class AlignmentPixels:
 
     def find_local_shifts(self, lag_dx, lag_dy, lag_drot=(0.0,), tile_shape=None, unit_rot="degree",
                           shift_solar_rotation_dx_large=False, method="correlation", min_overlap=None, min_fill=0.5,
-                          sub_lag=True, bins=None):
+                          sub_lag=True, bins=None, tile_step=None, apodization=None):
         """The local shift field: the small image is cut into tiles of `tile_shape` = (rows, columns) pixels (the last
         ones ragged) and every tile gets the lag cube of `find_best_parameters` on its own rectangle -- a rotated plane
         is still rotated about the whole image's centre -- with its sample counts, best entry and sub-lag fit.  Returns a
-        `LocalShiftField` (local_shift_field.py), which takes `min_overlap` (per tile), `min_fill` and `sub_lag`."""
+        `LocalShiftField` (local_shift_field.py), which takes `min_overlap` (per tile), `min_fill` and `sub_lag`.
+
+        tile_step = (sy, sx), 1 <= sy <= th, 1 <= sx <= tw: windows that slide by less than their size (`tile_grid`); the
+        default, the tile shape, is the disjoint tiles.  apodization (method "correlation" only): None, "gaussian" (sigma
+        = (th / 4, tw / 4)), (sigma_y, sigma_x) in pixels, or two tables of th and tw weights (`apodization_tables`):
+        pixel (r, c) of a window weighs wy[r] * wx[c] in the means and the three sums of its coefficient; a ragged
+        window uses the head of the tables (a bell cut off about the nominal centre; its `tile_centres` entry stays
+        the centre of the clipped rectangle).  The count of an entry stays the kept pixels, whatever their weight; the sum
+        of their weights is the field's `weight_sums`, and `min_fill` then compares weights, not pixels."""
         if tile_shape is None:
             raise ValueError("tile_shape = (rows, columns) is needed")
         plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
-                              tile_shape=tile_shape, bins=bins)
+                              tile_shape=tile_shape, bins=bins, tile_step=tile_step, apodization=apodization)
         hnd = _lib.shared_handle(-1 if self.device is None else self.device)
         hnd.pixels_set_large(self.data_large)
         hnd.pixels_set_small(self.data_small)
@@ -274,11 +364,13 @@ class AlignmentPixels:
         corr = hnd.pixels_sweep_tiles(plan, plan["method_code"])
         self.last_timing = hnd.pixels_last_timing()
         counts = hnd.pixels_last_tile_counts(corr.shape)
+        weights = None if plan["window"] is None else hnd.pixels_last_tile_weights(corr.shape)
         self._last_plan = plan
         from .local_shift_field import LocalShiftField
         return LocalShiftField(corr, counts, plan["lag_dx"], plan["lag_dy"], plan["lag_drot"], plan["tile_shape"],
                                self.data_small.shape, unit_rot=unit_rot, method=method, min_overlap=min_overlap,
-                               min_fill=min_fill, sub_lag=sub_lag)
+                               min_fill=min_fill, sub_lag=sub_lag, tile_step=plan["tile_step"], weight_sums=weights,
+                               window=plan["window"])
 
     # read-backs of the last call's device images (tests, inspection)
     def _large_box(self):

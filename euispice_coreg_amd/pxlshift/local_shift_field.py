@@ -11,6 +11,13 @@ A tile is `valid` when its largest count reaches `min_fill` times its pixel coun
 tile).  An invalid tile raises nothing: its shifts, score and rotation are NaN and its `best_index` is -1.  Only a field
 without any valid tile raises ValueError.
 
+With `tile_step` = (sy, sx) the tiles are windows whose origins lie a step apart, the tile shape or less
+(`alignment_pixels.tile_grid`): they overlap, and the field has a node per window.  With weight tables (`window`, the
+apodization of `find_local_shifts`) `weight_sums` holds the sum of the kept pixels' weights behind every entry; the count
+of an entry stays the kept pixels, and a tile is then valid when its largest weight sum reaches `min_fill` times the
+sum of the weights over its rectangle -- kept pixels in the corners of a bell do not make it valid.  A ragged window's
+weights are the head of the tables; its centre in `tile_centres` stays the centre of the clipped rectangle.
+
 From the valid tiles: `median_shift` and `scatter` (1.4826 x the median absolute deviation) of dx and dy -- an empirical
 error bar on a global shift -- and `drift()`, the least-squares planes of dx and dy over the tile centres: the drift
 across a raster.
@@ -28,7 +35,7 @@ import numpy as np
 
 from ..hdrshift.alignment import apply_min_overlap, min_overlap_floor
 from ..hdrshift.alignment_results import gaussian_sub_lag
-from .alignment_pixels import tile_grid
+from .alignment_pixels import check_tile_step, tile_grid, window_slices
 from .pixel_alignment_results import _BEST
 
 
@@ -40,7 +47,8 @@ MAX_ELEMENTS = 2 ** 31 - 1  # of one coreg_pixels_destretch call
 class LocalShiftField:
 
     def __init__(self, corr, n_samples, lag_dx, lag_dy, lag_drot, tile_shape, image_shape, unit_rot="degree",
-                 method="correlation", min_overlap=None, min_fill=0.5, sub_lag=True, fit=None):
+                 method="correlation", min_overlap=None, min_fill=0.5, sub_lag=True, fit=None, tile_step=None,
+                 weight_sums=None, window=None):
         if method not in _BEST:
             raise NotImplementedError
         fit = fit or os.environ.get("COREG_GAUSSIAN_FIT", "native")
@@ -54,15 +62,25 @@ class LocalShiftField:
         self.min_overlap, self.min_fill, self.sub_lag = min_overlap, float(min_fill), bool(sub_lag)
         self.lag_dx, self.lag_dy, self.lag_drot = (np.atleast_1d(np.asarray(v)) for v in (lag_dx, lag_dy, lag_drot))
         self.image_shape = (int(image_shape[0]), int(image_shape[1]))
-        self.tile_shape, grid = tile_grid(self.image_shape, tile_shape)
+        self.tile_shape, grid = tile_grid(self.image_shape, tile_shape, tile_step)
+        self.tile_step = check_tile_step(self.tile_shape, tile_step)
         corr, n_samples = np.asarray(corr, dtype=np.float64), np.asarray(n_samples, dtype=np.float64)
         if corr.shape != grid + (len(self.lag_dx), len(self.lag_dy), len(self.lag_drot)) or n_samples.shape != corr.shape:
             raise ValueError("corr and n_samples must be shaped [n_ty, n_tx, len(lag_dx), len(lag_dy), len(lag_drot)]")
         self.n_samples = n_samples
+        if (weight_sums is None) != (window is None):
+            raise ValueError("weight_sums and window (the weight tables) come together")
+        self.weight_sums = self.window = None
+        if window is not None:
+            if method != "correlation":
+                raise ValueError("apodization belongs to method='correlation'")
+            self.weight_sums = np.asarray(weight_sums, dtype=np.float64)
+            self.window = tuple(np.asarray(t, dtype=np.float64) for t in window)
+            if self.weight_sums.shape != corr.shape or tuple(t.shape for t in self.window) != tuple(
+                    (n,) for n in self.tile_shape):
+                raise ValueError("weight_sums must be shaped like corr, the weight tables like the tile shape")
         self.corr = np.full(corr.shape, np.nan)  # (after min_overlap; an emptied tile is all NaN)
-        (h, w), (th, tw) = self.image_shape, self.tile_shape
-        self.tile_slices = [[(slice(ty * th, min(h, (ty + 1) * th)), slice(tx * tw, min(w, (tx + 1) * tw)))
-                             for tx in range(grid[1])] for ty in range(grid[0])]
+        self.tile_slices = window_slices(self.image_shape, self.tile_shape, self.tile_step)
         # (x, y) of every tile's centre in small-image pixels
         self.tile_centres = np.array([[((c.start + c.stop - 1) / 2, (r.start + r.stop - 1) / 2) for r, c in row]
                                       for row in self.tile_slices], dtype=np.float64)
@@ -84,8 +102,12 @@ class LocalShiftField:
             return
         self.corr[ty, tx] = cube
         r, c = self.tile_slices[ty][tx]
-        n_pix = (r.stop - r.start) * (c.stop - c.start)
-        if not (np.isfinite(cube).any() and np.nanmax(counts) >= self.min_fill * n_pix):
+        if self.window is None:
+            filled = np.nanmax(counts) >= self.min_fill * ((r.stop - r.start) * (c.stop - c.start))
+        else:  # the weights the window holds against those of its rectangle (a ragged one: the head of the tables)
+            full = np.outer(self.window[0][:r.stop - r.start], self.window[1][:c.stop - c.start]).sum()
+            filled = np.nanmax(self.weight_sums[ty, tx]) >= self.min_fill * full
+        if not (np.isfinite(cube).any() and filled):
             return
         mi = np.unravel_index((np.nanargmin if self.best == "min" else np.nanargmax)(cube), cube.shape)
         pos = None
@@ -181,6 +203,9 @@ class LocalShiftField:
         = (u, v) of every output pixel."""
         if interpolation not in _INTERPOLATIONS:
             raise ValueError(f"interpolation must be one of {_INTERPOLATIONS}")
+        if interpolation == "nearest" and self.tile_step != self.tile_shape:
+            raise ValueError("interpolation='nearest' is the value of the pixel's tile: overlapping windows "
+                             "(tile_step != tile_shape) have none, use 'bilinear'")
         u, v = self.node_shifts(reference, fill)
         a = np.asarray(data)
         if a.dtype.kind != "f" or a.dtype.itemsize not in (4, 8):

@@ -595,6 +595,33 @@ int coreg_context_lag_headers(const coreg_wcs2d* hdr_target, const coreg_wcs2d* 
  *                                        sweep (over a lag they sum to the untiled count).  The two count calls answer for the
  *                                        last sweep only: COREG_ESTATE from this one after an untiled sweep or a changed
  *                                        image, from coreg_pixels_last_counts after a tiled sweep
+ *   coreg_pixels_sweep_windows           coreg_pixels_sweep_tiles on a grid of windows that may overlap, each optionally
+ *                                        weighted (local correlation tracking).  step_ny, step_nx: the rows and columns
+ *                                        between the origins of neighbouring windows, 1 <= step_ny <= tile_ny, 1 <= step_nx
+ *                                        <= tile_nx (a larger step would leave gaps).  Per axis of h pixels: n_ty = 1 when
+ *                                        h <= tile_ny, else ceil((h - tile_ny) / step_ny) + 1; window ty covers rows [ty
+ *                                        step_ny, min(h, ty step_ny + tile_ny)): every pixel is covered, the last window may
+ *                                        be ragged.  step = tile is coreg_pixels_sweep_tiles, bit for bit, and a window
+ *                                        that coincides with a disjoint tile has that tile's bits.  out[n_ty][n_tx][n_dx]
+ *                                        [n_dy][n_rot]; every method.
+ *                                        wy, wx: both NULL, or the weight tables wy[tile_ny], wx[tile_nx] of an apodized
+ *                                        sweep, COREG_METHOD_CORRELATION only: pixel (y, x) of the window at (r_lo, c_lo)
+ *                                        has the weight w = wy[y - r_lo] * wx[x - c_lo], one IEEE product (a ragged window
+ *                                        reads the head of the tables).  Over the kept pixels of the window (neither image
+ *                                        NaN): n = sum 1, W = sum w, am = sum w a / W, bm = sum w b / W, and
+ *                                        corr = (double)(float)(sum w (a - am)(b - bm)) / sqrt(sum w (a - am)^2 sum w (b - bm)^2),
+ *                                        NaN when W = 0 or a weighted variance is 0.  The count of an entry stays n, whatever
+ *                                        the weights.  Two passes of k_pixels_lct (csrc/kernels_pixels_lct.hpp), float64.
+ *                                        The library takes tables, not sigmas: a Gaussian is built by the caller.
+ *                                        COREG_EINVAL: a step outside [1, tile]; a table entry that is negative or not
+ *                                        finite, a table without a positive entry, one table without the other; tables
+ *                                        with another method; and the refusals of coreg_pixels_sweep_tiles, the limits
+ *                                        n_rot * n_windows <= 65535 and n_windows * n_dx * n_dy * n_rot <= 2^28 among them.
+ *                                        coreg_pixels_last_tile_counts and coreg_pixels_last_timing answer for this call
+ *                                        as for coreg_pixels_sweep_tiles
+ *   coreg_pixels_last_tile_weights       dst[n_ty][n_tx][n_dx][n_dy][n_rot], W behind every entry of the last sweep.
+ *                                        COREG_ESTATE unless the last sweep was an apodized one and no image has changed
+ *                                        since
  *   coreg_pixels_get_large_box           the part of the sub-resolved image the last sweep could read:
  *                                        [h + max dy - min dy][w + max dx - min dx] from (l0 + min dy, l1 + min dx) on
  *   coreg_pixels_get_rotated             plane k [h][w] of the last sweep
@@ -647,6 +674,10 @@ int coreg_pixels_last_counts(coreg_handle* h, double* dst);
 int coreg_pixels_sweep_tiles(coreg_handle* h, const coreg_pixels_plan* plan, int method, int32_t tile_ny, int32_t tile_nx,
                              double* out);
 int coreg_pixels_last_tile_counts(coreg_handle* h, double* dst);
+int coreg_pixels_sweep_windows(coreg_handle* h, const coreg_pixels_plan* plan, int method, int32_t tile_ny, int32_t tile_nx,
+                               int32_t step_ny, int32_t step_nx, const double* wy /* NULL or [tile_ny] */,
+                               const double* wx /* NULL or [tile_nx] */, double* out);
+int coreg_pixels_last_tile_weights(coreg_handle* h, double* dst);
 int coreg_pixels_get_large_box(coreg_handle* h, double* out);
 int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out);
 int coreg_pixels_last_timing(coreg_handle* h, double* ms);
