@@ -101,7 +101,7 @@ bool combo_slots(const SweepCall& call, const coreg_wcs2d& small, const Plan& pl
     call.d.inner(c, &i3, &i4, &i5);
     if (shift_header(small, 0.0, 0.0, call.lags->cdelt1[i3], call.lags->cdelt2[i4], call.lags->crota[i5], call.sem, hc))
         return false;
-    build_slots(call.d, c, call.lag_begin, call.lag_end, plan.sw, plan.sh, slots);
+    build_slots(call.d, c, call.lag_begin, call.lag_end, plan.rects, slots);
     return slots->n_batches > 0;
 }
 

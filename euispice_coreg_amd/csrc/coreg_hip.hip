@@ -32,6 +32,7 @@ using namespace coreg;
 
 #define COREG_VERSION "0.1.0"
 
+#include "lag_plan.hpp"          // lag patches of a sweep and their slot layout (no HIP in it)
 #include "host_state.hpp"        // buffers, FixLaunch, coreg_handle
 #include "host_upload.hpp"       // uploads, FITS decode, reference crop
 #include "host_plan.hpp"         // lag batching, tiles, groups, precompute

@@ -26,19 +26,13 @@ void parallel_for(long long n, unsigned max_threads, long long grain, Fn fn) {
     for (auto& x : th) x.join();
 }
 
-// ---- lag batching ---------------------------------------------------------------------------------------------
-struct LagDims {
-    int n1, n2, n3, n4, n5;
-    long long nc;  // (cdelt1, cdelt2, crota) combinations this sweep covers: n3*n4*n5, or the "combo_begin/_end" range
-    long long c0;  // first of them in the lag set's inner C-order index ((i3 * n4 + i4) * n5 + i5)
-    long long total() const { return (long long)n1 * n2 * nc; }
-    void inner(long long c, int* i3, int* i4, int* i5) const {  // c in [0, nc)
-        const long long g = c + c0;
-        *i5 = (int)(g % n5);
-        *i4 = (int)((g / n5) % n4);
-        *i3 = (int)(g / ((long long)n5 * n4));
-    }
-};
+// ---- lag batching (lag_plan.hpp: the planner and the slot layout, plain C++) ------------------------------------------
+using lag_plan::Geometry;
+using lag_plan::LagDims;
+using lag_plan::Plan;
+using lag_plan::SlotList;
+using lag_plan::build_slots;
+static_assert(lag_plan::kSlots == kBlock && lag_plan::kWaveLags == 64, "lag_plan.hpp restates the kernels' constants");
 
 // The one-shot combination range ("combo_begin" / "combo_end") belongs to THE NEXT sweep call, whatever becomes of it: the
 // entry points take it off the handle before any validation (a call that failed early used to leave it armed
@@ -99,68 +93,38 @@ static int check_grid(coreg_handle* h, const coreg_carr_grid* g) {
     return why ? fail(h, COREG_EINVAL, why) : COREG_OK;
 }
 
-// Local pixel-space geometry of a sweep (host estimates; they steer the plan, never the results):
-// small-image pixels per grid step (d?_di, d?_dj) and per CRVAL1 / CRVAL2 lag step (a?, b?).
-struct Geometry {
-    double dx_di = 1, dx_dj = 0, dy_di = 0, dy_dj = 1;
-    double ax = 0, ay = 0, bx = 0, by = 0;
-};
-struct Plan {
-    int tile_w = 32;      // grid tile = tile_w x (kTilePts / tile_w) points
-    int sw = 16, sh = 16; // lag patch of a workgroup: sw CRVAL1 lags x sh CRVAL2 lags (sw * sh <= 256)
-    double window = 0;    // estimated LDS window (elements)
-    double win_w = 0, win_h = 0;  // its estimated width / height in pixels
-};
-
-// Tile shape and lag patch chosen together: fewest lag batches (= least padded lane slots) among the combinations
-// whose LDS window (tile extent (+) patch extent, in pixels) fits; ties -> smaller window.  m1 x n2 = lag plane.
+// Tile shape and lag patches of a sweep (lag_plan::plan_patches) under the handle's options.  m1 x n2 = lag plane.
 Plan choose_plan(coreg_handle* h, const Geometry& g, int m1, int n2, long long lds_elems) {
-    Plan best, fallback;
-    double best_cost = std::numeric_limits<double>::max(), fb_win = std::numeric_limits<double>::max();
-    const int sw_hi = h->opt_patch_w > 0 ? std::min<int>((int)h->opt_patch_w, kBlock) : kBlock;
-    for (int tw = 4; tw <= 256; tw *= 2) {
-        if (h->opt_tile_w > 0 && tw != h->opt_tile_w) continue;
-        const int th = kTilePts / tw;
-        if (th < 1) continue;
-        const double tex = tw * std::fabs(g.dx_di) + th * std::fabs(g.dx_dj);
-        const double tey = tw * std::fabs(g.dy_di) + th * std::fabs(g.dy_dj);
-        for (int sw = 1; sw <= std::min(m1, sw_hi); ++sw) {
-            int sh = std::min(n2, kBlock / sw);
-            if (sh < 1) break;
-            const int cols = (m1 + sw - 1) / sw, rows = (n2 + sh - 1) / sh;
-            sh = (n2 + rows - 1) / rows;                    // smallest sh with the same batch count
-            const int sw2 = (m1 + cols - 1) / cols;         // likewise for sw
-            const double ex = tex + sw2 * std::fabs(g.ax) + sh * std::fabs(g.bx) + 6.0;
-            const double ey = tey + sw2 * std::fabs(g.ay) + sh * std::fabs(g.by) + 6.0;
-            const double win = (ex + 1.0) * ey;
-            if (win < fb_win) {
-                fb_win = win;
-                fallback.tile_w = tw;
-                fallback.sw = sw2;
-                fallback.sh = sh;
-                fallback.window = win;
-                fallback.win_w = ex + 1.0;
-                fallback.win_h = ey;
-            }
-            if (win > 0.94 * (double)lds_elems) continue;
-            const double cost = (double)cols * rows * (1.0 + 0.08 * win / (double)lds_elems);
-            if (cost < best_cost) {
-                best_cost = cost;
-                best.tile_w = tw;
-                best.sw = sw2;
-                best.sh = sh;
-                best.window = win;
-                best.win_w = ex + 1.0;
-                best.win_h = ey;
-            }
-        }
+    lag_plan::PlanOptions o;
+    o.tile_w = (int)h->opt_tile_w;
+    o.patch_w = (int)h->opt_patch_w;
+    coreg_handle::PlanMemo& memo = h->plan_memo;
+    const bool same = memo.valid && memo.m1 == m1 && memo.n2 == n2 && memo.lds_elems == lds_elems && memo.o.tile_w == o.tile_w &&
+                      memo.o.patch_w == o.patch_w && std::memcmp(&memo.g, &g, sizeof(g)) == 0;
+    if (!same) {
+        memo.plan = lag_plan::plan_patches(g, m1, n2, lds_elems, o, kTilePts);
+        memo.g = g;
+        memo.m1 = m1;
+        memo.n2 = n2;
+        memo.lds_elems = lds_elems;
+        memo.o = o;
+        memo.valid = true;
     }
-    const Plan& r = best_cost < std::numeric_limits<double>::max() ? best : fallback;
-    if (std::getenv("COREG_DEBUG_PLAN"))
-        std::fprintf(stderr, "[coreg plan] tile %d x %d, lag patch %d x %d, window estimate %.0f (%.1f x %.1f) of %lld elements; "
+    const Plan& r = memo.plan;
+    if (std::getenv("COREG_DEBUG_PLAN")) {
+        std::string patches;
+        for (size_t k = 0; k < r.rects.size(); ++k) {
+            size_t n = 1;
+            while (k + n < r.rects.size() && r.rects[k + n].w == r.rects[k].w && r.rects[k + n].h == r.rects[k].h) ++n;
+            patches += (patches.empty() ? "" : " + ") + std::to_string(n) + " of " + std::to_string(r.rects[k].w) + " x " +
+                       std::to_string(r.rects[k].h);
+            k += n - 1;
+        }
+        std::fprintf(stderr, "[coreg plan] tile %d x %d, lag patches %s = %d live lag-waves, window estimate %.0f (%.1f x %.1f) of %lld elements; "
                      "geometry d/di (%.3f, %.3f) d/dj (%.3f, %.3f) lag1 (%.3f, %.3f) lag2 (%.3f, %.3f)\n", r.tile_w,
-                     kTilePts / r.tile_w, r.sw, r.sh, r.window, r.win_w, r.win_h, lds_elems, g.dx_di, g.dy_di, g.dx_dj, g.dy_dj, g.ax, g.ay,
-                     g.bx, g.by);
+                     kTilePts / r.tile_w, patches.c_str(), r.live_waves, r.window, r.win_w, r.win_h, lds_elems, g.dx_di, g.dy_di,
+                     g.dx_dj, g.dy_dj, g.ax, g.ay, g.bx, g.by);
+    }
     return r;
 }
 
@@ -189,62 +153,6 @@ double lag_step(const double* v, int n) {
         hi = std::max(hi, v[i]);
     }
     return (hi - lo) / (double)(n - 1);
-}
-
-struct SlotList {
-    std::vector<int> i1, i2;        // lag indices supplying the lane parameters (clamped for padding)
-    std::vector<long long> outidx;  // raveled C-order lag index or -1
-    int n_batches = 0;
-};
-
-// slots for combo c (= (i3*n4 + i4)*n5 + i5) restricted to the raveled slice [begin, end)
-void build_slots(const LagDims& d, long long c, long long begin, long long end, int sw, int sh, SlotList* s) {
-    s->i1.clear();
-    s->i2.clear();
-    s->outidx.clear();
-    s->n_batches = 0;
-    {
-        const size_t cap = (size_t)((d.n1 + sw - 1) / sw + 1) * ((d.n2 + sh - 1) / sh) * kBlock;
-        s->i1.reserve(cap);
-        s->i2.reserve(cap);
-        s->outidx.reserve(cap);
-    }
-    const long long row = (long long)d.n2 * d.nc;
-    const int i1_lo = (int)(begin / row);
-    const int i1_hi = (int)((end - 1) / row);
-    const int m1 = i1_hi - i1_lo + 1;
-    for (int p1 = 0; p1 * sw < m1; ++p1)
-        for (int p2 = 0; p2 * sh < d.n2; ++p2) {
-            bool any = false;
-            const size_t at = s->i1.size();
-            for (int t = 0; t < kBlock; ++t) {
-                int lx = t % sw, ly = t / sw;
-                bool valid = ly < sh;
-                if (!valid) lx = ly = 0;
-                int i1 = i1_lo + p1 * sw + lx, i2 = p2 * sh + ly;
-                if (i1 > i1_hi) {
-                    i1 = i1_hi;
-                    valid = false;
-                }
-                if (i2 > d.n2 - 1) {
-                    i2 = d.n2 - 1;
-                    valid = false;
-                }
-                const long long idx = ((long long)i1 * d.n2 + i2) * d.nc + c;
-                if (idx < begin || idx >= end) valid = false;
-                s->i1.push_back(i1);
-                s->i2.push_back(i2);
-                s->outidx.push_back(valid ? idx : -1);
-                any |= valid;
-            }
-            if (!any) {
-                s->i1.resize(at);
-                s->i2.resize(at);
-                s->outidx.resize(at);
-            } else {
-                s->n_batches++;
-            }
-        }
 }
 
 int pick_groups(coreg_handle* h, int n_batches, int n_tiles) {
@@ -343,22 +251,15 @@ int setup_precompute(coreg_handle* h, const Plan& plan, int method, PrecomputeAr
 // indices are already on the device
 long long lds_window_elems(const coreg_handle* h);
 
-// Compile-time LDS window pitch for the Carrington order-2 sweep: the smallest instantiated pitch that holds the planned
-// window (width + slack) within the LDS.  All of them are 25 mod 32, the residue that spreads the ~2 px lag lattice best
-// over the 32 bank pairs in the conflict simulation.  0 = pitch chosen per visit.
+// Compile-time LDS window pitch of a launch (lag_plan::pitch_for) under the handle's options.  0 = pitch chosen per visit.
 int pick_pitch(const coreg_handle* h, const Plan& plan, long long lds_elems, int order = 2) {
     if (h->opt_pitch == 0 || !h->opt_use_lds) return 0;
-    static const int kPitches[] = {89, 121, 153, 185, 217};
     if (h->opt_pitch > 0) {
-        for (int p : kPitches)
+        for (int p : {89, 121, 153, 185, 217})
             if (p == h->opt_pitch) return p;
         return 0;
     }
-    for (int p : kPitches)
-        if ((double)p >= plan.win_w + (order > 2 ? 4.0 : 2.0) &&
-            (double)p * (plan.win_h + (order > 2 ? 2.0 : 0.0)) <= 0.985 * (double)lds_elems)
-            return p;
-    return 0;
+    return lag_plan::pitch_for(plan, lds_elems, order);
 }
 
 }  // namespace

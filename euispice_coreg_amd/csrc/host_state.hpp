@@ -218,6 +218,17 @@ struct coreg_handle {
         FixLaunch fixes;  // the launch's noise-decided samples, for the second run about the flagged slots' pivots
     };
     std::function<int(coreg_handle*)> last_precompute;  // the precompute launch the next launch_sweep follows
+    // the last plan and what it was made from (choose_plan): a session sweeps one lag set under one geometry many times,
+    // and planning the headline's 60 x 60 lags takes about 65 us on the host (tests/native/lag_plan_rules.cpp prints
+    // it), 2 % of its 3.2 ms step with one sweep in flight; keyed on every input of the planner, so it cannot go stale
+    struct PlanMemo {
+        bool valid = false;
+        lag_plan::Geometry g;
+        int m1 = 0, n2 = 0;
+        long long lds_elems = 0;
+        lag_plan::PlanOptions o;
+        lag_plan::Plan plan;
+    } plan_memo;
     DevBuf rf_flags, rf_pivots, rf_list, rf_head, rf_partial;  // work space of the re-evaluation (kernels.hpp: RefineArgs)
     std::vector<PendingFinalize> pending_fin;
     DevBuf fin_outidx;        // copy of the output indices of the pending sharded sweep

@@ -679,8 +679,14 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
     const int group = a.group_lo + (q / a.n_batches) * 8 + slot8;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int pg = __builtin_amdgcn_readfirstlane(threadIdx.x / kBlock);  // point-group of this wave (uniform)
-    const long long slot = (long long)batch * kBlock + (threadIdx.x % kBlock);
+    // wave w = kPointGroups * (lag-wave) + (point-group).  A CU places waves w, w + 4, w + 8, w + 12 of a 1024-thread
+    // workgroup on one SIMD (profiles/microbench/wave_simd.hip, profiles/r07_wave_simd.log), so the four lag-waves of a
+    // point-group share a SIMD: a batch whose last lag-waves are padding (the host packs the live lags into the first
+    // ones, build_slots) leaves every SIMD one wave short instead of leaving one SIMD idle.
+    const int pg = __builtin_amdgcn_readfirstlane(wave % kPointGroups);  // point-group of this wave (uniform)
+    const int lw = __builtin_amdgcn_readfirstlane(wave / kPointGroups);  // its lag-wave: lags 64 lw ... 64 lw + 63 of the batch
+    const int ls = 64 * lw + lane;                                       // this lane's lag slot within the batch
+    const long long slot = (long long)batch * kBlock + ls;
 
     // this lane's lag
     double px0 = 0.0, py0 = 0.0;
@@ -767,14 +773,14 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
         double(*wred)[4] = wred2[visit & 1];
         int* wdirt = wdirty[visit & 1];
         ++visit;
-        if (lane == 0 && wave < kLagWaves) {
-            wred[wave][0] = mnx;
-            wred[wave][1] = mxx;
-            wred[wave][2] = mny;
-            wred[wave][3] = mxy;
+        if (lane == 0 && pg == 0) {
+            wred[lw][0] = mnx;
+            wred[lw][1] = mxx;
+            wred[lw][2] = mny;
+            wred[lw][3] = mxy;
         }
         __syncthreads();  // every wave has left the previous tile's LDS window; the boxes of this visit are in place
-        // the kPointGroups copies of each lag are identical: the first kBlock/64 waves cover every lag
+        // the kPointGroups copies of each lag are identical: the waves of point-group 0 cover every lag
         mnx = fmin(fmin(wred[0][0], wred[1][0]), fmin(wred[2][0], wred[3][0]));
         mxx = fmax(fmax(wred[0][1], wred[1][1]), fmax(wred[2][1], wred[3][1]));
         mny = fmin(fmin(wred[0][2], wred[1][2]), fmin(wred[2][2], wred[3][2]));
@@ -930,7 +936,6 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
     }
     // add the kPointGroups partial sums of every lag in a fixed order (deterministic), one slab per workgroup
     __syncthreads();  // the window is dead: reuse the LDS
-    const int ls = threadIdx.x % kBlock;
     if (pg > 0) {
         double* st = lds + ((size_t)(pg - 1) * kNumSums) * kBlock + ls;
         st[0] = (double)acc.n;
