@@ -750,6 +750,17 @@ class CoregHandle(_ImageIntake):
         el = np.ascontiguousarray(edges_large, dtype=np.float64).ravel()
         self._chk(self._lib.coreg_pixels_set_bins(self._h, es.ctypes.data, len(es), el.ctypes.data, len(el)))
 
+    @staticmethod
+    def _pixels_tile_grid(small_shape, tile, step, n_rot):
+        """(n_ty, n_tx) of a tiled sweep: per axis one window when the tile covers it, else ceil((n - tile) / step) + 1
+        (csrc/pixels_plan.hpp: pixels_windows; step = tile: ceil(n / tile), the disjoint tiles).  (0, 0) for a shape the
+        library refuses: a tile or a step out of range, more than 65535 rotation planes x tiles."""
+        (h, w), (th, tw), (sy, sx) = (int(v) for v in small_shape), tile, step
+        if not (1 <= th <= h and 1 <= tw <= w and 1 <= sy <= th and 1 <= sx <= tw):
+            return (0, 0)
+        grid = (-(-(h - th) // sy) + 1, -(-(w - tw) // sx) + 1)
+        return grid if grid[0] * grid[1] * n_rot <= 65535 else (0, 0)
+
     def _pixels_sweep(self, plan, method, tile_shape, tile_step=None, window=None):
         if int(method) == METHOD_MUTUAL_INFORMATION and plan.get("bins") is not None:
             self.pixels_set_bins(*plan["bins"])
@@ -767,18 +778,12 @@ class CoregHandle(_ImageIntake):
         else:
             # (a tile shape the library refuses gives no grid: nothing is allocated for it)
             th, tw = int(tile_shape[0]), int(tile_shape[1])
-            h, w = (int(v) for v in plan["small_shape"])
+            sy, sx = (th, tw) if tile_step is None else (int(tile_step[0]), int(tile_step[1]))
+            grid = self._pixels_tile_grid(plan["small_shape"], (th, tw), (sy, sx), len(rot))
+            out = np.empty(grid + (len(dx), len(dy), len(rot)), dtype=np.float64)
             if tile_step is None and window is None:
-                ok = 1 <= th <= h and 1 <= tw <= w and -(-h // th) * -(-w // tw) * len(rot) <= 65535
-                grid = (-(-h // th), -(-w // tw)) if ok else (0, 0)
-                out = np.empty(grid + (len(dx), len(dy), len(rot)), dtype=np.float64)
                 rc = self._lib.coreg_pixels_sweep_tiles(self._h, C.byref(p), int(method), th, tw, out.ctypes.data)
             else:
-                sy, sx = (th, tw) if tile_step is None else (int(tile_step[0]), int(tile_step[1]))
-                ok = 1 <= th <= h and 1 <= tw <= w and 1 <= sy <= th and 1 <= sx <= tw
-                grid = (-(-(h - th) // sy) + 1, -(-(w - tw) // sx) + 1) if ok else (0, 0)
-                if grid[0] * grid[1] * len(rot) > 65535:
-                    grid = (0, 0)
                 wy = wx = None
                 if window is not None:
                     # (tables of another length than the tile are the caller's error: the library reads th and tw entries)
@@ -786,7 +791,6 @@ class CoregHandle(_ImageIntake):
                     wx = np.ascontiguousarray(window[1], dtype=np.float64)
                     if wy.shape != (th,) or wx.shape != (tw,):
                         raise ValueError("the weight tables must hold tile rows and tile columns entries")
-                out = np.empty(grid + (len(dx), len(dy), len(rot)), dtype=np.float64)
                 rc = self._lib.coreg_pixels_sweep_windows(self._h, C.byref(p), int(method), th, tw, sy, sx,
                                                           None if wy is None else wy.ctypes.data,
                                                           None if wx is None else wx.ctypes.data, out.ctypes.data)

@@ -42,7 +42,8 @@ using namespace coreg;
 #include "host_fix_lists.hpp"    // wcslib-decided border pixels / single samples
 #include "host_sweep_io.hpp"     // begin / end of a sweep call, stats, plan upload
 #include "host_context.hpp"      // iterative-context sweep: frame stack, per-lag plan, launches
-#include "host_pixels.hpp"       // integer pixel-lag sweep (pxlshift): state, resamples, the two passes
+#include "pixels_plan.hpp"       // integer pixel-lag sweep (pxlshift): checks, window grid, dx groups, band, plan blob (no HIP in it)
+#include "host_pixels.hpp"       // ... its state, uploads and resamples; a sweep = plan, prepare, one score's passes, finish
 
 
 // =====================================================================================================================

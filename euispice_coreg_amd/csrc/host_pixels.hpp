@@ -1,15 +1,24 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the integer pixel-lag sweep
 // of pxlshift.AlignmentPixels -- per-handle state, uploads, the displacement of the large image, the
-// sub-resolved box, the rotation planes and the two sweep passes of either score (csrc/kernels_pixels.hpp).
+// sub-resolved box, the rotation planes and the sweep itself (kernels: csrc/kernels_pixels.hpp).  A sweep is four steps
+// (pixels_sweep_run): the plan -- every check of the request, groups, band, grid and blob layout, csrc/pixels_plan.hpp, no
+// GPU work --, pixels_prepare (buffers, blob, box, rotation planes: the same for every score), the passes of one score
+// (pixels_run_sums / _lct / _mi) and pixels_finish (the cube back, the record of what the sweep left).
 #pragma once
+
+// what the last sweep left in `counts` (and, apodized, in `weights`): nothing once an image has changed
+enum PixLast { PIX_LAST_NONE = 0, PIX_LAST_UNTILED, PIX_LAST_TILED, PIX_LAST_APODIZED };
 
 struct PixelsState {
     DevBuf large, large_tmp, small, box, planes, sums, plan, corr, counts, weights;
     int lW = 0, lH = 0, sW = 0, sH = 0;
     int bW = 0, bH = 0, n_rot = 0;  // what the last sweep left in `box` / `planes`
-    long long n_counts = 0;         // ... and in `counts`: lags of the last untiled sweep, 0 once an image has changed
-    long long n_tile_counts = 0;    //     or a tiled sweep has run; tiles x lags of the last tiled sweep, likewise
-    long long n_tile_weights = 0;   // ... and in `weights`: windows x lags of the last sweep when it was apodized, else 0
+    PixLast last = PIX_LAST_NONE;   // ... and in `counts` / `weights`: its kind and
+    long long last_n_out = 0;       //     its entries (lags, or tiles x lags)
+    void forget_last() {
+        last = PIX_LAST_NONE;
+        last_n_out = 0;
+    }
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     bool timed = false;
     // coreg_pixels_destretch: buffers, events and time of its own (the sweep's images, counts and events are not touched)
@@ -22,31 +31,16 @@ struct PixelsState {
     size_t mi_lds[2][2] = {{0, 0}, {0, 0}};
 };
 
-namespace {
-std::mutex g_pixels_mutex;
-std::map<coreg_handle*, PixelsState*> g_pixels;  // (coreg_handle's own fields are those of the header-shift sweeps)
-}  // namespace
-
 static PixelsState* pixels_state(coreg_handle* h, bool create) {
-    std::lock_guard<std::mutex> lk(g_pixels_mutex);
-    auto it = g_pixels.find(h);
-    if (it != g_pixels.end()) return it->second;
-    if (!create) return nullptr;
-    PixelsState* st = new (std::nothrow) PixelsState();
-    if (st) g_pixels[h] = st;
-    return st;
+    if (!h->pix && create) h->pix = new (std::nothrow) PixelsState();
+    return h->pix;
 }
 
 // called by coreg_destroy with the handle's device current and its stream idle
 void pixels_release(coreg_handle* h) {
-    PixelsState* st = nullptr;
-    {
-        std::lock_guard<std::mutex> lk(g_pixels_mutex);
-        auto it = g_pixels.find(h);
-        if (it == g_pixels.end()) return;
-        st = it->second;
-        g_pixels.erase(it);
-    }
+    PixelsState* st = h->pix;
+    if (!st) return;
+    h->pix = nullptr;
     DevBuf* bufs[] = {&st->large, &st->large_tmp, &st->small, &st->box, &st->planes, &st->sums, &st->plan, &st->corr,
                       &st->counts, &st->weights, &st->ds_src, &st->ds_dst, &st->ds_disp, &st->ds_nodes};
     for (DevBuf* b : bufs) b->release();
@@ -94,7 +88,7 @@ int pixels_set_large(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->bW = st->bH = 0;  // (the box of the last sweep is no longer this image's)
-    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
+    st->forget_last();
     return pixels_upload(h, st->large, img, dtype, ny, nx, &st->lW, &st->lH);
 }
 
@@ -102,7 +96,7 @@ int pixels_set_small(coreg_handle* h, const void* img, int dtype, int32_t ny, in
     PixelsState* st = pixels_state(h, true);
     if (!st) return fail(h, COREG_ENOMEM, "pixels: out of memory");
     st->n_rot = 0;
-    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
+    st->forget_last();
     return pixels_upload(h, st->small, img, dtype, ny, nx, &st->sW, &st->sH);
 }
 
@@ -113,7 +107,7 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     if (!(dx == dx) || !(dy == dy)) return fail(h, COREG_EINVAL, "pixels: the displacement is not a number");
     RETCHK(bind_device(h));
     st->bW = st->bH = 0;
-    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
+    st->forget_last();
     const size_t n = (size_t)st->lW * st->lH;
     HIPCHK(st->large_tmp.reserve(n * sizeof(double)));
     PixResample a = {};
@@ -167,140 +161,21 @@ static int pixels_launch_mi(coreg_handle* h, const dim3& grid, size_t dyn, size_
     return COREG_OK;
 }
 
-// windows along an axis of n pixels: one when the window covers it, else ceil((n - size) / step) + 1 (step = size:
-// ceil(n / size), the disjoint tiles)
-static long long pixels_windows(int n, int size, int step) { return n <= size ? 1 : ((long long)n - size + step - 1) / step + 1; }
-
-// The untiled sweep (tile == nullptr: one cube [n_dx][n_dy][n_rot]) and the tiled one (tile = {rows, columns} of a tile:
-// one such cube per tile, [n_ty][n_tx] of them): the same validation, box, rotation planes, groups and events.  step:
-// nullptr (the tile shape: disjoint tiles) or {rows, columns} between the origins of neighbouring tiles.  wy, wx: both
-// nullptr, or the weight tables [tile rows], [tile columns] of an apodized sweep (the correlation only: k_pixels_lct).
-static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int method, const int32_t* tile, const int32_t* step,
-                            const double* wy, const double* wx, double* corr_out) {
-    if (method == COREG_METHOD_RESIDUS)
-        return fail(h, COREG_ENOTIMPL, "pixels: method residus is not implemented (the reference's pxlshift has no such score); "
-                                       "residus_masked is");
-    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS_MASKED && method != COREG_METHOD_MUTUAL_INFORMATION)
-        return fail(h, COREG_EINVAL, "pixels: unknown method");
-    const bool resid = method == COREG_METHOD_RESIDUS_MASKED, mi = method == COREG_METHOD_MUTUAL_INFORMATION;
-    const bool lct = wy || wx;
-    if (lct && (!wy || !wx || !tile)) return fail(h, COREG_EINVAL, "pixels: an apodized sweep needs both weight tables and a tile");
-    if (lct && method != COREG_METHOD_CORRELATION)
-        return fail(h, COREG_EINVAL, "pixels: weight tables belong to the correlation (no weighted residus_masked or histogram)");
-    PixelsState* st = pixels_state(h, false);
-    if (mi && (!st || st->edges_small.empty() || st->edges_large.empty()))
-        return fail(h, COREG_ESTATE, "pixels: mutual information needs its bins (coreg_pixels_set_bins)");
-    if (!st || !st->large.p || !st->small.p) return fail(h, COREG_ESTATE, "pixels: the large and the small image must be set");
-    if (!pl || !corr_out || !pl->lag_dx || !pl->lag_dy || !pl->lag_drot) return fail(h, COREG_EINVAL, "pixels: null pointer");
-    if (pl->n_dx < 1 || pl->n_dy < 1 || pl->n_rot < 1) return fail(h, COREG_EINVAL, "pixels: empty lag axis");
-    if (pl->n_dy > 65535 || pl->n_rot > 65535) return fail(h, COREG_EINVAL, "pixels: more than 65535 dy or rotation lags");
-    if (!(pl->ratio1 > 0.0) || !(pl->ratio2 > 0.0) || pl->sub_nx < 1 || pl->sub_ny < 1)
-        return fail(h, COREG_EINVAL, "pixels: ratios and sub-resolved shape must be positive");
+// What every score needs, from the reservations on (the record of the last sweep ends here): buffers, the plan blob on
+// the device, the box, the rotation planes -- events 0 and 1 about the two resamples -- and the kernels' common arguments.
+static int pixels_prepare(coreg_handle* h, PixelsState* st, const coreg_pixels_plan* pl, const PixPlan& p, const double* wy,
+                          const double* wx, PixSweep* s) {
     const int w = st->sW, hh = st->sH;
-    const long long n_lag = (long long)pl->n_dx * pl->n_dy * pl->n_rot;
-    if (n_lag > (1ll << 28)) return fail(h, COREG_EINVAL, "pixels: too many lags");
-    PixTiles tl = {};
-    PixStep ts = {0, 0};
-    long long n_tiles = 1;
-    if (tile) {
-        if (tile[0] < 1 || tile[0] > hh || tile[1] < 1 || tile[1] > w)
-            return fail(h, COREG_EINVAL, "pixels: the tile shape must lie within [1, h] x [1, w] of the small image");
-        tl.th = tile[0];
-        tl.tw = tile[1];
-        if (step) {
-            if (step[0] < 1 || step[0] > tl.th || step[1] < 1 || step[1] > tl.tw)
-                return fail(h, COREG_EINVAL, "pixels: the tile step must lie within [1, tile rows] x [1, tile columns]");
-            ts.sy = step[0];
-            ts.sx = step[1];
-        } else {
-            ts.sy = tl.th;
-            ts.sx = tl.tw;
-        }
-        if (lct) {
-            const double* tab[2] = {wy, wx};
-            const int len[2] = {tl.th, tl.tw};
-            for (int a = 0; a < 2; ++a) {
-                bool any = false;
-                for (int k = 0; k < len[a]; ++k) {
-                    if (!std::isfinite(tab[a][k]) || tab[a][k] < 0.0)
-                        return fail(h, COREG_EINVAL, "pixels: a weight is negative or not finite");
-                    any = any || tab[a][k] > 0.0;
-                }
-                if (!any) return fail(h, COREG_EINVAL, "pixels: a weight table without a positive entry");
-            }
-        }
-        const long long n_tx = pixels_windows(w, tl.tw, ts.sx);
-        n_tiles = pixels_windows(hh, tl.th, ts.sy) * n_tx;  // (either factor at most the axis: no overflow)
-        tl.n_tx = (int)n_tx;
-        if (n_tiles * pl->n_rot > 65535) return fail(h, COREG_EINVAL, "pixels: more than 65535 rotation planes x tiles");
-        if (n_tiles * n_lag > (1ll << 28)) return fail(h, COREG_EINVAL, "pixels: too many tiles x lags");
-        tl.n_tiles = (int)n_tiles;
-        tl.n_rot = pl->n_rot;
-    }
-    const long long n_out = n_tiles * n_lag;
-    int min_dx = pl->lag_dx[0], max_dx = min_dx, min_dy = pl->lag_dy[0], max_dy = min_dy;
-    for (int i = 0; i < pl->n_dx; ++i) {
-        min_dx = std::min(min_dx, pl->lag_dx[i]);
-        max_dx = std::max(max_dx, pl->lag_dx[i]);
-    }
-    for (int j = 0; j < pl->n_dy; ++j) {
-        min_dy = std::min(min_dy, pl->lag_dy[j]);
-        max_dy = std::max(max_dy, pl->lag_dy[j]);
-    }
-    // alignment_pixels.py:150-156, for every lag before any GPU work
-    if ((long long)pl->l0 + min_dy < 0 || (long long)pl->l0 + max_dy + hh > pl->sub_ny || (long long)pl->l1 + min_dx < 0 ||
-        (long long)pl->l1 + max_dx + w > pl->sub_nx)
-        return fail(h, COREG_EINVAL, "too large shift : outside FSI");
-    for (int k = 0; k < pl->n_rot; ++k)
-        if (!std::isfinite(pl->lag_drot[k])) return fail(h, COREG_EINVAL, "pixels: a rotation lag is not finite");
-    const int bW = w + (max_dx - min_dx), bH = hh + (max_dy - min_dy);
-    if (too_many(bW, bH) || too_many((long long)w * hh, pl->n_rot)) return fail(h, COREG_EINVAL, "pixels: work space too large");
-    RETCHK(bind_device(h));
-
-    // groups: runs of the dx list, at most kPixG entries, all within kPixG columns of the run's smallest
-    std::vector<PixGroup> groups;
-    for (int i = 0; i < pl->n_dx;) {
-        int lo = pl->lag_dx[i], hi = lo, n = 1;
-        while (i + n < pl->n_dx && n < kPixG) {
-            const int v = pl->lag_dx[i + n];
-            if (std::max(hi, v) - std::min(lo, v) > kPixG - 1) break;
-            lo = std::min(lo, v);
-            hi = std::max(hi, v);
-            ++n;
-        }
-        groups.push_back(PixGroup{i, n, lo, 0});
-        i += n;
-    }
-    const size_t n_groups = groups.size();
-    // plan on the device: groups, dx, dy
-    const size_t off_dx = n_groups * sizeof(PixGroup), off_dy = off_dx + (size_t)pl->n_dx * sizeof(int);
-    // (mutual information: the two edge lists behind them, on a multiple of 8 bytes)
-    const size_t off_es = (off_dy + (size_t)pl->n_dy * sizeof(int) + 7) / 8 * 8;
-    const size_t off_el = off_es + (mi ? st->edges_small.size() : 0) * sizeof(double);
-    // (an apodized sweep: the two weight tables there instead)
-    const size_t off_wx = off_es + (lct ? (size_t)tl.th : 0) * sizeof(double);
-    std::vector<unsigned char> blob(mi ? off_el + st->edges_large.size() * sizeof(double)
-                                    : lct ? off_wx + (size_t)tl.tw * sizeof(double)
-                                          : off_dy + (size_t)pl->n_dy * sizeof(int));
-    std::memcpy(blob.data(), groups.data(), off_dx);
-    std::memcpy(blob.data() + off_dx, pl->lag_dx, (size_t)pl->n_dx * sizeof(int));
-    std::memcpy(blob.data() + off_dy, pl->lag_dy, (size_t)pl->n_dy * sizeof(int));
-    if (mi) {
-        std::memcpy(blob.data() + off_es, st->edges_small.data(), st->edges_small.size() * sizeof(double));
-        std::memcpy(blob.data() + off_el, st->edges_large.data(), st->edges_large.size() * sizeof(double));
-    }
-    if (lct) {
-        std::memcpy(blob.data() + off_es, wy, (size_t)tl.th * sizeof(double));
-        std::memcpy(blob.data() + off_wx, wx, (size_t)tl.tw * sizeof(double));
-    }
+    std::vector<unsigned char> blob(p.bytes);
+    pixels_plan_write(p, pl, p.mi ? st->edges_small.data() : wy, p.mi ? st->edges_large.data() : wx, blob.data());
     HIPCHK(st->plan.reserve(blob.size()));
-    HIPCHK(st->box.reserve((size_t)bW * bH * sizeof(double)));
+    HIPCHK(st->box.reserve((size_t)p.bW * p.bH * sizeof(double)));
     HIPCHK(st->planes.reserve((size_t)w * hh * pl->n_rot * sizeof(double)));
-    if (!mi) HIPCHK(st->sums.reserve((size_t)n_out * (lct ? 7 : 6) * sizeof(double)));
-    if (lct) HIPCHK(st->weights.reserve((size_t)n_out * sizeof(double)));
-    HIPCHK(st->corr.reserve((size_t)n_out * sizeof(double)));
-    HIPCHK(st->counts.reserve((size_t)n_out * sizeof(double)));
-    st->n_counts = st->n_tile_counts = st->n_tile_weights = 0;
+    if (!p.mi) HIPCHK(st->sums.reserve((size_t)p.n_out * (p.lct ? 7 : 6) * sizeof(double)));
+    if (p.lct) HIPCHK(st->weights.reserve((size_t)p.n_out * sizeof(double)));
+    HIPCHK(st->corr.reserve((size_t)p.n_out * sizeof(double)));
+    HIPCHK(st->counts.reserve((size_t)p.n_out * sizeof(double)));
+    st->forget_last();
     for (hipEvent_t& e : st->ev)
         if (!e) HIPCHK(hipEventCreate(&e));
     st->timed = false;
@@ -314,16 +189,16 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
     a.sW = st->lW;
     a.sH = st->lH;
     a.dst = st->box.as<double>();
-    a.dW = bW;
-    a.dH = bH;
-    a.i0 = pl->l1 + min_dx;
-    a.j0 = pl->l0 + min_dy;
+    a.dW = p.bW;
+    a.dH = p.bH;
+    a.i0 = pl->l1 + p.min_dx;
+    a.j0 = pl->l0 + p.min_dy;
     a.ax = pl->ratio1;
     a.ay = pl->ratio2;
     a.fill = -32768.0;
     RETCHK(pixels_resample(h, PIX_AFFINE, a));
-    st->bW = bW;
-    st->bH = bH;
+    st->bW = p.bW;
+    st->bH = p.bH;
     // rotation planes (alignment_pixels.py:72-81), each from the original
     for (int k = 0; k < pl->n_rot; ++k) {
         double* plane = st->planes.as<double>() + (size_t)k * w * hh;
@@ -345,104 +220,129 @@ static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int me
     st->n_rot = pl->n_rot;
     HIPCHK(hipEventRecord(st->ev[1], h->stream));
 
-    PixSweep s = {};
-    s.planes = st->planes.as<double>();
-    s.box = st->box.as<double>();
-    s.groups = (const PixGroup*)st->plan.p;
-    s.lag_dx = (const int*)((const unsigned char*)st->plan.p + off_dx);
-    s.lag_dy = (const int*)((const unsigned char*)st->plan.p + off_dy);
-    s.w = w;
-    s.h = hh;
-    s.bW = bW;
-    s.bH = bH;
-    s.n_dx = pl->n_dx;
-    s.n_dy = pl->n_dy;
-    s.min_dx = min_dx;
-    s.min_dy = min_dy;
-    // the band of the whole image, or of the nominal tile: one value for the launch
-    const int band_w = tile ? tl.tw : w, band_h = tile ? tl.th : hh;
-    s.cw = std::min(band_w, kPixTile);
-    s.bh = std::max(1, std::min(std::min(kPixBandRows, kPixTile / s.cw), band_h));
-    const PixTiles* t = tile ? &tl : nullptr;
-    const dim3 grid((unsigned)n_groups, (unsigned)pl->n_dy, (unsigned)(pl->n_rot * n_tiles));
-    if (mi) {
-        // one pass: histograms, score and counts (csrc/kernels_pixels_mi.hpp); the last two events bracket nothing
-        PixBins b = {};
-        b.edges_small = (const double*)((const unsigned char*)st->plan.p + off_es);
-        b.edges_large = (const double*)((const unsigned char*)st->plan.p + off_el);
-        b.n_small = (int)st->edges_small.size();
-        b.n_large = (int)st->edges_large.size();
-        b.corr = st->corr.as<double>();
-        b.counts = st->counts.as<double>();
-        b.n_rot = pl->n_rot;
-        const size_t dyn = (size_t)kPixG * (b.n_small + 1) * (b.n_large + 1) * sizeof(uint32_t);
-        const bool wide = dyn > kPixMiWideBytes;
-        size_t* allowed = &st->mi_lds[t ? 1 : 0][wide ? 1 : 0];
-        RETCHK(t ? (wide ? pixels_launch_mi<true, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b, ts)
-                         : pixels_launch_mi<true, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b, ts))
-                 : (wide ? pixels_launch_mi<false, kPixMiThreadsWide>(h, grid, dyn, allowed, s, tl, b, ts)
-                         : pixels_launch_mi<false, kPixMiThreads>(h, grid, dyn, allowed, s, tl, b, ts)));
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(st->ev[2], h->stream));
-        HIPCHK(hipEventRecord(st->ev[3], h->stream));
-        HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        st->timed = true;
-        (tile ? st->n_tile_counts : st->n_counts) = n_out;
-        return COREG_OK;
-    }
+    *s = {};
+    s->planes = st->planes.as<double>();
+    s->box = st->box.as<double>();
+    s->groups = pixels_plan_at<PixGroup>(st->plan.p, 0);
+    s->lag_dx = pixels_plan_at<int>(st->plan.p, p.off_dx);
+    s->lag_dy = pixels_plan_at<int>(st->plan.p, p.off_dy);
+    s->w = w;
+    s->h = hh;
+    s->bW = p.bW;
+    s->bH = p.bH;
+    s->n_dx = pl->n_dx;
+    s->n_dy = pl->n_dy;
+    s->min_dx = p.min_dx;
+    s->min_dy = p.min_dy;
+    s->cw = p.cw;
+    s->bh = p.bh;
+    return COREG_OK;
+}
+
+// The passes of one score.  (The three functions stand in the order in which the sweep first named their kernels -- mutual
+// information, apodized, sums: the compiler emits the kernels in that order, and the device code stays as it was.)
+// Mutual information, one pass: histograms, score and counts (csrc/kernels_pixels_mi.hpp); the last two events bracket nothing
+static int pixels_run_mi(coreg_handle* h, PixelsState* st, const coreg_pixels_plan* pl, const PixPlan& p, const PixSweep& s) {
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    PixBins b = {};
+    b.edges_small = pixels_plan_at<double>(st->plan.p, p.off_a);
+    b.edges_large = pixels_plan_at<double>(st->plan.p, p.off_b);
+    b.n_small = p.n_a;
+    b.n_large = p.n_b;
+    b.corr = st->corr.as<double>();
+    b.counts = st->counts.as<double>();
+    b.n_rot = pl->n_rot;
+    const size_t dyn = (size_t)kPixG * (b.n_small + 1) * (b.n_large + 1) * sizeof(uint32_t);
+    const bool wide = dyn > kPixMiWideBytes;
+    size_t* allowed = &st->mi_lds[p.tiled ? 1 : 0][wide ? 1 : 0];
+    RETCHK(p.tiled ? (wide ? pixels_launch_mi<true, kPixMiThreadsWide>(h, grid, dyn, allowed, s, p.tl, b, p.ts)
+                           : pixels_launch_mi<true, kPixMiThreads>(h, grid, dyn, allowed, s, p.tl, b, p.ts))
+                   : (wide ? pixels_launch_mi<false, kPixMiThreadsWide>(h, grid, dyn, allowed, s, p.tl, b, p.ts)
+                           : pixels_launch_mi<false, kPixMiThreads>(h, grid, dyn, allowed, s, p.tl, b, p.ts)));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(st->ev[2], h->stream));
+    HIPCHK(hipEventRecord(st->ev[3], h->stream));
+    return COREG_OK;
+}
+
+// the apodized windows: four sums, then three (csrc/kernels_pixels_lct.hpp), and a finalize step of their own
+static int pixels_run_lct(coreg_handle* h, PixelsState* st, const coreg_pixels_plan* pl, const PixPlan& p, PixSweep s) {
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    const PixWindow win = {pixels_plan_at<double>(st->plan.p, p.off_a), pixels_plan_at<double>(st->plan.p, p.off_b)};
     double* sums0 = st->sums.as<double>();
-    if (lct) {
-        // the apodized windows: four sums, then three (csrc/kernels_pixels_lct.hpp), and a finalize step of their own
-        const PixWindow win = {(const double*)((const unsigned char*)st->plan.p + off_es),
-                               (const double*)((const unsigned char*)st->plan.p + off_wx)};
-        double* lsums1 = sums0 + 4 * n_out;
-        s.sums0 = nullptr;
-        s.sums = sums0;
-        hipLaunchKernelGGL(k_pixels_lct<0>, grid, dim3(kPixThreads), 0, h->stream, s, tl, ts, win);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(st->ev[2], h->stream));
-        s.sums0 = sums0;
-        s.sums = lsums1;
-        hipLaunchKernelGGL(k_pixels_lct<1>, grid, dim3(kPixThreads), 0, h->stream, s, tl, ts, win);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(st->ev[3], h->stream));
-        hipLaunchKernelGGL(k_pixels_lct_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads), (unsigned)n_tiles),
-                           dim3(kPixThreads), 0, h->stream, (const double*)sums0, (const double*)lsums1, pl->n_dx, pl->n_dy,
-                           pl->n_rot, st->corr.as<double>(), st->counts.as<double>(), st->weights.as<double>());
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        st->timed = true;
-        st->n_tile_counts = st->n_tile_weights = n_out;
-        return COREG_OK;
-    }
-    double* sums1 = sums0 + 3 * n_out;
+    double* lsums1 = sums0 + 4 * p.n_out;
     s.sums0 = nullptr;
     s.sums = sums0;
-    if (resid)
-        pixels_launch_pass<kPixR0>(h, grid, s, t, ts);
+    hipLaunchKernelGGL(k_pixels_lct<0>, grid, dim3(kPixThreads), 0, h->stream, s, p.tl, p.ts, win);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(st->ev[2], h->stream));
+    s.sums0 = sums0;
+    s.sums = lsums1;
+    hipLaunchKernelGGL(k_pixels_lct<1>, grid, dim3(kPixThreads), 0, h->stream, s, p.tl, p.ts, win);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(st->ev[3], h->stream));
+    hipLaunchKernelGGL(k_pixels_lct_finalize, dim3(p.fin_grid[0], p.fin_grid[1]), dim3(kPixThreads), 0, h->stream,
+                       (const double*)sums0, (const double*)lsums1, pl->n_dx, pl->n_dy, pl->n_rot, st->corr.as<double>(),
+                       st->counts.as<double>(), st->weights.as<double>());
+    HIPCHK(hipGetLastError());
+    return COREG_OK;
+}
+
+// Pearson or residus_masked: the two passes, events 2 and 3 behind them, and k_pixels_finalize
+static int pixels_run_sums(coreg_handle* h, PixelsState* st, const coreg_pixels_plan* pl, const PixPlan& p, PixSweep s) {
+    const dim3 grid(p.grid[0], p.grid[1], p.grid[2]);
+    const PixTiles* t = p.tiled ? &p.tl : nullptr;
+    double* sums0 = st->sums.as<double>();
+    double* sums1 = sums0 + 3 * p.n_out;
+    s.sums0 = nullptr;
+    s.sums = sums0;
+    if (p.resid)
+        pixels_launch_pass<kPixR0>(h, grid, s, t, p.ts);
     else
-        pixels_launch_pass<0>(h, grid, s, t, ts);
+        pixels_launch_pass<0>(h, grid, s, t, p.ts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[2], h->stream));
     s.sums0 = sums0;
     s.sums = sums1;
-    if (resid)
-        pixels_launch_pass<kPixR1>(h, grid, s, t, ts);
+    if (p.resid)
+        pixels_launch_pass<kPixR1>(h, grid, s, t, p.ts);
     else
-        pixels_launch_pass<1>(h, grid, s, t, ts);
+        pixels_launch_pass<1>(h, grid, s, t, p.ts);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(st->ev[3], h->stream));
-    hipLaunchKernelGGL(k_pixels_finalize, dim3((unsigned)((n_lag + kPixThreads - 1) / kPixThreads), (unsigned)n_tiles),
-                       dim3(kPixThreads), 0, h->stream, (const double*)sums0, (const double*)sums1, pl->n_dx, pl->n_dy, pl->n_rot,
-                       (int)resid, st->corr.as<double>(), st->counts.as<double>());
+    hipLaunchKernelGGL(k_pixels_finalize, dim3(p.fin_grid[0], p.fin_grid[1]), dim3(kPixThreads), 0, h->stream,
+                       (const double*)sums0, (const double*)sums1, pl->n_dx, pl->n_dy, pl->n_rot, (int)p.resid,
+                       st->corr.as<double>(), st->counts.as<double>());
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return COREG_OK;
+}
+
+// the one tail: the cube back, and what this sweep left for the getters
+static int pixels_finish(coreg_handle* h, PixelsState* st, const PixPlan& p, double* corr_out) {
+    HIPCHK(hipMemcpyAsync(corr_out, st->corr.p, (size_t)p.n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     st->timed = true;
-    (tile ? st->n_tile_counts : st->n_counts) = n_out;
+    st->last = !p.tiled ? PIX_LAST_UNTILED : p.lct ? PIX_LAST_APODIZED : PIX_LAST_TILED;
+    st->last_n_out = p.n_out;
     return COREG_OK;
+}
+
+// The untiled sweep (tile == nullptr) and the tiled one, any score (the arguments: PixRequest, csrc/pixels_plan.hpp).  A
+// request the plan refuses changes nothing of the handle's state but its error text.
+static int pixels_sweep_run(coreg_handle* h, const coreg_pixels_plan* pl, int method, const int32_t* tile, const int32_t* step,
+                            const double* wy, const double* wx, double* corr_out) {
+    PixelsState* st = pixels_state(h, false);
+    PixHave have = {};
+    if (st)
+        have = {st->large.p != nullptr, st->small.p != nullptr, st->sW, st->sH, (int)st->edges_small.size(),
+                (int)st->edges_large.size()};
+    const PixPlan p = pixels_plan(PixRequest{pl, method, tile, step, wy, wx, corr_out}, have);
+    if (p.code != COREG_OK) return fail(h, p.code, p.msg);
+    RETCHK(bind_device(h));
+    PixSweep s;
+    RETCHK(pixels_prepare(h, st, pl, p, wy, wx, &s));
+    RETCHK(p.mi ? pixels_run_mi(h, st, pl, p, s) : p.lct ? pixels_run_lct(h, st, pl, p, s) : pixels_run_sums(h, st, pl, p, s));
+    return pixels_finish(h, st, p, corr_out);
 }
 
 int pixels_sweep(coreg_handle* h, const coreg_pixels_plan* pl, int method, double* corr_out) {
@@ -502,23 +402,23 @@ int pixels_get_rotated(coreg_handle* h, int32_t k, double* out) {
 // per-lag sample counts of the last sweep, laid out like its cube
 int pixels_last_counts(coreg_handle* h, double* out) {
     PixelsState* st = pixels_state(h, false);
-    if (!st || st->n_counts < 1) return fail(h, COREG_ESTATE, "pixels: no untiled sweep has run since the images were set");
-    return pixels_read(h, st->counts.p, (size_t)st->n_counts, out);
+    if (!st || st->last != PIX_LAST_UNTILED) return fail(h, COREG_ESTATE, "pixels: no untiled sweep has run since the images were set");
+    return pixels_read(h, st->counts.p, (size_t)st->last_n_out, out);
 }
 
 // the same of the last tiled sweep: [n_ty][n_tx][n_dx][n_dy][n_rot]
 int pixels_last_tile_counts(coreg_handle* h, double* out) {
     PixelsState* st = pixels_state(h, false);
-    if (!st || st->n_tile_counts < 1) return fail(h, COREG_ESTATE, "pixels: no tiled sweep has run since the images were set");
-    return pixels_read(h, st->counts.p, (size_t)st->n_tile_counts, out);
+    if (!st || (st->last != PIX_LAST_TILED && st->last != PIX_LAST_APODIZED)) return fail(h, COREG_ESTATE, "pixels: no tiled sweep has run since the images were set");
+    return pixels_read(h, st->counts.p, (size_t)st->last_n_out, out);
 }
 
 // the sums of weights W of the last tiled sweep when it was apodized, laid out like its cubes
 int pixels_last_tile_weights(coreg_handle* h, double* out) {
     PixelsState* st = pixels_state(h, false);
-    if (!st || st->n_tile_weights < 1)
+    if (!st || st->last != PIX_LAST_APODIZED)
         return fail(h, COREG_ESTATE, "pixels: the last sweep since the images were set was not an apodized one");
-    return pixels_read(h, st->weights.p, (size_t)st->n_tile_weights, out);
+    return pixels_read(h, st->weights.p, (size_t)st->last_n_out, out);
 }
 
 // The destretch of a cube [n_planes][ny][nx] by a local shift field (csrc/pixels_field.hpp, k_pixels_destretch): every

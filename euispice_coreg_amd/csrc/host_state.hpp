@@ -113,6 +113,7 @@ struct FixLaunch {
 };
 
 struct ContextState;  // frames and work space of the iterative-context sweep (host_context.hpp)
+struct PixelsState;   // images and work space of the integer pixel-lag sweep (host_pixels.hpp)
 
 struct coreg_handle {
     int device = 0;
@@ -121,6 +122,7 @@ struct coreg_handle {
     std::string err;
 
     ContextState* ctx = nullptr;  // created by coreg_set_context_frames
+    PixelsState* pix = nullptr;   // created by the first coreg_pixels_* call that needs it (pixels_state)
 
     // small image
     DevBuf small;

@@ -23,19 +23,17 @@
 //                             field (csrc/pixels_field.hpp): one thread per output pixel forms
 //                             the displacement, the taps and the weights once and walks a chunk of planes with them
 //
+// The constants of the band and the groups (kPixG, kPixTile, kPixBandRows, kPixLdsB, ...) and the PODs PixGroup, PixTiles,
+// PixStep are declared in csrc/pixels_plan.hpp, with the host's planner that forms groups and band and checks them
+// against these bounds.
+//
 // Reference arithmetic restated (paths relative to euispice_coreg/): pxlshift/alignment_pixels.py:38-55 (mask),
 // pxlshift/c_correlate.py:41-63 (Pearson, numerator stored as float32), :126-143 (sub-resolution), :72-81 +
 // utils/matrix_transform.py:78-106 (polar round trip), :86-107 (displacement of the large image).
 #pragma once
 #include "pixels_field.hpp"
+#include "pixels_plan.hpp"  // kPixG ... kPixR1, PixGroup, PixTiles, PixStep: what the kernels share with the host's planner
 namespace coreg {
-
-constexpr int kPixG = 16;         // dx lags per workgroup, all within kPixG columns of the group's first
-constexpr int kPixThreads = 256;
-constexpr int kPixTile = 2048;    // small-image pixels staged per band (8 per thread)
-constexpr int kPixBandRows = 64;  // rows per band at most: bounds the G - 1 extra columns of the large rows
-constexpr int kPixLdsB = kPixTile + kPixBandRows * (kPixG - 1);
-constexpr int kPixR0 = 2, kPixR1 = 3;  // k_pixels_sweep<PASS>: the two passes of residus_masked (0 / 1: Pearson)
 
 enum { PIX_AFFINE = 0, PIX_POLAR = 1 };
 
@@ -96,11 +94,6 @@ __global__ __launch_bounds__(kPixThreads) void k_pixels_resample(PixResample p) 
     }
 }
 
-// One group of dx lags: entries [first, first + count) of the dx list, every one within kPixG columns of dx_min.
-struct PixGroup {
-    int first, count, dx_min, pad;
-};
-
 struct PixSweep {
     const double* planes;  // [n_rot][h][w]
     const double* box;     // [bH][bW]: the sub-resolved large image from (slice origin + min lag) on
@@ -111,19 +104,6 @@ struct PixSweep {
     double* sums;          // the pass's output, same layout
     int w, h, bW, bH, n_dx, n_dy, min_dx, min_dy;
     int cw, bh;            // band: columns [c0, c0 + cw) x rows [r0, r0 + bh), cw * bh <= kPixTile, bh <= kPixBandRows
-};
-
-// The window grid of k_pixels_sweep_tiles: tile (ty, tx) is rows [ty sy, min(h, ty sy + th)) x columns [tx sx, min(w, tx sx + tw))
-// of every plane (a rotated plane is rotated about the whole image's centre; a tile is a rectangle of it).  (sy, sx) = (th,
-// tw): disjoint tiles; a smaller step: windows that overlap
-struct PixTiles {
-    int th, tw, n_tx, n_tiles, n_rot;
-};
-
-// The step of the grid, 1 <= sy <= th, 1 <= sx <= tw: the last argument of the kernels that can be tiled, not a part of
-// PixTiles, so that the untiled k_pixels_mi finds its arguments where it found them before the step existed
-struct PixStep {
-    int sy, sx;
 };
 
 template <int PASS>
