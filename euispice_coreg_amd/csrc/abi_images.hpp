@@ -240,7 +240,7 @@ static int reference_crop(coreg_handle* h, int mode, const ResampleArgs& a0, int
     const int nb = 256;
     // On a side stream: the box depends on headers and grid tables only, so it need not queue behind the upload of the
     // image to align that usually precedes it on the handle's stream (its last DMA segment is still in flight).
-    if (!h->aux_stream) HIPCHK(hipStreamCreateWithFlags(&h->aux_stream, hipStreamNonBlocking));
+    if (!h->aux_stream) HIPCHK(hipStreamCreateWithFlags(&h->aux_stream.s, hipStreamNonBlocking));
     HIPCHK(h->bbox_buf.reserve((size_t)nb * 4 * sizeof(double)));
     ResampleArgs a = a0;
     a.bbox = h->bbox_buf.as<double>();

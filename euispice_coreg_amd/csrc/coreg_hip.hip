@@ -33,7 +33,8 @@ using namespace coreg;
 #define COREG_VERSION "0.1.0"
 
 #include "lag_plan.hpp"          // lag patches of a sweep and their slot layout (no HIP in it)
-#include "host_state.hpp"        // buffers, FixLaunch, coreg_handle
+#include "host_owned.hpp"        // the owners of a device / page-locked buffer, an event, a stream
+#include "host_state.hpp"        // FixLaunch, coreg_handle
 #include "host_upload.hpp"       // uploads, FITS decode, reference crop
 #include "host_plan.hpp"         // lag batching, tiles, groups, precompute
 #include "host_fix_launch.hpp"   // re-evaluation work space, k_finalize, fix kernels of a launch
@@ -45,6 +46,7 @@ using namespace coreg;
 #include "pixels_plan.hpp"       // integer pixel-lag sweep (pxlshift): checks, window grid, dx groups, band, plan blob (no HIP in it)
 #include "host_pixels.hpp"       // ... its state, uploads and resamples; a sweep = plan, prepare, one score's passes, finish
 
+coreg_handle::~coreg_handle() = default;  // its members free themselves (host_state.hpp: what coreg_destroy sees to first)
 
 // =====================================================================================================================
 extern "C" {
@@ -54,38 +56,31 @@ const char* coreg_version(void) { return "coreg_hip " COREG_VERSION " (gfx950)";
 int coreg_create(coreg_handle** out, int device) {
     if (!out) return COREG_EINVAL;
     *out = nullptr;
-    coreg_handle* h = new (std::nothrow) coreg_handle();
-    if (!h) return COREG_ENOMEM;
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev < 1) {
-        delete h;
-        return COREG_EHIP;
-    }
+    if (e != hipSuccess || ndev < 1) return COREG_EHIP;
     if (device < 0) {
         if (hipGetDevice(&device) != hipSuccess) device = 0;
     }
-    if (device >= ndev) {
-        delete h;
-        return COREG_EINVAL;
-    }
+    if (device >= ndev) return COREG_EINVAL;
+    coreg_handle* h = new (std::nothrow) coreg_handle();
+    if (!h) return COREG_ENOMEM;
     h->device = device;
-    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreate(&h->ev_end[0]) != hipSuccess ||
-        hipEventCreate(&h->ev_end[1]) != hipSuccess || hipEventRecord(h->ev_end[0], h->stream) != hipSuccess ||
+    if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream.s, hipStreamNonBlocking) != hipSuccess ||
+        hipEventCreate(&h->ev_end[0].e) != hipSuccess ||
+        hipEventCreate(&h->ev_end[1].e) != hipSuccess || hipEventRecord(h->ev_end[0], h->stream) != hipSuccess ||
         hipEventRecord(h->ev_end[1], h->stream) != hipSuccess ||
         h->pivots.reserve(2 * sizeof(double)) != hipSuccess ||
         hipMemsetAsync(h->pivots.p, 0, 2 * sizeof(double), h->stream) != hipSuccess) {
-        h->own_stream = h->stream != nullptr;
         coreg_destroy(h);  // releases whatever was created
         return COREG_EHIP;
     }
-    h->own_stream = true;
     std::memset(&h->stats, 0, sizeof(h->stats));
     *out = h;
     return COREG_OK;
 }
 
+// What is not ownership (the invariants at coreg_handle): the device current, the upload thread gone, the streams idle.
 void coreg_destroy(coreg_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
@@ -99,44 +94,7 @@ void coreg_destroy(coreg_handle* h) {
         h->up_thread.join();
     }
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    context_release(h);
-    pixels_release(h);
     if (h->up_stream) (void)hipStreamSynchronize(h->up_stream);
-    for (int k = 0; k < 2; ++k) {
-        h->pin_small[k].release();
-        if (h->ev_pin_small[k]) (void)hipEventDestroy(h->ev_pin_small[k]);
-    }
-    DevBuf* bufs[] = {&h->rf_flags, &h->rf_pivots, &h->rf_list, &h->rf_head, &h->rf_partial, &h->small, &h->ref, &h->pivots, &h->red_sum, &h->red_cnt, &h->t_sin_lon, &h->t_cos_lon,
-                      &h->t_cos_lat, &h->t_sin_lat, &h->pts, &h->tile_count, &h->tile_list, &h->tile_cum, &h->group_first,
-                      &h->tile_info, &h->tile_bbox, &h->counters, &h->lane_params, &h->out_index, &h->partials, &h->out_dev,
-                      &h->tmp_img, &h->up_f64, &h->up_flag, &h->up_raw, &h->rice_blob, &h->rice_rand, &h->dec_img, &h->border_dev, &h->sums, &h->fin_outidx, &h->border_flags, &h->fix_partial, &h->rf_fix_slab, &h->counts};
-    for (DevBuf* b : bufs) b->release();
-    for (int k = 0; k < 2; ++k) {
-        h->pin_img[k].release();
-        if (h->ev_img[k]) (void)hipEventDestroy(h->ev_img[k]);
-    }
-    for (auto& e : h->ev_sweep) {
-        (void)hipEventDestroy(e.a);
-        (void)hipEventDestroy(e.b);
-    }
-    for (auto& e : h->ev_pre) {
-        (void)hipEventDestroy(e.a);
-        (void)hipEventDestroy(e.b);
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (h->ev_end[k]) (void)hipEventDestroy(h->ev_end[k]);
-        h->pin_plan[k].release();
-    }
-    h->pin_info.release();
-    h->pin_border.release();
-    h->bbox_buf.release();
-    if (h->aux_stream) (void)hipStreamDestroy(h->aux_stream);
-    if (h->up_stream) (void)hipStreamDestroy(h->up_stream);
-    if (h->ev_small) (void)hipEventDestroy(h->ev_small);
-    if (h->ev_main) (void)hipEventDestroy(h->ev_main);
-    h->red_sum_up.release();
-    h->red_cnt_up.release();
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
 
@@ -147,9 +105,7 @@ int coreg_set_stream(coreg_handle* h, void* hip_stream) {
     RETCHK(bind_device(h));
     RETCHK(collect_stats(h));
     HIPCHK(hipStreamSynchronize(h->stream));
-    if (h->own_stream && h->stream) HIPCHK(hipStreamDestroy(h->stream));
-    h->stream = (hipStream_t)hip_stream;
-    h->own_stream = false;
+    HIPCHK(h->stream.borrow((hipStream_t)hip_stream));
     return COREG_OK;
 }
 

@@ -1,5 +1,6 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the iterative-context
-// sweep (AlignementSpiceIterativeContextRaster): the resident imager frames, the per-lag plan (homographies of every
+// sweep (AlignementSpiceIterativeContextRaster): the resident imager frames (ContextState, freed with the handle that owns
+// it), the per-lag plan (homographies of every
 // (frame, lag) and of the SPICE resample, wcslib's bounds decisions on the grid's border), the launches.
 #pragma once
 
@@ -11,25 +12,13 @@ struct ContextState {
     bool have_pivot = false;
     double pivot = 0.0;  // mean of the finite frame pixels (pivot of the context sums)
     DevBuf mean, col_frame, h_ctx, h_sp, edge, partials, out_index, flags, slot_pivots, list, head, out_tmp;
-    hipEvent_t ev_a = nullptr, ev_b = nullptr;
+    Event ev_a, ev_b;
 };
 
 namespace {
 
 constexpr long long kCtxBatch = 8192;  // lag slots per launch (bounds the plan and the partial slabs)
 constexpr double kCtxEdgeTol = 1e-6;   // px: a border sample this close to a bound is decided by wcslib's arithmetic
-
-void context_release(coreg_handle* h) {
-    ContextState* c = h->ctx;
-    if (!c) return;
-    DevBuf* bufs[] = {&c->frames, &c->mean, &c->col_frame, &c->h_ctx, &c->h_sp, &c->edge, &c->partials,
-                      &c->out_index, &c->flags, &c->slot_pivots, &c->list, &c->head, &c->out_tmp};
-    for (DevBuf* b : bufs) b->release();
-    if (c->ev_a) (void)hipEventDestroy(c->ev_a);
-    if (c->ev_b) (void)hipEventDestroy(c->ev_b);
-    delete c;
-    h->ctx = nullptr;
-}
 
 int context_set_frames(coreg_handle* h, int n, int ny, int nx, int dtype, const coreg_wcs2d* hdrs,
                        const void* const* pixels) {
@@ -42,12 +31,12 @@ int context_set_frames(coreg_handle* h, int n, int ny, int nx, int dtype, const 
     }
     RETCHK(bind_device(h));
     if (!h->ctx) {
-        h->ctx = new (std::nothrow) ContextState();
+        h->ctx.reset(new (std::nothrow) ContextState());
         if (!h->ctx) return fail(h, COREG_ENOMEM, "set_context_frames: out of host memory");
-        HIPCHK(hipEventCreate(&h->ctx->ev_a));
-        HIPCHK(hipEventCreate(&h->ctx->ev_b));
+        HIPCHK(hipEventCreate(&h->ctx->ev_a.e));
+        HIPCHK(hipEventCreate(&h->ctx->ev_b.e));
     }
-    ContextState* c = h->ctx;
+    ContextState* c = h->ctx.get();
     const size_t esz = dtype == COREG_F32 ? sizeof(float) : sizeof(double);
     const size_t per = (size_t)ny * nx * esz;
     HIPCHK(hipStreamSynchronize(h->stream));  // (a sweep in flight may still read the old stack)
@@ -64,7 +53,7 @@ int context_set_frames(coreg_handle* h, int n, int ny, int nx, int dtype, const 
 }
 
 int context_frame_from_small(coreg_handle* h, int k) {
-    ContextState* c = h->ctx;
+    ContextState* c = h->ctx.get();
     if (!c) return fail(h, COREG_ESTATE, "context_frame_from_small: coreg_set_context_frames has not been called");
     if (k < 0 || k >= c->n) return fail(h, COREG_EINVAL, "context_frame_from_small: no such frame");
     if (!h->small.p || h->sW != c->W || h->sH != c->H)
@@ -156,7 +145,7 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
     const ComboRange combo = take_combo_range(h);
     if (combo.begin != 0 || combo.end != 0)
         return fail(h, COREG_EINVAL, "sweep_context: combo_begin/combo_end do not apply to this sweep");
-    ContextState* c = h->ctx;
+    ContextState* c = h->ctx.get();
     if (!c) return fail(h, COREG_ESTATE, "sweep_context: coreg_set_context_frames has not been called");
     if (!h->small.p) return fail(h, COREG_ESTATE, "sweep_context: coreg_set_small (the SPICE image) has not been called");
     if (!target4 || !small || !col_frame || !lags) return fail(h, COREG_EINVAL, "sweep_context: null argument");

@@ -1,5 +1,6 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the integer pixel-lag sweep
-// of pxlshift.AlignmentPixels -- per-handle state, uploads, the displacement of the large image, the
+// of pxlshift.AlignmentPixels -- per-handle state (PixelsState, freed with the handle that owns it),
+// uploads, the displacement of the large image, the
 // sub-resolved box, the rotation planes and the sweep itself (kernels: csrc/kernels_pixels.hpp).  A sweep is four steps
 // (pixels_sweep_run): the plan -- every check of the request, groups, band, grid and blob layout, csrc/pixels_plan.hpp, no
 // GPU work --, pixels_prepare (buffers, blob, box, rotation planes: the same for every score), the passes of one score
@@ -19,11 +20,11 @@ struct PixelsState {
         last = PIX_LAST_NONE;
         last_n_out = 0;
     }
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev[4];
     bool timed = false;
     // coreg_pixels_destretch: buffers, events and time of its own (the sweep's images, counts and events are not touched)
     DevBuf ds_src, ds_dst, ds_disp, ds_nodes;
-    hipEvent_t ds_ev[2] = {nullptr, nullptr};
+    Event ds_ev[2];
     bool ds_timed = false;
     // coreg_pixels_set_bins: the edge lists of COREG_METHOD_MUTUAL_INFORMATION, kept until set again
     std::vector<double> edges_small, edges_large;
@@ -32,23 +33,8 @@ struct PixelsState {
 };
 
 static PixelsState* pixels_state(coreg_handle* h, bool create) {
-    if (!h->pix && create) h->pix = new (std::nothrow) PixelsState();
-    return h->pix;
-}
-
-// called by coreg_destroy with the handle's device current and its stream idle
-void pixels_release(coreg_handle* h) {
-    PixelsState* st = h->pix;
-    if (!st) return;
-    h->pix = nullptr;
-    DevBuf* bufs[] = {&st->large, &st->large_tmp, &st->small, &st->box, &st->planes, &st->sums, &st->plan, &st->corr,
-                      &st->counts, &st->weights, &st->ds_src, &st->ds_dst, &st->ds_disp, &st->ds_nodes};
-    for (DevBuf* b : bufs) b->release();
-    for (hipEvent_t e : st->ev)
-        if (e) (void)hipEventDestroy(e);
-    for (hipEvent_t e : st->ds_ev)
-        if (e) (void)hipEventDestroy(e);
-    delete st;
+    if (!h->pix && create) h->pix.reset(new (std::nothrow) PixelsState());
+    return h->pix.get();
 }
 
 static int pixels_upload(coreg_handle* h, DevBuf& buf, const void* img, int dtype, int32_t ny, int32_t nx, int* W, int* H) {
@@ -176,8 +162,8 @@ static int pixels_prepare(coreg_handle* h, PixelsState* st, const coreg_pixels_p
     HIPCHK(st->corr.reserve((size_t)p.n_out * sizeof(double)));
     HIPCHK(st->counts.reserve((size_t)p.n_out * sizeof(double)));
     st->forget_last();
-    for (hipEvent_t& e : st->ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
+    for (Event& e : st->ev)
+        if (!e) HIPCHK(hipEventCreate(&e.e));
     st->timed = false;
     HIPCHK(hipMemcpyAsync(st->plan.p, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -461,8 +447,8 @@ int pixels_destretch(coreg_handle* h, const void* cube, int dtype, int32_t n_pla
     HIPCHK(st->ds_src.reserve(bytes));
     HIPCHK(st->ds_dst.reserve(bytes));
     if (displacement) HIPCHK(st->ds_disp.reserve(2 * n_pix * sizeof(double)));
-    for (hipEvent_t& e : st->ds_ev)
-        if (!e) HIPCHK(hipEventCreate(&e));
+    for (Event& e : st->ds_ev)
+        if (!e) HIPCHK(hipEventCreate(&e.e));
     st->ds_timed = false;
     HIPCHK(hipMemcpyAsync(st->ds_nodes.p, nodes.data(), nodes.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(st->ds_src.p, cube, bytes, hipMemcpyHostToDevice, h->stream));

@@ -1,56 +1,8 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order; round 6 split by concern,
-// no behaviour change): device / page-locked buffers, the per-launch fix arguments and the handle (coreg_handle): every field the ABI functions share.
+// no behaviour change): the per-launch fix arguments and the handle (coreg_handle): every field the ABI functions share,
+// every buffer, event and stream an owning member (host_owned.hpp) -- there is no list of what to free.
 #pragma once
 namespace {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) {
-            hipError_t e = hipFree(p);
-            if (e != hipSuccess) return e;
-            p = nullptr;
-            cap = 0;
-        }
-        const size_t want = bytes + bytes / 4 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) return e;
-        cap = want;
-        return hipSuccess;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-    template <typename T>
-    T* as() const {
-        return (T*)p;
-    }
-};
-
-struct PinBuf {  // page-locked host staging (async H2D without a host sync)
-    void* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t bytes) {
-        if (bytes <= cap) return hipSuccess;
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-        const size_t want = bytes + bytes / 2 + 4096;
-        hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        cap = want;
-        return hipSuccess;
-    }
-    void release() {
-        if (p) (void)hipHostFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 // where the pixels of an upload live
 enum SrcKind {
@@ -80,7 +32,7 @@ constexpr int kMaxDevices = 64;
 std::mutex g_attr_mutex;
 
 struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
+    Event a, b;
     bool b_is_next_sweep = false;  // precompute intervals end at the opening event of sweep launch `next_sweep_index`
     size_t next_sweep_index = 0;
 };
@@ -93,7 +45,6 @@ struct EventPair {
 // (a launch's single-sample lists kept past the next launch of the same sweep: grid-shared plate-carree sweeps)
 struct KeptTapLists {
     DevBuf all;  // the five lists of TapFixArgs, one after another (keep_tap_lists)
-    ~KeptTapLists() { all.release(); }
 };
 // single samples near an integer coordinate: the device lists k_tap_fix reads (prepare_tap_fix fills them into the
 // BorderFix of a launch, build_fix_launch adds the fields every fix kernel shares)
@@ -115,14 +66,20 @@ struct FixLaunch {
 struct ContextState;  // frames and work space of the iterative-context sweep (host_context.hpp)
 struct PixelsState;   // images and work space of the integer pixel-lag sweep (host_pixels.hpp)
 
+// Ownership: every buffer, event and stream below frees itself when the handle is deleted; coreg_destroy is the one route
+// there and keeps three invariants.  (1) Every stream is idle before anything is freed: it stops the upload thread and
+// synchronizes `stream` and `up_stream` (`aux_stream` is synchronized by its one user before that returns).  (2) The
+// handle's device is current while it is destroyed.  (3) A borrowed stream (coreg_set_stream) is never destroyed.
+// With (1) no member needs another to outlive it, so the members stand in the order that reads best and ~coreg_handle
+// has an empty body.
 struct coreg_handle {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    Stream stream;  // the library's own, or the caller's (coreg_set_stream: borrowed)
     std::string err;
 
-    ContextState* ctx = nullptr;  // created by coreg_set_context_frames
-    PixelsState* pix = nullptr;   // created by the first coreg_pixels_* call that needs it (pixels_state)
+    std::unique_ptr<ContextState> ctx;  // created by coreg_set_context_frames
+    std::unique_ptr<PixelsState> pix;   // created by the first coreg_pixels_* call that needs it (pixels_state)
+    ~coreg_handle();                    // (defined where both are complete: coreg_hip.hip)
 
     // small image
     DevBuf small;
@@ -142,7 +99,7 @@ struct coreg_handle {
     CarrTables tabs;
     std::vector<double> tabs_key;
     PinBuf pin_img[2];
-    hipEvent_t ev_img[2] = {nullptr, nullptr};
+    Event ev_img[2];
     int pin_img_next = 0;
     // precompute outputs
     DevBuf pts, tile_count, tile_list, tile_cum, group_first, tile_info, tile_bbox;
@@ -160,13 +117,13 @@ struct coreg_handle {
                                            // decoded reference image (the image to align is decoded in place)
     PrologueArgs pending_prologue = {};  // set by upload_plan, consumed by the sweep's first k_precompute launch
     DevBuf bbox_buf;         // reference_crop: partial bounding boxes
-    hipStream_t aux_stream = nullptr;  // side stream of reference_crop (created on first use)
+    Stream aux_stream;  // side stream of reference_crop (created on first use)
     // The image to align goes up on a stream of its own (round 5): the preparation of the reference image -- bounding
     // box, crop upload, resample -- depends on headers and the reference image only and no longer queues behind the
     // 16 MiB of the image to align; the first call that reads the image (or its pivot) joins the two streams with an event
     // (bind_device).  float32 / byte-swap-only uploads from host memory; everything else stays on `stream`.
-    hipStream_t up_stream = nullptr;
-    hipEvent_t ev_small = nullptr, ev_main = nullptr;
+    Stream up_stream;
+    Event ev_small, ev_main;
     bool small_pending = false;
     DevBuf red_sum_up, red_cnt_up;  // device_mean's scratch on up_stream
     int64_t opt_overlap_upload = 1;
@@ -185,7 +142,7 @@ struct coreg_handle {
     bool up_has = false, up_stop = false, up_busy = false;
     hipError_t up_rc = hipSuccess;
     PinBuf pin_small[2];
-    hipEvent_t ev_pin_small[2] = {nullptr, nullptr};
+    Event ev_pin_small[2];
     int pin_small_next = 0;
     // zero-lag border decision of the helioprojective sub-map path (geometry.hpp WcslibTan): grid pixels the
     // reference's wcslib round trip drops, cached per header
@@ -246,11 +203,11 @@ struct coreg_handle {
     PinBuf pin_info;              // tile_info read-back of the in-flight sweep
     std::vector<EventPair> ev_sweep, ev_pre;
     size_t ev_sweep_used = 0, ev_pre_used = 0;
-    hipEvent_t ev_t1 = nullptr;
+    hipEvent_t ev_t1 = nullptr;  // (not owned)
     // The plan staging (lag parameters in pinned memory) is double-buffered: slot k is rewritten only when the sweep
     // that last used it has ended (its end event), so the host can plan sweep n + 1 while the GPU runs sweep n, with no
     // extra event between the kernels.  ev_t1 is an alias of the current slot's end event.
-    hipEvent_t ev_end[2] = {nullptr, nullptr};
+    Event ev_end[2];
     PinBuf pin_plan[2];
     int plan_slot = 0;
     bool plan_open = false;  // upload_plan has staged a plan that no end_sweep has closed yet (a sweep that failed midway)

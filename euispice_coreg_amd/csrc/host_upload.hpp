@@ -99,9 +99,9 @@ int begin_small_upload(coreg_handle* h, hipStream_t* s) {
     *s = h->stream;
     if (!h->opt_overlap_upload) return COREG_OK;
     if (!h->up_stream) {
-        HIPCHK(hipStreamCreateWithFlags(&h->up_stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_small, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_main, hipEventDisableTiming));
+        HIPCHK(hipStreamCreateWithFlags(&h->up_stream.s, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&h->ev_small.e, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&h->ev_main.e, hipEventDisableTiming));
     }
     HIPCHK(hipEventRecord(h->ev_main, h->stream));
     HIPCHK(hipStreamWaitEvent(h->up_stream, h->ev_main, 0));
@@ -118,8 +118,8 @@ int end_small_upload(coreg_handle* h, hipStream_t s) {
 EventPair* next_event(coreg_handle* h, std::vector<EventPair>& v, size_t& used) {
     if (used == v.size()) {
         EventPair e;
-        if (hipEventCreate(&e.a) != hipSuccess || hipEventCreate(&e.b) != hipSuccess) return nullptr;
-        v.push_back(e);
+        if (hipEventCreate(&e.a.e) != hipSuccess || hipEventCreate(&e.b.e) != hipSuccess) return nullptr;
+        v.push_back(std::move(e));
     }
     return &v[used++];
 }
@@ -317,7 +317,7 @@ hipError_t stage_to_device(coreg_handle* h, StageRing ring, void* dev, const voi
     if (mine) h->pin_img_next ^= 1;
     else h->pin_small_next ^= 1;
     PinBuf& slot = mine ? h->pin_img[k] : h->pin_small[k];
-    hipEvent_t& ev = mine ? h->ev_img[k] : h->ev_pin_small[k];
+    hipEvent_t& ev = (mine ? h->ev_img[k] : h->ev_pin_small[k]).e;
     hipError_t e = ev ? hipEventSynchronize(ev)  // the upload that last used this slot has left it
                       : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     if (e != hipSuccess) return e;

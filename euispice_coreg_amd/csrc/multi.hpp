@@ -277,6 +277,8 @@ void multi_grid_share(const MultiPlan& p, int n1, int n2, long long inner, int k
 
 }  // namespace
 
+// Ownership: the handles are destroyed and blk / gat / img / pre emptied by coreg_multi_destroy, device k's on worker k
+// with that device current and its stream drained; the two page-locked buffers go with the struct itself.
 struct coreg_multi {
     int n = 0;
     bool virtual_devices = false;  // several logical devices on one GPU (COREG_VIRTUAL_DEVICES): no RCCL
@@ -295,7 +297,7 @@ struct coreg_multi {
     int force_mode = -1;            // coreg_multi_set_option "force_mode": tests of one partition on any lag set
     int opt_image_shares = 1;       // "image_shares": 1 = row shares + one all-gather when RCCL is in use, 0 = N copies
     std::string rccl_error;         // why RCCL was given up on this handle ("" = it was not)
-    std::vector<hipEvent_t> pre;    // per device: recorded on the stream right before a group's collective (what the
+    std::vector<Event> pre;         // per device: recorded on the stream right before a group's collective (what the
                                     // bounded wait times is the collective, not the sweep queued in front of it)
     double phase_s[3] = {0, 0, 0};  // the last abandoned group: polling the streams, ncclCommAbort, draining the streams
     bool force_collective = false;  // COREG_MULTI_FORCE_RCCL=1 with ONE device: the RCCL calls run with a one-rank group
@@ -346,15 +348,8 @@ int multi_on(coreg_multi* m, int k, F fn) {
 
 // host image -> the shared pinned staging (one parallel copy), page-locked so that every device DMAs from it
 int multi_stage(coreg_multi* m, const void* src, size_t bytes) {
-    if (bytes > m->stage.cap) {
-        m->stage.release();
-        void* p = nullptr;
-        const size_t want = bytes + bytes / 8 + 4096;
-        if (hipHostMalloc(&p, want, hipHostMallocPortable) != hipSuccess)
-            return mfail(m, COREG_ENOMEM, "hipHostMalloc (shared staging) failed");
-        m->stage.p = p;
-        m->stage.cap = want;
-    }
+    if (m->stage.reserve(bytes, hipHostMallocPortable, 8) != hipSuccess)
+        return mfail(m, COREG_ENOMEM, "hipHostMalloc (shared staging) failed");
     parallel_memcpy(m->stage.p, src, bytes);
     return COREG_OK;
 }
@@ -384,11 +379,11 @@ void multi_drop_rccl(coreg_multi* m, const std::string& why) {
 
 // the stream position "just before the group": on every device after its sweep is enqueued, before the group is issued
 int multi_mark_pre_group(coreg_multi* m) {
-    if (m->pre.size() != (size_t)m->n) m->pre.assign(m->n, nullptr);
+    m->pre.resize(m->n);
     return multi_run(m, [&](int k) {
         coreg_handle* h = m->h[k];
         RETCHK(bind_device(h));
-        if (!m->pre[k]) HIPCHK(hipEventCreateWithFlags(&m->pre[k], hipEventDisableTiming));
+        if (!m->pre[k]) HIPCHK(hipEventCreateWithFlags(&m->pre[k].e, hipEventDisableTiming));
         HIPCHK(hipEventRecord(m->pre[k], h->stream));
         return COREG_OK;
     });
@@ -407,14 +402,12 @@ __global__ void k_test_stall(int* release) {
         __builtin_amdgcn_s_sleep(64);
 }
 struct StallFlag {
+    PinBuf mem;
     int* p = nullptr;
     explicit StallFlag(bool wanted) {
         if (!wanted) return;
-        if (hipHostMalloc((void**)&p, sizeof(int), hipHostMallocPortable | hipHostMallocCoherent) != hipSuccess) p = nullptr;
+        if (mem.reserve(sizeof(int), hipHostMallocPortable | hipHostMallocCoherent) == hipSuccess) p = (int*)mem.p;
         if (p) __atomic_store_n(p, 0, __ATOMIC_SEQ_CST);
-    }
-    ~StallFlag() {
-        if (p) (void)hipHostFree(p);
     }
 };
 inline bool multi_test_stall() {
@@ -950,7 +943,7 @@ void coreg_multi_destroy(coreg_multi* m) {
             m->blk[k].release();
             m->gat[k].release();
             m->img[k].release();
-            if (k < (int)m->pre.size() && m->pre[k]) (void)hipEventDestroy(m->pre[k]);
+            if (k < (int)m->pre.size()) m->pre[k].reset();
         });
         m->w[k]->wait();
     }
@@ -960,9 +953,10 @@ void coreg_multi_destroy(coreg_multi* m) {
         m->w[k]->post([m, k] { coreg_destroy(m->h[k]); });
         m->w[k]->wait();
     }
-    m->stage.release();
-    m->host_gather.release();
     m->w.clear();  // joins the threads
+    // Left to `delete m`, on this thread with whatever device is current: `stage` and `host_gather` only.  Both are
+    // page-locked HOST memory, which hipHostFree releases whichever device is current; every device-side owner was
+    // emptied on its own worker above.
     delete m;
 }
 
