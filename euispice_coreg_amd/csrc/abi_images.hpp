@@ -353,7 +353,8 @@ static int prepare_carrington(coreg_handle* h, const void* large, const PixFmt& 
     RETCHK(bind_device_nowait(h));  // (touches neither the image to align nor its pivot: no join with the upload stream)
     ResampleArgs a;
     std::memset(&a, 0, sizeof(a));
-    RETCHK(upload_carr_tables(h, *grid, *hdr, &a.carr, h->has_rot_ref ? &h->rot_ref : nullptr));
+    RETCHK(upload_carr_tables(h, *grid, *hdr, h->has_rot_ref ? &h->rot_ref : nullptr));
+    a.carr = carr_dev(h);
     set_carr_common(&a.carr, carr_common(*hdr, solar_r));
     carr_origin(*hdr, &a.x0, &a.y0);
     a.W = nx;
@@ -521,7 +522,8 @@ int coreg_resample_carrington(coreg_handle* h, const coreg_wcs2d* hdr, const cor
     RETCHK(bind_device(h));
     ResampleArgs a;
     std::memset(&a, 0, sizeof(a));
-    RETCHK(upload_carr_tables(h, *grid, *hdr, &a.carr, h->has_rot_small ? &h->rot_small : nullptr));
+    RETCHK(upload_carr_tables(h, *grid, *hdr, h->has_rot_small ? &h->rot_small : nullptr));
+    a.carr = carr_dev(h);
     set_carr_common(&a.carr, carr_common(*hdr, solar_r));
     carr_origin(*hdr, &a.x0, &a.y0);
     a.img = h->small.p;

@@ -33,14 +33,15 @@ using namespace coreg;
 #define COREG_VERSION "0.1.0"
 
 #include "lag_plan.hpp"          // lag patches of a sweep and their slot layout (no HIP in it)
+#include "sweep_plan.hpp"        // the planners of the header-shift sweeps: what to launch, decided without the device (no HIP in it)
 #include "host_owned.hpp"        // the owners of a device / page-locked buffer, an event, a stream
 #include "host_state.hpp"        // FixLaunch, coreg_handle
 #include "host_upload.hpp"       // uploads, FITS decode, reference crop
-#include "host_plan.hpp"         // lag batching, tiles, groups, precompute
+#include "host_plan.hpp"         // lag checks, the planners' view of the handle, tile groups, precompute
 #include "host_fix_launch.hpp"   // re-evaluation work space, k_finalize, fix kernels of a launch
 #include "sweep_variant.hpp"     // the list of k_sweep instantiations and the rule that picks one (no HIP in it)
 #include "host_sweep_launch.hpp" // SweepLaunchSpec, launch_sweep
-#include "host_fix_lists.hpp"    // wcslib-decided border pixels / single samples
+#include "host_fix_lists.hpp"    // uploads of the plan's border pixels / flags, the single-sample scan
 #include "host_sweep_io.hpp"     // begin / end of a sweep call, stats, plan upload
 #include "host_context.hpp"      // iterative-context sweep: frame stack, per-lag plan, launches
 #include "pixels_plan.hpp"       // integer pixel-lag sweep (pxlshift): checks, window grid, dx groups, band, plan blob (no HIP in it)

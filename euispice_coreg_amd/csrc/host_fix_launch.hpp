@@ -3,16 +3,12 @@
 // the one k_finalize launch, the fix kernels of one launch, and their second run with k_refine.
 #pragma once
 namespace {
-struct BorderFix {  // lag-points of a launch whose border pixels are decided by wcslib's rounding noise
-    struct Item {
-        long long slot;  // slot of the launch
-        int first, n;    // its pixels in h->border_dev: [first, first + n)
-        long long flags_off;  // odd spline order: offset of its per-pixel tap-shift flags in h->border_flags, or -1
-    };
-    std::vector<Item> items;
-    std::vector<int> pixels;  // concatenated linear grid indices (host copy of h->border_dev)
+struct BorderFix {  // the noise-decided samples of a launch
+    // lag-points whose border pixels are decided by wcslib's rounding noise: the plan's (sweep_plan.hpp; its pixels are in
+    // h->border_dev, its flag grids in h->border_flags), or none
+    const BorderItems* border = nullptr;
     TapFix tap;  // single samples near an integer coordinate (odd spline orders): device arrays ready for k_tap_fix
-    bool any() const { return !items.empty() || tap.segs > 0; }
+    bool any() const { return (border && !border->items.empty()) || tap.segs > 0; }
 };
 
 // work space + arguments of the re-evaluation of ill-conditioned lag-points (kernels.hpp: RefineArgs) for a launch of

@@ -1,139 +1,7 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order; round 6 split by concern,
-// no behaviour change): noise-decided samples, host side: invariant axes, wcslib's dropped border pixels and tap-shift flags, the single-sample scan + lists.
+// no behaviour change): noise-decided samples, what of their host side uses HIP: the uploads of the plan's border pixels and tap-shift flags (sweep_plan.hpp decides them), the single-sample scan + lists.
 #pragma once
 namespace {
-// Zero-CRVAL lags of a helioprojective sweep share the target header's tangent point, so the map target pixel ->
-// shifted pixel is exactly affine, A = (CDELT' PC')^-1 (CDELT PC) about CRPIX.  When A leaves an image axis invariant
-// (the zero lag: A = I; a CDELT1-only lag: rows map to rows; CDELT2-only: columns to columns; `reference` CDELT
-// semantics: A = I up to the rebuilt PC's last bit) the border rows / columns of the grid sit ON the bounds rule
-// c < 0 or c > n-1 and what the reference does with them is decided by the rounding noise of its wcslib round trip
-// (alignment.py:1038-1069).  For such a lag the device map is SNAPPED to the exact invariant form (every border
-// pixel in bounds along that axis) and the pixels wcslib drops are listed for k_border_fix.
-struct AxisInvariance {
-    bool rows = false, cols = false;
-};
-AxisInvariance snap_invariant_axes(const coreg_wcs2d& target, const coreg_wcs2d& shifted, int gw, int gh, double hm[9]) {
-    AxisInvariance inv;
-    if (target.crval1 != shifted.crval1 || target.crval2 != shifted.crval2 || target.lonpole != shifted.lonpole ||
-        target.unit_to_deg != shifted.unit_to_deg)
-        return inv;
-    const Mat3 a = mat_mul(iwc_to_pix(shifted), pix_to_iwc(target));
-    const double tol = 1e-6;  // pixels, over the whole grid; rounding noise is < 1e-9, a real lag moves >> 1e-6
-    const double a00 = (double)a.m[0][0], a01 = (double)a.m[0][1], a02 = (double)a.m[0][2];
-    const double a10 = (double)a.m[1][0], a11 = (double)a.m[1][1], a12 = (double)a.m[1][2];
-    inv.rows = std::fabs(a10) * gw + std::fabs(a11 - 1.0) * gh + std::fabs(a12) < tol;
-    inv.cols = std::fabs(a00 - 1.0) * gw + std::fabs(a01) * gh + std::fabs(a02) < tol;
-    if (inv.rows || inv.cols) {
-        hm[0] = inv.cols ? 1.0 : a00;
-        hm[1] = inv.cols ? 0.0 : a01;
-        hm[2] = inv.cols ? 0.0 : a02;
-        hm[3] = inv.rows ? 0.0 : a10;
-        hm[4] = inv.rows ? 1.0 : a11;
-        hm[5] = inv.rows ? 0.0 : a12;
-        hm[6] = hm[7] = 0.0;
-        hm[8] = 1.0;
-    }
-    return inv;
-}
-
-// Pixels of the invariant border rows / columns that the reference's round trip pixel -> sky (target header) ->
-// ang2pipi -> pixel (shifted header) sends outside [0, W-1] x [0, H-1] of the image to align.  Appended to `out`.
-template <typename Chain>
-void wcslib_dropped_border_pixels_t(coreg_handle* h, const coreg_wcs2d& target, const coreg_wcs2d& shifted,
-                                    AxisInvariance inv, std::vector<int>* out) {
-    const int gw = h->gW, gh = h->gH;
-    std::vector<double> key = {(double)target.proj, target.latpole == target.latpole ? target.latpole : -999.0, target.crpix1, target.crpix2, target.crval1, target.crval2, target.cdelt1, target.cdelt2,
-                               target.pc1_1, target.pc1_2, target.pc2_1, target.pc2_2, target.unit_to_deg,
-                               target.lonpole == target.lonpole ? target.lonpole : -999.0,
-                               shifted.crpix1, shifted.crpix2, shifted.cdelt1, shifted.cdelt2, shifted.pc1_1,
-                               shifted.pc1_2, shifted.pc2_1, shifted.pc2_2, (double)gw, (double)gh, (double)h->sW,
-                               (double)h->sH, inv.rows ? 1.0 : 0.0, inv.cols ? 1.0 : 0.0};
-    auto hit = h->border_cache.find(key);
-    if (hit == h->border_cache.end()) {
-        Chain wf, wt;
-        wf.init(target);
-        wt.init(shifted);
-        std::vector<int> cand;  // row-major, each pixel once
-        const int jb = h->sH - 1, ib = h->sW - 1;
-        for (int j = 0; j < gh; ++j) {
-            const bool row = inv.rows && (j == 0 || j == jb);
-            if (row) {
-                for (int i = 0; i < gw; ++i) cand.push_back(j * gw + i);
-            } else if (inv.cols) {
-                cand.push_back(j * gw);
-                if (ib > 0 && ib < gw) cand.push_back(j * gw + ib);
-            }
-        }
-        std::vector<char> drop(cand.size(), 0);
-        const double wmax = (double)(h->sW - 1), hmax = (double)(h->sH - 1);
-        auto work = [&](size_t lo, size_t hi) {
-            for (size_t k = lo; k < hi; ++k) {
-                double x, y;
-                wcslib_pixel_to_pixel(wf, wt, (double)(cand[k] % gw), (double)(cand[k] / gw), &x, &y);
-                drop[k] = !((x >= 0.0) && (x <= wmax) && (y >= 0.0) && (y <= hmax));  // NaN -> dropped
-            }
-        };
-        parallel_for((long long)cand.size(), cand.size() < 2048 ? 1 : 8, 0, work);
-        std::vector<int> dropped;
-        for (size_t k = 0; k < cand.size(); ++k)
-            if (drop[k]) dropped.push_back(cand[k]);
-        if (h->border_cache.size() >= 64) h->border_cache.clear();
-        hit = h->border_cache.emplace(std::move(key), std::move(dropped)).first;
-    }
-    out->insert(out->end(), hit->second.begin(), hit->second.end());
-}
-
-void wcslib_dropped_border_pixels(coreg_handle* h, const coreg_wcs2d& target, const coreg_wcs2d& shifted,
-                                  AxisInvariance inv, std::vector<int>* out) {
-    if (target.proj == COREG_PROJ_CAR) wcslib_dropped_border_pixels_t<WcslibCar>(h, target, shifted, inv, out);
-    else wcslib_dropped_border_pixels_t<WcslibTan>(h, target, shifted, inv, out);
-}
-
-// Odd spline orders: for every grid pixel, does the reference's round trip come back BELOW the integer along an
-// invariant axis (bit 0: rows / y, bit 1: columns / x)?  Then floor(c) -- the first tap of an odd-order spline -- is one
-// less than at the exact integer the sweep used (k_parity_fix).  W x H evaluations of the wcslib chain, in threads;
-// cached per header pair.
-template <typename Chain>
-const std::vector<unsigned char>& wcslib_tap_shift_flags_t(coreg_handle* h, const coreg_wcs2d& target,
-                                                           const coreg_wcs2d& shifted, AxisInvariance inv) {
-    const int gw = h->gW, gh = h->gH;
-    std::vector<double> key = {(double)target.proj, target.latpole == target.latpole ? target.latpole : -999.0, target.crpix1, target.crpix2, target.crval1, target.crval2, target.cdelt1, target.cdelt2,
-                               target.pc1_1, target.pc1_2, target.pc2_1, target.pc2_2, target.unit_to_deg,
-                               target.lonpole == target.lonpole ? target.lonpole : -999.0,
-                               shifted.crpix1, shifted.crpix2, shifted.cdelt1, shifted.cdelt2, shifted.pc1_1,
-                               shifted.pc1_2, shifted.pc2_1, shifted.pc2_2, (double)gw, (double)gh, (double)h->sW,
-                               (double)h->sH, inv.rows ? 1.0 : 0.0, inv.cols ? 1.0 : 0.0};
-    auto hit = h->flags_cache.find(key);
-    if (hit != h->flags_cache.end()) return hit->second;
-    Chain wf, wt;
-    wf.init(target);
-    wt.init(shifted);
-    std::vector<unsigned char> flags((size_t)gw * gh, 0);
-    const double wmax = (double)(h->sW - 1), hmax = (double)(h->sH - 1);
-    auto work = [&](int j0, int j1) {
-        for (int j = j0; j < j1; ++j)
-            for (int i = 0; i < gw; ++i) {
-                double x, y;
-                wcslib_pixel_to_pixel(wf, wt, (double)i, (double)j, &x, &y);
-                unsigned char f = 0;
-                if (inv.rows && y < (double)j) f |= 1;
-                if (inv.cols && x < (double)i) f |= 2;
-                // the bounds rule drops the pixel altogether (border pixels only; k_border_fix has taken it out)
-                if (!((x >= 0.0) && (x <= wmax) && (y >= 0.0) && (y <= hmax))) f |= 4;
-                flags[(size_t)j * gw + i] = f;
-            }
-    };
-    parallel_for(gh, (long long)gw * gh < 4096 ? 1 : 12, 0, work);
-    if (h->flags_cache.size() >= 4) h->flags_cache.clear();
-    return h->flags_cache.emplace(std::move(key), std::move(flags)).first->second;
-}
-
-const std::vector<unsigned char>& wcslib_tap_shift_flags(coreg_handle* h, const coreg_wcs2d& target,
-                                                         const coreg_wcs2d& shifted, AxisInvariance inv) {
-    if (target.proj == COREG_PROJ_CAR) return wcslib_tap_shift_flags_t<WcslibCar>(h, target, shifted, inv);
-    return wcslib_tap_shift_flags_t<WcslibTan>(h, target, shifted, inv);
-}
-
 int upload_border_pixels(coreg_handle* h, const std::vector<int>& pixels) {
     const size_t bytes = std::max<size_t>(1, pixels.size()) * sizeof(int);
     HIPCHK(h->border_dev.reserve(bytes));
@@ -246,61 +114,24 @@ int prepare_tap_fix(coreg_handle* h, int sweep_mode, int order, const coreg_wcs2
     h->tap_last[1] = 0;
     h->tap_last[2] = count > cap ? 1 : 0;
     if (count == 0 || count > cap) return COREG_OK;
-    std::vector<uint2> list(count);
+    // the scan's list back; grouped by slot, put in pixel order and evaluated with wcslib's chain on the host
+    // (sweep_plan.hpp group_tap_samples); the lists k_tap_fix reads up
+    static_assert(sizeof(TapSample) == sizeof(uint2), "TapSample mirrors the uint2 entries of k_tap_scan's list");
+    std::vector<TapSample> list(count);
     HIPCHK(hipMemcpy(list.data(), h->tap_list.p, (size_t)count * sizeof(uint2), hipMemcpyDeviceToHost));
-    // group by slot (counting sort), then every segment is put in pixel order by the thread that evaluates it: the
-    // summation order of k_tap_fix does not depend on the order the scan's atomics happened to list the samples in
-    std::vector<int> first((size_t)n_slots + 1, 0);
-    for (unsigned k = 0; k < count; ++k) ++first[(size_t)list[k].x + 1];
-    for (long long sl = 0; sl < n_slots; ++sl) first[(size_t)sl + 1] += first[(size_t)sl];
-    std::vector<unsigned> pixel(count);
-    {
-        std::vector<int> at(first.begin(), first.end() - 1);
-        for (unsigned k = 0; k < count; ++k) pixel[(size_t)at[list[k].x]++] = list[k].y;
-    }
-    std::vector<int> seg_slot, seg_begin;
-    for (long long sl = 0; sl < n_slots; ++sl)
-        if (first[(size_t)sl + 1] > first[(size_t)sl]) {
-            seg_slot.push_back((int)sl);
-            seg_begin.push_back(first[(size_t)sl]);
-        }
-    seg_begin.push_back((int)count);
-    const int n_seg = (int)seg_slot.size();
-    std::vector<double> xw(count), yw(count);
-    WcslibTan wf;
-    WcslibCar wfc;
-    const bool car = target.proj == COREG_PROJ_CAR;
-    if (car) wfc.init(target);
-    else wf.init(target);
-    const int gw = h->gW;
-    auto work = [&](int s0, int s1) {  // (one segment at a time: the threads share the entries about evenly)
-        for (int sg = s0; sg < s1; ++sg) {
-            std::sort(pixel.begin() + seg_begin[sg], pixel.begin() + seg_begin[sg + 1]);
-            if (car) {
-                WcslibCar wt;
-                wt.init(shifted_of(seg_slot[sg]));
-                for (int e = seg_begin[sg]; e < seg_begin[sg + 1]; ++e)
-                    wcslib_pixel_to_pixel(wfc, wt, (double)(pixel[e] % (unsigned)gw), (double)(pixel[e] / (unsigned)gw), &xw[e], &yw[e]);
-            } else {
-                WcslibTan wt;
-                wt.init(shifted_of(seg_slot[sg]));
-                for (int e = seg_begin[sg]; e < seg_begin[sg + 1]; ++e)
-                    wcslib_pixel_to_pixel(wf, wt, (double)(pixel[e] % (unsigned)gw), (double)(pixel[e] / (unsigned)gw), &xw[e], &yw[e]);
-            }
-        }
-    };
-    parallel_for(n_seg, count < 4096 ? 1 : 12, 1, work);
+    const TapLists t = group_tap_samples(list, n_slots, h->gW, target, shifted_of);
+    const int n_seg = (int)t.seg_slot.size();
     HIPCHK(h->tap_seg_slot.reserve((size_t)n_seg * sizeof(int)));
     HIPCHK(h->tap_seg_begin.reserve((size_t)(n_seg + 1) * sizeof(int)));
     HIPCHK(h->tap_pixel.reserve((size_t)count * sizeof(unsigned)));
     HIPCHK(h->tap_xw.reserve((size_t)count * sizeof(double)));
     HIPCHK(h->tap_yw.reserve((size_t)count * sizeof(double)));
     // (pageable sources, rare path: blocking copies)
-    HIPCHK(hipMemcpy(h->tap_seg_slot.p, seg_slot.data(), (size_t)n_seg * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->tap_seg_begin.p, seg_begin.data(), (size_t)(n_seg + 1) * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->tap_pixel.p, pixel.data(), (size_t)count * sizeof(unsigned), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->tap_xw.p, xw.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->tap_yw.p, yw.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tap_seg_slot.p, t.seg_slot.data(), (size_t)n_seg * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tap_seg_begin.p, t.seg_begin.data(), (size_t)(n_seg + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tap_pixel.p, t.pixel.data(), (size_t)count * sizeof(unsigned), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tap_xw.p, t.xw.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->tap_yw.p, t.yw.data(), (size_t)count * sizeof(double), hipMemcpyHostToDevice));
     fix->tap.segs = n_seg;
     fix->tap.count = (long long)count;
     fix->tap.mode = sweep_mode;

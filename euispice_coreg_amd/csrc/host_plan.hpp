@@ -1,38 +1,9 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order; round 6 split by concern,
-// no behaviour change): planning of a sweep: lag dimensions and checks, tile shape + lag patch, lag slots, tile groups, precompute launch, LDS pitch.
+// no behaviour change): what a sweep needs of the handle before its launches: lag dimensions and checks, tile groups, tapered shares, the precompute launch and its buffers.
 #pragma once
 namespace {
-// ---- host fork/join ---------------------------------------------------------------------------------------------
-// fn(lo, hi) over [0, n) in chunks of `grain` items (0: one even share per thread) dealt from a shared counter, on up to
-// `max_threads` threads, this one included, and never more than there are chunks or cores.  Every caller's items are
-// independent of one another, so the split never changes a result.  Work run here must not touch the handle's caches.
-template <typename Fn>
-void parallel_for(long long n, unsigned max_threads, long long grain, Fn fn) {
-    if (n <= 0) return;
-    const long long nt_max = std::max<long long>(1, std::min(max_threads, std::thread::hardware_concurrency()));
-    if (grain <= 0) grain = (n + nt_max - 1) / nt_max;
-    const long long nt = std::min(nt_max, (n + grain - 1) / grain);
-    if (nt <= 1) {
-        fn(0ll, n);
-        return;
-    }
-    std::atomic<long long> next(0);
-    auto worker = [&] {
-        for (long long lo = next.fetch_add(grain); lo < n; lo = next.fetch_add(grain)) fn(lo, std::min(n, lo + grain));
-    };
-    std::vector<std::thread> th;
-    for (long long t = 1; t < nt; ++t) th.emplace_back(worker);
-    worker();
-    for (auto& x : th) x.join();
-}
-
-// ---- lag batching (lag_plan.hpp: the planner and the slot layout, plain C++) ------------------------------------------
-using lag_plan::Geometry;
-using lag_plan::LagDims;
-using lag_plan::Plan;
-using lag_plan::SlotList;
-using lag_plan::build_slots;
-static_assert(lag_plan::kSlots == kBlock && lag_plan::kWaveLags == 64, "lag_plan.hpp restates the kernels' constants");
+// (sweep_plan.hpp, plain C++: parallel_for, the lag planner under the handle's options, the pure rules pick_groups /
+// pick_pitch, and the three planners of the header-shift sweeps)
 
 // The one-shot combination range ("combo_begin" / "combo_end") belongs to THE NEXT sweep call, whatever becomes of it: the
 // entry points take it off the handle before any validation (a call that failed early used to leave it armed
@@ -93,81 +64,36 @@ static int check_grid(coreg_handle* h, const coreg_carr_grid* g) {
     return why ? fail(h, COREG_EINVAL, why) : COREG_OK;
 }
 
-// Tile shape and lag patches of a sweep (lag_plan::plan_patches) under the handle's options.  m1 x n2 = lag plane.
-Plan choose_plan(coreg_handle* h, const Geometry& g, int m1, int n2, long long lds_elems) {
-    lag_plan::PlanOptions o;
-    o.tile_w = (int)h->opt_tile_w;
-    o.patch_w = (int)h->opt_patch_w;
-    coreg_handle::PlanMemo& memo = h->plan_memo;
-    const bool same = memo.valid && memo.m1 == m1 && memo.n2 == n2 && memo.lds_elems == lds_elems && memo.o.tile_w == o.tile_w &&
-                      memo.o.patch_w == o.patch_w && std::memcmp(&memo.g, &g, sizeof(g)) == 0;
-    if (!same) {
-        memo.plan = lag_plan::plan_patches(g, m1, n2, lds_elems, o, kTilePts);
-        memo.g = g;
-        memo.m1 = m1;
-        memo.n2 = n2;
-        memo.lds_elems = lds_elems;
-        memo.o = o;
-        memo.valid = true;
-    }
-    const Plan& r = memo.plan;
-    if (std::getenv("COREG_DEBUG_PLAN")) {
-        std::string patches;
-        for (size_t k = 0; k < r.rects.size(); ++k) {
-            size_t n = 1;
-            while (k + n < r.rects.size() && r.rects[k + n].w == r.rects[k].w && r.rects[k + n].h == r.rects[k].h) ++n;
-            patches += (patches.empty() ? "" : " + ") + std::to_string(n) + " of " + std::to_string(r.rects[k].w) + " x " +
-                       std::to_string(r.rects[k].h);
-            k += n - 1;
-        }
-        std::fprintf(stderr, "[coreg plan] tile %d x %d, lag patches %s = %d live lag-waves, window estimate %.0f (%.1f x %.1f) of %lld elements; "
-                     "geometry d/di (%.3f, %.3f) d/dj (%.3f, %.3f) lag1 (%.3f, %.3f) lag2 (%.3f, %.3f)\n", r.tile_w,
-                     kTilePts / r.tile_w, patches.c_str(), r.live_waves, r.window, r.win_w, r.win_h, lds_elems, g.dx_di, g.dy_di,
-                     g.dx_dj, g.dy_dj, g.ax, g.ay, g.bx, g.by);
-    }
-    return r;
-}
-
-// indices of the smallest, the most central and the largest value of a lag axis (any order, NaNs ignored)
-void extreme_lags(const double* v, int n, int out[3]) {
-    int lo = 0, hi = 0;
-    for (int i = 1; i < n; ++i) {
-        if (v[i] < v[lo] || v[lo] != v[lo]) lo = i;
-        if (v[i] > v[hi] || v[hi] != v[hi]) hi = i;
-    }
-    const double mid = 0.5 * (v[lo] + v[hi]);
-    int m = lo;
-    for (int i = 0; i < n; ++i)
-        if (std::fabs(v[i] - mid) < std::fabs(v[m] - mid)) m = i;
-    out[0] = lo;
-    out[1] = m;
-    out[2] = hi;
-}
-
-// mean spacing of a lag axis over its value range (plan heuristics only; lists may come in any order)
-double lag_step(const double* v, int n) {
-    if (n < 2) return 0.0;
-    double lo = v[0], hi = v[0];
-    for (int i = 1; i < n; ++i) {
-        lo = std::min(lo, v[i]);
-        hi = std::max(hi, v[i]);
-    }
-    return (hi - lo) / (double)(n - 1);
-}
-
-int pick_groups(coreg_handle* h, int n_batches, int n_tiles) {
-    // the compacted points are cut in n_groups EQUAL shares (k_tile_list), so n_groups * n_batches workgroups of equal
-    // work: 256 groups make every round of 256 CUs full; fewer when there are many lag batches
-    if (h->opt_shard_world > 1) {
-        // point sharding: every rank takes a multiple of 8 groups (the XCD-aware block mapping of k_sweep), as close
-        // to one full round of 256 workgroups as the batch count allows
-        const long long per_rank = 8 * std::max<long long>(1, std::llround(256.0 / (8.0 * n_batches)));
-        return (int)std::min<long long>(per_rank * h->opt_shard_world, 1000 / (8 * h->opt_shard_world) * 8 * h->opt_shard_world);
-    }
-    long long g = h->opt_n_groups > 0 ? h->opt_n_groups : (4096 + n_batches - 1) / n_batches;
+// tile groups of a launch under the handle's options (sweep_plan.hpp pick_groups)
+int pick_groups(const coreg_handle* h, int n_batches, int n_tiles) {
     (void)n_tiles;
-    g = std::max<long long>(8, std::min<long long>(h->opt_n_groups > 0 ? 1000 : 256, ((g + 7) / 8) * 8));
-    return (int)g;
+    return coreg::pick_groups(h->opt_shard_world, h->opt_n_groups, n_batches);
+}
+
+// What the planners of the header-shift sweeps (sweep_plan.hpp) may read of the handle, and the state they may update:
+// the wcslib caches and the lag-plan memo.
+long long lds_window_elems(const coreg_handle* h);
+SweepEnv sweep_env(coreg_handle* h) {
+    SweepEnv e;
+    e.sW = h->sW;
+    e.sH = h->sH;
+    e.gW = h->gW;
+    e.gH = h->gH;
+    e.border_fix = h->opt_border_fix != 0;
+    e.tap_fix = h->opt_tap_fix != 0;
+    e.use_lds = h->opt_use_lds != 0;
+    e.h_series = h->opt_h_series != 0;
+    e.tile_skip = h->opt_tile_skip != 0;
+    e.lds_elems = lds_window_elems(h);
+    e.tile_w = (int)h->opt_tile_w;
+    e.patch_w = (int)h->opt_patch_w;
+    e.shard_world = h->opt_shard_world;
+    e.n_groups = h->opt_n_groups;
+    e.pitch = h->opt_pitch;
+    e.tabs = &h->tabs;
+    e.caches = &h->wcslib;
+    e.memo = &h->plan_memo;
+    return e;
 }
 
 // Tapered shares (kernels.hpp group_start) pay when the launch has many rounds of workgroups; with few rounds the large
@@ -245,21 +171,6 @@ int setup_precompute(coreg_handle* h, const Plan& plan, int method, PrecomputeAr
     a->tile_bbox = h->tile_bbox.as<double>();
     a->residus = method != COREG_METHOD_CORRELATION ? 1 : 0;  // (both residus methods)
     return COREG_OK;
-}
-
-// one sweep-kernel launch + finalize over n_batches * 256 slots whose parameters (SoA [np][n_slots]) and output
-// indices are already on the device
-long long lds_window_elems(const coreg_handle* h);
-
-// Compile-time LDS window pitch of a launch (lag_plan::pitch_for) under the handle's options.  0 = pitch chosen per visit.
-int pick_pitch(const coreg_handle* h, const Plan& plan, long long lds_elems, int order = 2) {
-    if (h->opt_pitch == 0 || !h->opt_use_lds) return 0;
-    if (h->opt_pitch > 0) {
-        for (int p : {89, 121, 153, 185, 217})
-            if (p == h->opt_pitch) return p;
-        return 0;
-    }
-    return lag_plan::pitch_for(plan, lds_elems, order);
 }
 
 }  // namespace

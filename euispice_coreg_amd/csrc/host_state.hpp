@@ -98,6 +98,7 @@ struct coreg_handle {
     bool has_rot_ref = false, has_rot_small = false;
     CarrTables tabs;
     std::vector<double> tabs_key;
+    bool tabs_uploaded = false;  // the device tables are those of `tabs`
     PinBuf pin_img[2];
     Event ev_img[2];
     int pin_img_next = 0;
@@ -144,10 +145,8 @@ struct coreg_handle {
     PinBuf pin_small[2];
     Event ev_pin_small[2];
     int pin_small_next = 0;
-    // zero-lag border decision of the helioprojective sub-map path (geometry.hpp WcslibTan): grid pixels the
-    // reference's wcslib round trip drops, cached per header
-    std::map<std::vector<double>, std::vector<int>> border_cache;
-    std::map<std::vector<double>, std::vector<unsigned char>> flags_cache;
+    // zero-lag border decisions of the sub-map paths, cached per header pair (sweep_plan.hpp: the planners are handed it)
+    WcslibCaches wcslib;
     DevBuf border_flags, fix_partial;
     DevBuf border_dev;
     PinBuf pin_border;
@@ -177,17 +176,7 @@ struct coreg_handle {
         FixLaunch fixes;  // the launch's noise-decided samples, for the second run about the flagged slots' pivots
     };
     std::function<int(coreg_handle*)> last_precompute;  // the precompute launch the next launch_sweep follows
-    // the last plan and what it was made from (choose_plan): a session sweeps one lag set under one geometry many times,
-    // and planning the headline's 60 x 60 lags takes about 65 us on the host (tests/native/lag_plan_rules.cpp prints
-    // it), 2 % of its 3.2 ms step with one sweep in flight; keyed on every input of the planner, so it cannot go stale
-    struct PlanMemo {
-        bool valid = false;
-        lag_plan::Geometry g;
-        int m1 = 0, n2 = 0;
-        long long lds_elems = 0;
-        lag_plan::PlanOptions o;
-        lag_plan::Plan plan;
-    } plan_memo;
+    PlanMemo plan_memo;  // the last lag plan and what it was made from (sweep_plan.hpp choose_plan)
     DevBuf rf_flags, rf_pivots, rf_list, rf_head, rf_partial;  // work space of the re-evaluation (kernels.hpp: RefineArgs)
     std::vector<PendingFinalize> pending_fin;
     DevBuf fin_outidx;        // copy of the output indices of the pending sharded sweep

@@ -125,7 +125,8 @@ void fill_fix_common(Args& x, const coreg_handle* h, const SweepLaunchSpec& L) {
 int build_fix_launch(coreg_handle* h, const SweepLaunchSpec& L, FixLaunch* fl) {
     fl->small_f32 = h->small_f32;
     if (!L.fix || !L.fix->any()) return COREG_OK;
-    for (const BorderFix::Item& it : L.fix->items) {
+    static const std::vector<BorderItems::Item> no_items;
+    for (const BorderItems::Item& it : L.fix->border ? L.fix->border->items : no_items) {
         if (it.flags_off >= 0) {
             // odd spline order: re-decide the tap set of every pixel of this lag-point (k_parity_fix), after
             // k_border_fix has set the slab entry (same stream)

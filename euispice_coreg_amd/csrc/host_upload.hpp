@@ -24,17 +24,6 @@ static bool too_many(long long a, long long b) { return a * b > 2147483647ll; }
         if (_r != COREG_OK) return _r; \
     } while (0)
 
-// COREG_TRACE=1: host-side timestamps (microseconds since the first one) of the hand-over's stages on stderr
-inline void trace(const char* what) {
-    static const bool on = [] {
-        const char* e = std::getenv("COREG_TRACE");
-        return e && std::atoi(e) == 1;
-    }();
-    if (!on) return;
-    static const auto t0 = std::chrono::steady_clock::now();
-    const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-    std::fprintf(stderr, "[coreg %9.1f us] %s\n", us, what);
-}
 int bind_device_nowait(coreg_handle* h) {
     HIPCHK(hipSetDevice(h->device));
     return COREG_OK;
@@ -622,55 +611,57 @@ int decode_tiled_device(coreg_handle* h, const coreg_fits_tiled* t, DevBuf& pix,
     return upload_image(h, h->up_f64.as<double>(), n, pix, is_f32, SRC_DEVICE);
 }
 
-// rot: differential rotation of the image this resample is for (null: none)
-int upload_carr_tables(coreg_handle* h, const coreg_carr_grid& g, const coreg_wcs2d& hdr, CarrDev* dev,
-                       const coreg_diffrot* rot = nullptr) {
-    if (g.n_lon < 1 || g.n_lat < 1) return fail(h, COREG_EINVAL, "carrington grid: n_lon/n_lat must be >= 1");
-    // key: everything the tables depend on (caller-supplied latitude trig by value)
-    std::vector<double> key = {g.lon0, g.lon1, (double)g.n_lon, g.lat0, g.lat1, (double)g.n_lat, hdr.crln_obs,
-                               g.lat_cos ? 1.0 : 0.0, g.lat_sin ? 1.0 : 0.0, rot ? 1.0 : 0.0};
-    if (rot) key.insert(key.end(), {rot->delta_t_days, rot->c0, rot->c1, rot->c2});
-    if (g.lat_cos) key.insert(key.end(), g.lat_cos, g.lat_cos + g.n_lat);
-    if (g.lat_sin) key.insert(key.end(), g.lat_sin, g.lat_sin + g.n_lat);
-    if (key != h->tabs_key || !h->t_sin_lon.p) {
-        CarrTables& t = h->tabs;
-        carr_tables(g, hdr.crln_obs, t);
-        if (rot) {
-            diffrot_dx(t.sin_lat.data(), g.n_lat, *rot, t.dx);
-            // nothing to rotate: the per-column tables serve, as without a rotation
-            if (std::all_of(t.dx.begin(), t.dx.end(), [](double v) { return v == 0.0; })) t.dx.clear();
-        }
-        HIPCHK(h->t_sin_lon.reserve(g.n_lon * sizeof(double)));
-        HIPCHK(h->t_cos_lon.reserve(g.n_lon * sizeof(double)));
-        HIPCHK(h->t_cos_lat.reserve(g.n_lat * sizeof(float)));
-        HIPCHK(h->t_sin_lat.reserve(g.n_lat * sizeof(float)));
-        if (!t.dx.empty()) {
-            HIPCHK(h->t_lon_deg.reserve(g.n_lon * sizeof(double)));
-            HIPCHK(h->t_dx.reserve(g.n_lat * sizeof(double)));
-        }
-        // h->tabs outlives the copies (it is only rebuilt after the next key mismatch, behind this same stream)
-        HIPCHK(hipStreamSynchronize(h->stream));
-        HIPCHK(hipMemcpyAsync(h->t_sin_lon.p, t.sin_lon.data(), g.n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->t_cos_lon.p, t.cos_lon.data(), g.n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->t_cos_lat.p, t.cos_lat.data(), g.n_lat * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(h->t_sin_lat.p, t.sin_lat.data(), g.n_lat * sizeof(float), hipMemcpyHostToDevice, h->stream));
-        if (!t.dx.empty()) {
-            HIPCHK(hipMemcpyAsync(h->t_lon_deg.p, t.lon_deg.data(), g.n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(h->t_dx.p, t.dx.data(), g.n_lat * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        }
-        HIPCHK(hipStreamSynchronize(h->stream));
-        h->tabs_key.swap(key);
+// the host tables `t` to the device (reads nothing else)
+int upload_tables(coreg_handle* h, const CarrTables& t) {
+    const size_t n_lon = t.sin_lon.size(), n_lat = t.sin_lat.size();
+    HIPCHK(h->t_sin_lon.reserve(n_lon * sizeof(double)));
+    HIPCHK(h->t_cos_lon.reserve(n_lon * sizeof(double)));
+    HIPCHK(h->t_cos_lat.reserve(n_lat * sizeof(float)));
+    HIPCHK(h->t_sin_lat.reserve(n_lat * sizeof(float)));
+    if (!t.dx.empty()) {
+        HIPCHK(h->t_lon_deg.reserve(n_lon * sizeof(double)));
+        HIPCHK(h->t_dx.reserve(n_lat * sizeof(double)));
     }
-    dev->sin_lon = h->t_sin_lon.as<double>();
-    dev->cos_lon = h->t_cos_lon.as<double>();
-    dev->cos_lat = h->t_cos_lat.as<float>();
-    dev->sin_lat = h->t_sin_lat.as<float>();
-    dev->n_lon = g.n_lon;
-    dev->n_lat = g.n_lat;
+    // `t` outlives the copies (it is only rebuilt after the next key mismatch, behind this same stream)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(h->t_sin_lon.p, t.sin_lon.data(), n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->t_cos_lon.p, t.cos_lon.data(), n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->t_cos_lat.p, t.cos_lat.data(), n_lat * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->t_sin_lat.p, t.sin_lat.data(), n_lat * sizeof(float), hipMemcpyHostToDevice, h->stream));
+    if (!t.dx.empty()) {
+        HIPCHK(hipMemcpyAsync(h->t_lon_deg.p, t.lon_deg.data(), n_lon * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(h->t_dx.p, t.dx.data(), n_lat * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return COREG_OK;
+}
+
+// the device tables of h->tabs as kernel arguments (the per-launch members: set_carr_common)
+CarrDev carr_dev(const coreg_handle* h) {
+    CarrDev dev;
+    std::memset(&dev, 0, sizeof(dev));
+    dev.sin_lon = h->t_sin_lon.as<double>();
+    dev.cos_lon = h->t_cos_lon.as<double>();
+    dev.cos_lat = h->t_cos_lat.as<float>();
+    dev.sin_lat = h->t_sin_lat.as<float>();
+    dev.n_lon = (int)h->tabs.sin_lon.size();
+    dev.n_lat = (int)h->tabs.sin_lat.size();
     const bool rotated = !h->tabs.dx.empty();
-    dev->dx = rotated ? h->t_dx.as<double>() : nullptr;
-    dev->lon_deg = rotated ? h->t_lon_deg.as<double>() : nullptr;
-    dev->l0 = h->tabs.l0;
+    dev.dx = rotated ? h->t_dx.as<double>() : nullptr;
+    dev.lon_deg = rotated ? h->t_lon_deg.as<double>() : nullptr;
+    dev.l0 = h->tabs.l0;
+    return dev;
+}
+
+// The Carrington tables of grid `g` under hdr's CRLN_OBS, on the host (h->tabs, behind their key: sweep_plan.hpp
+// update_carr_tables) and on the device.  rot: differential rotation of the image they are for (null: none)
+int upload_carr_tables(coreg_handle* h, const coreg_carr_grid& g, const coreg_wcs2d& hdr, const coreg_diffrot* rot = nullptr) {
+    if (g.n_lon < 1 || g.n_lat < 1) return fail(h, COREG_EINVAL, "carrington grid: n_lon/n_lat must be >= 1");
+    if (update_carr_tables(h->tabs, h->tabs_key, g, hdr.crln_obs, rot, !h->tabs_uploaded)) {
+        h->tabs_uploaded = false;
+        RETCHK(upload_tables(h, h->tabs));
+        h->tabs_uploaded = true;
+    }
     return COREG_OK;
 }
 
@@ -682,28 +673,6 @@ void set_carr_common(CarrDev* dev, const CarrCommon& c) {
     dev->sr = c.sr;
     dev->cdelt1 = c.cdelt1;
     dev->cdelt2 = c.cdelt2;
-}
-
-// the affine part of a launch's uniforms (MODE_CAR: pixel <-> native angles); the other members are left as they are
-void set_affine(LaunchU* u, const Affine2& a) {
-    u->m00 = a.m00;
-    u->m01 = a.m01;
-    u->m10 = a.m10;
-    u->m11 = a.m11;
-    u->b0 = a.b0;
-    u->b1 = a.b1;
-}
-
-// host mirror of kernels.hpp carr_term (tile-shape heuristics only)
-bool carr_term_host(const CarrTables& t, const CarrCommon& c, int i, int j, double* t0, double* t1) {
-    const double cl = (double)t.cos_lat[j], y = (double)t.sin_lat[j];
-    const double x = cl * t.sin_lon[i], z = cl * t.cos_lon[i];
-    const double zz = z * c.cb + y * c.sb, yy = y * c.cb - z * c.sb;
-    const double yr = yy * c.cr - x * c.sr, xr = x * c.cr + yy * c.sr;
-    const double zd = c.dist - zz;
-    *t0 = std::atan(xr / zd) * kRad2Deg * 3600.0 / c.cdelt1;
-    *t1 = std::atan(yr / zd) * kRad2Deg * 3600.0 / c.cdelt2;
-    return zz >= 0.0;
 }
 
 template <typename F>

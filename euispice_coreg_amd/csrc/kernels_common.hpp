@@ -1,15 +1,11 @@
 // Part of csrc/kernels.hpp (included from there in order; round 6 split by concern, no behaviour change): launch constants, argument structs, the per-lag maps (translation, homography, sphere rotation), scipy's spline weights.
 #pragma once
+#include "launch_uniforms.hpp"  // kTilePts, kBlock, MODE_*, LaunchU: what the host's planner shares with the kernels (no HIP in it)
 namespace coreg {
 
-#ifndef COREG_TILE_PTS
-#define COREG_TILE_PTS 1024
-#endif
 #ifndef COREG_POINT_GROUPS
 #define COREG_POINT_GROUPS 4
 #endif
-constexpr int kTilePts = COREG_TILE_PTS;  // grid points per tile
-constexpr int kBlock = 256;     // lag slots per batch (one lag per lane, 4 waves)
 constexpr int kPointGroups = COREG_POINT_GROUPS; // a sweep workgroup = kPointGroups x kBlock threads sharing one LDS window
 constexpr int kSweepThreads = kBlock * kPointGroups;
 constexpr int kChunk = 4;       // points per scalar-load chunk
@@ -21,21 +17,6 @@ constexpr int kNumSums = 6;     // n, sum a, sum b, sum aa, sum bb, sum ab
 // their squares, k_precompute)
 struct __attribute__((aligned(32))) Pt {
     double b0, b1, a, pad;
-};
-
-// MODE_HOMOGRAPHY_SERIES: same map, denominator 1 + eps inverted as 1 - eps + eps^2 (host guarantees |eps| < 4e-6, i.e.
-// a truncation error below 1e-16 relative); MODE_HOMOGRAPHY divides exactly (any field of view)
-// MODE_CAR: plate-carree maps on both sides (align_using_initial_carrington): base coordinates = native (phi, theta) of
-// the target pixel [radians], per lag a rotation of the sphere (h[0..8]) between the two native frames, then
-// (atan2, asin) and the affine native -> pixel map of the shifted header (uniform per launch, LaunchU)
-enum { MODE_TRANSLATE = 0, MODE_HOMOGRAPHY = 1, MODE_HOMOGRAPHY_SERIES = 2, MODE_CAR = 3 };
-// per-launch uniforms of the coordinate map / sampler that are not per-lane
-struct LaunchU {
-    double m00, m01, m10, m11, b0, b1;  // MODE_CAR: native (phi, theta) [rad] -> 0-based pixel
-    int order_rt;                       // ORDER == ORDER_RT kernels: the spline order (0..5)
-    int h_incr;                         // HOMOGRAPHY[_SERIES], order 2, interior LDS visits: advance along runs (tile_points)
-    double box_c;     // MODE_CAR: (tile half-diagonal [rad])^2 / 2 x pixels per radian of the shifted map (car_tile_margin)
-    double pole_sep;  // MODE_CAR: largest angle [rad] between the native poles of the target and of a shifted map
 };
 
 // MODE_CAR: pixels by which the image of a tile may leave the bounding box of its four mapped corners.  The map

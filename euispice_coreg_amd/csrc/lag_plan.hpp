@@ -1,5 +1,5 @@
 // How the (CRVAL1 x CRVAL2) lag plane of a sweep is cut into batches of <= 256 lags (one k_sweep workgroup each) and how
-// the lags of a batch are laid over its 256 slots.  Plain C++ with no HIP dependency: included by host_plan.hpp (part
+// the lags of a batch are laid over its 256 slots.  Plain C++ with no HIP dependency: included by sweep_plan.hpp (part
 // of libcoreg_hip.so's one translation unit), and tests/native/lag_plan_rules.cpp walks it on the host under sanitizers.
 #pragma once
 #include <algorithm>
