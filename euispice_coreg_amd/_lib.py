@@ -272,6 +272,7 @@ SYMBOLS = [
     ("coreg_last_counts", C.c_int, [_P, _P, C.c_int]),
     ("coreg_last_visit_counts", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("coreg_last_tap_fix", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("coreg_last_sweep_variant", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("coreg_set_option", C.c_int, [_P, C.c_char_p, C.c_int64]),
     ("coreg_shift_header", C.c_int,
      [_WP, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int, _WP]),
@@ -949,6 +950,12 @@ class CoregHandle(_ImageIntake):
         return {"visits": c[0], "lds": c[1], "interior": c[2], "all_finite": c[3], "refined_lag_points": c[4],
                 "flagged_not_refined": c[5]}
 
+    def last_sweep_variant(self) -> dict:
+        """The k_sweep instantiation the last launch of the last sweep ran (csrc/sweep_variant.hpp; index -1: none)."""
+        v = (C.c_int32 * 7)()
+        self._chk(self._lib.coreg_last_sweep_variant(self._h, v))
+        return {"index": v[0], "mode": v[1], "order": v[2], "f32": bool(v[3]), "round": bool(v[4]), "resid": bool(v[5]),
+                "pitch": v[6]}
 
     def last_tap_fix(self) -> dict:
         """Odd spline orders, helioprojective frame: samples of the last sweep re-evaluated with wcslib's arithmetic."""

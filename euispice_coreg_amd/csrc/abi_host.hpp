@@ -40,6 +40,12 @@ int coreg_last_tap_fix(coreg_handle* h, int64_t* counts3) {
     return COREG_OK;
 }
 
+int coreg_last_sweep_variant(coreg_handle* h, int32_t* v7) {
+    if (!h || !v7) return COREG_EINVAL;
+    for (int k = 0; k < 7; ++k) v7[k] = h->last_variant[k];
+    return COREG_OK;
+}
+
 int coreg_car_tile_margin(const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_shifted, int32_t tile_w,
                           double tile_abs_lat_rad, double* margin_px) {
     if (!hdr_target || !hdr_shifted || !margin_px || tile_w < 1 || tile_w > kTilePts) return COREG_EINVAL;

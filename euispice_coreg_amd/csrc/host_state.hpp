@@ -156,6 +156,9 @@ struct coreg_handle {
     int64_t opt_tap_fix = 1, opt_tap_cap = 1 << 24;
     DevBuf tap_count, tap_segq, tap_list, tap_skip, tap_seg_slot, tap_seg_begin, tap_pixel, tap_xw, tap_yw;
     long long tap_last[3] = {0, 0, 0};  // last sweep: samples listed, lag-points concerned, 1 = list overflowed (no fix)
+    // the k_sweep instantiation of the last launch of the last sweep (coreg_last_sweep_variant): index in
+    // sweep_variant::kSweepVariants, mode, order, f32, round, resid, pitch; index -1: that sweep launched none
+    int last_variant[7] = {-1, 0, 0, 0, 0, 0, 0};
     // multi-GPU point sharding (coreg_set_option "shard_world" / "shard_rank"): a sweep covers this rank's share of the
     // tile groups and leaves the six sums per lag slot in `sums`; coreg_finalize_sums turns the all-reduced sums into
     // coefficients

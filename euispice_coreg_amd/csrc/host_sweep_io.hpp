@@ -22,6 +22,7 @@ int begin_sweep(coreg_handle* h, long long n_out, double* corr_out, int out_on_d
     h->sums_slots = 0;
     h->pending_n_out = 0;
     h->tap_last[0] = h->tap_last[1] = h->tap_last[2] = 0;  // (coreg_last_tap_fix speaks of THIS sweep)
+    h->last_variant[0] = -1;                               // (and coreg_last_sweep_variant)
     // A sweep that failed between upload_plan and end_sweep leaves its prologue armed and may have enqueued kernels that
     // still read its pinned plan slot: forget the prologue, and let everything it enqueued finish before that slot (it
     // was never handed on) is written again.

@@ -71,6 +71,8 @@ int launch_k_sweep(coreg_handle* h, const SweepLaunchSpec& L, const SweepArgs& a
     hipLaunchKernelGGL(k->fn, grid, dim3(kSweepThreads), lds_bytes, h->stream, a);
     HIPCHK(hipEventRecord(ev->b, h->stream));
     HIPCHK(hipGetLastError());
+    const int rec[7] = {at, v.mode, v.order, v.f32 ? 1 : 0, v.round ? 1 : 0, v.resid ? 1 : 0, v.pitch};
+    std::copy(rec, rec + 7, h->last_variant);  // (coreg_last_sweep_variant: a diagnostic, host memory only)
     return COREG_OK;
 }
 

@@ -364,6 +364,13 @@ int coreg_last_visit_counts(coreg_handle* h, int64_t* counts6);
  * concerned, counts3[2] = 1 when the list exceeded "tap_cap" and nothing was applied. */
 int coreg_last_tap_fix(coreg_handle* h, int64_t* counts3);
 
+/* Which of the sweep kernel's instantiations (csrc/sweep_variant.hpp) the LAST launch of the last coreg_sweep_carrington /
+ * coreg_sweep_helioprojective call ran: v7 = index in the instantiation list, mode (0 translation = Carrington,
+ * 1 homography by exact division, 2 homography by the series inverse, 3 plate carree), compiled spline order (0: read at
+ * run time), float32 pixels, samples rounded to float32, residus accumulators, compile-time LDS pitch (0: per visit).
+ * index -1: that call launched no sweep kernel.  Host memory only: no device work, no wait. */
+int coreg_last_sweep_variant(coreg_handle* h, int32_t* v7);
+
 /* Options (name -> integer value), in three groups.  A caller of the drop-in API needs NONE of them: every default is
  * the behaviour that reproduces the reference; euispice_coreg_amd/hdrshift sets only "async_upload" (when a reference
  * preparation follows the upload) and the sharding options of group B.

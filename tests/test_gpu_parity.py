@@ -204,9 +204,11 @@ def test_homography_exact_division_path_equals_series_path(gpu_handle):
     gpu_handle.set_option("h_series", 0)
     try:
         exact = H.gpu_helio(gpu_handle, small, hs, large, hl, lags)
+        assert gpu_handle.last_sweep_variant()["mode"] == 1  # (sweep_variant.hpp kHomography: exact division ran)
     finally:
         gpu_handle.set_option("h_series", 1)
     series = H.gpu_helio(gpu_handle, small, hs, large, hl, lags)
+    assert gpu_handle.last_sweep_variant()["mode"] == 2  # (kHomographySeries: the host proved eps_max < 4e-6)
     H.assert_corr_close(exact, want, 1e-7, "helio, exact division")
     H.assert_corr_close(series, want, 1e-7, "helio, series inverse")
     assert np.nanmax(np.abs(exact - series)) <= 1e-9
@@ -231,6 +233,8 @@ def test_homography_sweeps_advanced_along_runs_equal_the_per_sample_map(gpu_hand
             gpu_handle.set_option("h_incr", incr)
             maps.append(H.gpu_helio(gpu_handle, small, hs, large, hl, lags))
             assert gpu_handle.last_visit_counts()["interior"] > 0
+            # (sweep_variant.hpp: kHomographySeries = 2, kHomography = 1 -- the variant the parameter names did run)
+            assert gpu_handle.last_sweep_variant()["mode"] == (2 if series else 1)
     finally:
         gpu_handle.set_option("h_series", 1)
         gpu_handle.set_option("h_incr", 1)
