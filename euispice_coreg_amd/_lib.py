@@ -20,7 +20,7 @@ COREG_EINVAL, COREG_EHIP, COREG_ESTATE, COREG_ENOTIMPL, COREG_ENOMEM = -1, -2, -
 COREG_F32, COREG_F64 = 0, 1
 PROJ_TAN, PROJ_CAR = 0, 1
 METHOD_CORRELATION, METHOD_RESIDUS, METHOD_RESIDUS_MASKED = 0, 1, 2
-METHOD_MUTUAL_INFORMATION = 3  # (the pixel-lag sweep only: coreg_pixels_set_bins)
+METHOD_MUTUAL_INFORMATION = 3  # (the pixel-lag sweep: coreg_pixels_set_bins; sweep_carrington: coreg_sweep_set_bins)
 CDELT_INTENDED, CDELT_REFERENCE = 0, 1
 
 
@@ -261,6 +261,7 @@ SYMBOLS = [
     ("coreg_sweep_carrington", C.c_int,
      [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.POINTER(Lags), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P,
       C.c_int]),
+    ("coreg_sweep_set_bins", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_sweep_helioprojective", C.c_int,
      [_P, _WP, _WP, C.POINTER(Lags), C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, _P, C.c_int]),
     ("coreg_sums_size", C.c_int, [_P, C.POINTER(C.c_int64)]),
@@ -654,6 +655,14 @@ class CoregHandle(_ImageIntake):
         return out
 
     # -- sweeps
+    def sweep_set_bins(self, edges_small, edges_large):
+        """coreg_sweep_set_bins: the edge lists of `sweep_carrington(..., method=METHOD_MUTUAL_INFORMATION)` -- edges_small
+        for the samples of the image to align, edges_large for the reference on the grid (1 to 31 finite, strictly
+        increasing float64 entries each); they stay with the handle until set again."""
+        es = np.ascontiguousarray(edges_small, dtype=np.float64).ravel()
+        el = np.ascontiguousarray(edges_large, dtype=np.float64).ravel()
+        self._chk(self._lib.coreg_sweep_set_bins(self._h, es.ctypes.data, len(es), el.ctypes.data, len(el)))
+
     def sweep_carrington(self, hdr_small, grid: Grid, solar_r, lags: LagSet, order=2, method=METHOD_CORRELATION,
                          cdelt_semantics=CDELT_INTENDED, lag_begin=0, lag_end=None, out_dev_ptr=None):
         lag_end = lags.size if lag_end is None else int(lag_end)

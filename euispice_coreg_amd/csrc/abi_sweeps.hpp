@@ -7,17 +7,31 @@ namespace {
 // An entry point = its checks (open_sweep), the Carrington table upload where it has one, its planner (sweep_plan.hpp:
 // what to launch, decided on the host without the device) and run_sweep_plan (the one launch loop).
 
-// The checks and set-up of the public sweeps, in this order: method, order, the entry point's own checks (`own_checks`),
+// The method of a header-shift sweep.  mi_ok: the entry point has a mutual-information score (the Carrington sweep alone:
+// its plans have no noise-decided samples, and the corrections of the others are slabs of Pearson sums, sweep_plan.hpp);
+// it is then refused here for what it lacks on this handle -- a grid share, its bins (host_sweep_mi.hpp).
+int check_method(coreg_handle* h, int method, bool mi_ok) {
+    if (method == COREG_METHOD_MUTUAL_INFORMATION) {
+        if (!mi_ok)
+            return fail(h, COREG_ENOTIMPL, "method COREG_METHOD_MUTUAL_INFORMATION is a score of coreg_sweep_carrington only: the "
+                                           "noise-decided samples of the other header-shift sweeps are corrected as Pearson sums");
+        return check_sweep_mi(h);
+    }
+    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS && method != COREG_METHOD_RESIDUS_MASKED)
+        return fail(h, COREG_ENOTIMPL,
+                    "method must be COREG_METHOD_CORRELATION, COREG_METHOD_RESIDUS or COREG_METHOD_RESIDUS_MASKED");
+    return COREG_OK;
+}
+
+// The checks and set-up of the public sweeps, in this order: method (check_method), order, the entry point's own checks (`own_checks`),
 // the lag set with the combination range the entry point took off the handle, the device, the reference-on-grid shape
 // (`grid_w` x `grid_h`, `grid_what` names it), begin_sweep.  With nothing to sweep (call->n_out == 0) the caller returns
 // end_sweep at once.
 template <typename OwnChecks>
 int open_sweep(coreg_handle* h, ComboRange combo, OwnChecks own_checks, const coreg_lags* lags, int order, int method,
-               int sem, int64_t lag_begin, int64_t lag_end, int grid_w, int grid_h, const char* grid_what,
+               bool mi_ok, int sem, int64_t lag_begin, int64_t lag_end, int grid_w, int grid_h, const char* grid_what,
                double* corr_out, int out_on_device, SweepCall* call) {
-    if (method != COREG_METHOD_CORRELATION && method != COREG_METHOD_RESIDUS && method != COREG_METHOD_RESIDUS_MASKED)
-        return fail(h, COREG_ENOTIMPL,
-                    "method must be COREG_METHOD_CORRELATION, COREG_METHOD_RESIDUS or COREG_METHOD_RESIDUS_MASKED");
+    RETCHK(check_method(h, method, mi_ok));
     RETCHK(check_order(h, order));
     RETCHK(own_checks());
     RETCHK(check_lags(h, lags, &call->d, lag_begin, lag_end, combo));
@@ -123,6 +137,11 @@ int run_sweep_plan(coreg_handle* h, const SweepCall& call, const SweepPlan& plan
             trace("run_sweep_plan: single-sample scan done");
         }
         SweepLaunchSpec sl = sweep_launch(call, L.mode, L.slot_off, L.n_batches, n_tiles);
+        if (call.method == COREG_METHOD_MUTUAL_INFORMATION) {
+            // (plan_carrington's launches only: MODE_TRANSLATE, nothing noise-decided, no re-evaluation)
+            RETCHK(launch_sweep_mi(h, sl, plan.outidx.data() + L.slot_off));
+            continue;
+        }
         if (car) sl.car_inv = &L.car_inv;
         sl.fix = &fix;
         sl.pitch_sel = plan.pitch;
@@ -170,7 +189,7 @@ int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const 
         return COREG_OK;
     };
     SweepCall call;
-    RETCHK(open_sweep(h, combo, own_checks, lags, order, method, cdelt_semantics, lag_begin, lag_end, grid->n_lon,
+    RETCHK(open_sweep(h, combo, own_checks, lags, order, method, true, cdelt_semantics, lag_begin, lag_end, grid->n_lon,
                       grid->n_lat, "the Carrington grid", corr_out, out_on_device, &call));
     if (call.n_out == 0) return close_sweep(h, call);  // (nothing to fill)
     RETCHK(upload_carr_tables(h, *grid, *hdr_small, h->has_rot_small ? &h->rot_small : nullptr));
@@ -191,12 +210,18 @@ int coreg_sweep_helioprojective(coreg_handle* h, const coreg_wcs2d* hdr_target, 
         return check_wcs(h, hdr_small, false);
     };
     SweepCall call;
-    RETCHK(open_sweep(h, combo, own_checks, lags, order, method, cdelt_semantics, lag_begin, lag_end,
+    RETCHK(open_sweep(h, combo, own_checks, lags, order, method, false, cdelt_semantics, lag_begin, lag_end,
                       hdr_target->naxis1, hdr_target->naxis2, "hdr_target NAXIS1/NAXIS2", corr_out, out_on_device, &call));
     if (call.n_out == 0) return close_sweep(h, call);  // (nothing to fill)
     if (hdr_small->proj == COREG_PROJ_CAR) return run_sweep_plan(h, call, plan_car(call, *hdr_target, *hdr_small, sweep_env(h)));
     trace("sweep_helioprojective: enter (checks done)");
     return run_sweep_plan(h, call, plan_tan(call, *hdr_target, *hdr_small, sweep_env(h)));
+}
+
+int coreg_sweep_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small, const double* edges_large,
+                         int32_t n_large) {
+    if (!h) return COREG_EINVAL;
+    return sweep_mi_set_bins(h, edges_small, n_small, edges_large, n_large);
 }
 
 int coreg_sums_size(coreg_handle* h, int64_t* n_doubles) {

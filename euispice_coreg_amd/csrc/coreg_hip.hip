@@ -41,6 +41,7 @@ using namespace coreg;
 #include "host_fix_launch.hpp"   // re-evaluation work space, k_finalize, fix kernels of a launch
 #include "sweep_variant.hpp"     // the list of k_sweep instantiations and the rule that picks one (no HIP in it)
 #include "host_sweep_launch.hpp" // SweepLaunchSpec, launch_sweep
+#include "host_sweep_mi.hpp"     // the Carrington sweep's mutual-information score: bins, refusals, one launch
 #include "host_fix_lists.hpp"    // uploads of the plan's border pixels / flags, the single-sample scan
 #include "host_sweep_io.hpp"     // begin / end of a sweep call, stats, plan upload
 #include "host_context.hpp"      // iterative-context sweep: frame stack, per-lag plan, launches
@@ -190,6 +191,9 @@ int coreg_set_option(coreg_handle* h, const char* name, int64_t value) {
     } else if (n == "patch_w") {
         if (value < 0 || value > kBlock) return fail(h, COREG_EINVAL, "patch_w must be in [0, 256]");
         h->opt_patch_w = value;
+    } else if (n == "mi_chunks") {
+        if (value < 0 || value > kMiMaxChunks) return fail(h, COREG_EINVAL, "mi_chunks must be in [0, 64]");
+        h->opt_mi_chunks = value;
     } else if (n == "lds_bytes") {
         // 160 KiB per CU minus the kernel's static LDS
         if (value < 1024 || value > 159 * 1024) return fail(h, COREG_EINVAL, "lds_bytes must be in [1 KiB, 159 KiB]");

@@ -145,6 +145,8 @@ int context_sweep(coreg_handle* h, const coreg_wcs2d* target4, const coreg_wcs2d
     const ComboRange combo = take_combo_range(h);
     if (combo.begin != 0 || combo.end != 0)
         return fail(h, COREG_EINVAL, "sweep_context: combo_begin/combo_end do not apply to this sweep");
+    if (method == COREG_METHOD_MUTUAL_INFORMATION)
+        return fail(h, COREG_ENOTIMPL, "sweep_context: COREG_METHOD_MUTUAL_INFORMATION is a score of coreg_sweep_carrington only");
     ContextState* c = h->ctx.get();
     if (!c) return fail(h, COREG_ESTATE, "sweep_context: coreg_set_context_frames has not been called");
     if (!h->small.p) return fail(h, COREG_ESTATE, "sweep_context: coreg_set_small (the SPICE image) has not been called");

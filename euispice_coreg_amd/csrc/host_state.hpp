@@ -184,6 +184,14 @@ struct coreg_handle {
     std::vector<PendingFinalize> pending_fin;
     DevBuf fin_outidx;        // copy of the output indices of the pending sharded sweep
     long long pending_n_out = 0;
+    // COREG_METHOD_MUTUAL_INFORMATION of coreg_sweep_carrington (host_sweep_mi.hpp): the edge lists of
+    // coreg_sweep_set_bins, kept until set again (a state of their own: coreg_pixels_set_bins has the pixel-lag sweep's);
+    // the global histograms uint32 [slot][cell] of a launch, zeroed per launch and sized by the largest one; the dynamic
+    // LDS each k_sweep_mi instantiation has been allowed on this handle's device so far
+    std::vector<double> mi_edges_small, mi_edges_large;
+    DevBuf mi_hist;
+    size_t mi_lds[6] = {0, 0, 0, 0, 0, 0};
+    int64_t opt_mi_chunks = 0;  // chunks of the tile list per group of 16 lag slots; 0: the planner's choice
 
     // options
     int64_t opt_crop_reference = 1;

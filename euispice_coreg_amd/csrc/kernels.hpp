@@ -26,6 +26,7 @@
 #include "kernels_sweep.hpp"     // Taps, gathers, point_lag, tile_points, k_sweep
 #include "kernels_fix.hpp"       // noise-decided samples: border / parity / tap scan + fix
 #include "kernels_finalize.hpp"  // k_finalize, k_refine_list, k_refine
+#include "kernels_sweep_mi.hpp"  // the Carrington sweep's mutual-information score: per-lag joint histograms, integer counters
 #include "kernels_context.hpp"   // iterative-context sweep (per-lag synthetic rasters)
 #include "kernels_pixels.hpp"    // integer pixel-lag sweep (pxlshift): resample, two-pass sweep, finalize
 #include "kernels_pixels_mi.hpp" // ... its mutual-information score: joint histograms in LDS, one pass

@@ -1090,8 +1090,11 @@ int coreg_multi_prepare_reference_helioprojective_tiled(coreg_multi* m, const co
     });
 }
 
+// (a per-device histogram path is not part of the multi-device driver: the single-device handle has the score)
+static const char* const kMultiNoMi = "multi sweep: COREG_METHOD_MUTUAL_INFORMATION is not implemented on multi-device handles";
 int coreg_multi_sweep_carrington(coreg_multi* m, const coreg_wcs2d* hdr_small, const coreg_carr_grid* grid, double solar_r,
                                  const coreg_lags* lags, int order, int method, int cdelt_semantics, double* corr_out) {
+    if (m && method == COREG_METHOD_MUTUAL_INFORMATION) return mfail(m, COREG_ENOTIMPL, kMultiNoMi);
     return multi_sweep(m, lags, corr_out, true, [&](int k, const coreg_lags* l, int64_t lo, int64_t hi, double* out_dev) {
         return out_dev ? coreg_sweep_carrington(m->h[k], hdr_small, grid, solar_r, l, order, method, cdelt_semantics, lo,
                                                 hi, out_dev, 1)
@@ -1103,6 +1106,7 @@ int coreg_multi_sweep_carrington(coreg_multi* m, const coreg_wcs2d* hdr_small, c
 int coreg_multi_sweep_helioprojective(coreg_multi* m, const coreg_wcs2d* hdr_target, const coreg_wcs2d* hdr_small,
                                       const coreg_lags* lags, int order, int method, int cdelt_semantics, double* corr_out) {
     // (TAN headers: one launch whatever the lag set; plate-carree maps: one launch per (cdelt, crota) combination)
+    if (m && method == COREG_METHOD_MUTUAL_INFORMATION) return mfail(m, COREG_ENOTIMPL, kMultiNoMi);
     const bool per_combo = hdr_target && hdr_target->proj == COREG_PROJ_CAR;
     return multi_sweep(m, lags, corr_out, per_combo, [&](int k, const coreg_lags* l, int64_t lo, int64_t hi, double* out_dev) {
         return out_dev ? coreg_sweep_helioprojective(m->h[k], hdr_target, hdr_small, l, order, method, cdelt_semantics, lo,

@@ -22,6 +22,11 @@ surface.  Differences, all deliberate and listed in DESIGN.md:
     the MINIMUM (quirk Q8: the reference's `residus` forgets its NaN mask and is NaN on any practical grid; it stays
     so).  After a sweep `self.last_counts` holds the per-lag sample counts (6-D like the map); `min_overlap` (an
     integer count, or a fraction in (0, 1) of the sweep's largest count) turns lag-points with fewer samples into NaN.
+  * `align_using_carrington(method="mutual_information", bins=...)`: the mutual information (nats) of the joint histogram
+    of the reference on the Carrington grid and the resampled image to align over `bins`, best entry = the MAXIMUM -- for
+    two instruments whose intensities are not linearly related (include/coreg_hip.h: coreg_sweep_set_bins states the rule).
+    The Carrington frame only: the other `align_using_*` raise NotImplementedError for it.  `self.last_bins` holds the
+    edges used.
 There is no CPU fallback: without the HIP library / a GPU the sweep raises.
 """
 from __future__ import annotations
@@ -43,6 +48,12 @@ _METHODS = {"correlation": _lib.METHOD_CORRELATION,
             "residus_masked": _lib.METHOD_RESIDUS_MASKED}
 
 
+# A method of `align_using_carrington` only, recognised beside `_METHODS` (the helioprojective and plate-carree sweeps
+# correct their noise-decided samples as slabs of Pearson sums: no histogram there, `library_method` has none)
+MUTUAL_INFORMATION = "mutual_information"
+DEFAULT_BINS, MAX_BINS = 16, 32
+
+
 def library_method(name):
     """The library's method code of an `align_using_*` method name (alignment.py:549: anything else is not implemented)."""
     if name not in _METHODS:
@@ -61,6 +72,40 @@ def min_overlap_floor(min_overlap, counts=None):
         finite = np.zeros(0) if counts is None else counts[np.isfinite(counts)]
         return float(min_overlap) * float(finite.max()) if finite.size else np.nan
     raise ValueError("min_overlap must be None, an integer >= 1 or a float in (0, 1)")
+
+
+def parse_bins(method, bins):
+    """The `bins` argument of `align_using_carrington`, checked without any image: None for every method but
+    "mutual_information" (`bins` with another method raises ValueError); else an integer 2 <= B <= 32 (None: 16), or the
+    pair (edges_small, edges_large) as `pxlshift.alignment_pixels.check_edges` returns them.  ValueError otherwise."""
+    from ..pxlshift.alignment_pixels import check_edges
+    if method != MUTUAL_INFORMATION:
+        if bins is not None:
+            raise ValueError("bins belongs to method='mutual_information'")
+        return None
+    if bins is None:
+        return DEFAULT_BINS
+    if isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_)):
+        if not 2 <= bins <= MAX_BINS:
+            raise ValueError(f"bins as a number must lie in [2, {MAX_BINS}]")
+        return int(bins)
+    if isinstance(bins, (bool, np.bool_, float, np.floating, str)):
+        raise ValueError("bins must be an integer or a pair (edges_small, edges_large)")
+    try:
+        es, el = bins
+    except (TypeError, ValueError):
+        raise ValueError("bins must be an integer or a pair (edges_small, edges_large)") from None
+    return check_edges(es, "edges_small"), check_edges(el, "edges_large")
+
+
+def default_edges(small_pixels, value_min, value_max, reference_on_grid, n_bins):
+    """(edges_small, edges_large) of `n_bins` quantile bins (`pxlshift.alignment_pixels.quantile_edges`): of the image to
+    align after the thresholds `small_fov_value_min` / `small_fov_value_max` (alignment.py:876-887), and of the prepared
+    reference on the target grid.  Plain numpy on the images, thresholds and grid: no lag, slice or rank enters."""
+    from ..pxlshift.alignment_pixels import quantile_edges
+    small = np.array(small_pixels, dtype=np.float64)
+    hdrutil.set_threshold_minmax_to_nan(small, value_min, value_max)
+    return quantile_edges(small, int(n_bins)), quantile_edges(reference_on_grid, int(n_bins))
 
 
 def apply_min_overlap(corr, counts, min_overlap):
@@ -130,6 +175,8 @@ class Alignment:
             min_overlap_floor(min_overlap)  # (its checks, before anything is loaded)
         self.min_overlap = min_overlap  # lag-points with fewer samples become NaN (apply_min_overlap); None: no floor
         self.last_counts = None         # per-lag sample counts of the last sweep, shaped like its map
+        self.last_bins = None           # (edges_small, edges_large) of the last "mutual_information" sweep
+        self._bins = None               # `bins` of the sweep being run, as parse_bins leaves it
         self.last_sharding = None       # how the last sweep was spread over the GPUs (parallel.lag_sharding)
         # set by the jitter-correction session (jitter_correction/jitter_correction.py):
         self.shard_lags = True          # False: every rank runs whole sweeps (images, not lags, are spread over GPUs)
@@ -172,6 +219,11 @@ class Alignment:
             # goes up as stored, and only the rectangle the target grid can touch
             self.data_large = fits_io.native_pixels(dl)
         return self.data_large
+
+    def _small_pixels_on_host(self):
+        """The pixels of the image to align as loaded (a memory-mapped or tile-compressed data unit decoded on the host)."""
+        d = self.data_small
+        return d.decode() if isinstance(d, (fits_io.RawImage, fits_io.CompressedImage)) else np.asarray(d)
 
     def _reference_tag(self, frame, *what):
         """Identity of a prepared reference: (file identity of the reference image, preparation parameters), or None
@@ -230,10 +282,15 @@ class Alignment:
     # ------------------------------------------------------------------------------------------------------------
     def align_using_carrington(self, lonlims=None, latlims=None, size_deg_carrington=None, shape=None,
                                reference_date=None, method="correlation", method_carrington_reprojection="fa",
-                               return_type="AlignmentResults"):
-        """alignment.py:144-261.  `reference_date` (default: DATE-AVG of the reference image) acts only with
+                               return_type="AlignmentResults", bins=None):
+        """alignment.py:144-261.  `bins` (method "mutual_information" only, ValueError with any other): an integer
+        2 <= B <= 32 (default 16) -- B quantile bins of the image to align after its thresholds and of the prepared
+        reference on the grid for the first `lag_solar_r` (`default_edges`) -- or a pair (edges_small, edges_large) as
+        `pxlshift.alignment_pixels.check_edges` takes them; the edges used are kept as `self.last_bins`.
+        `reference_date` (default: DATE-AVG of the reference image) acts only with
         `differential_rotation="intended"`: each image is then rotated over (its DATE-OBS - reference_date), leap seconds
         inside that interval ignored, at the rate of the band the reference image's WAVELNTH selects (utils/diffrot.py)."""
+        self._bins = parse_bins(method, bins)  # (refused before anything is loaded)
         self.method = method
         self.coordinate_frame = "final_carrington"
         if method_carrington_reprojection == "sunpy":
@@ -364,7 +421,12 @@ class Alignment:
     def _find_best_header_parameters(self, ang2pipi=True, fov_limits=None, remove_fov_limits=None):
         """alignment.py:613-797 on the GPU.  Returns float64 [n_crval1, n_crval2, n_cdelt1, n_cdelt2, n_crota,
         n_solar_r]; lag-points the library could not evaluate are NaN, never 0 (quirk Q9)."""
-        method = library_method(self.method)
+        mi = self.method == MUTUAL_INFORMATION
+        if mi and self.coordinate_frame != "final_carrington":
+            raise NotImplementedError("method='mutual_information' is a score of align_using_carrington only: the border and "
+                                      "near-integer samples of the helioprojective and plate-carree sweeps are corrected as "
+                                      "Pearson sums, which a histogram cannot take")
+        method = _lib.METHOD_MUTUAL_INFORMATION if mi else library_method(self.method)
         device = self.device
         rank, world = parallel.world_info()
         if not self.shard_lags:
@@ -381,7 +443,7 @@ class Alignment:
         # COREG_SINGLE_DEVICE=1 keep the single-device context.
         use_all = (self.parallelism and world == 1 and self.device is None and self.shard_lags
                    and parallel.world_info()[1] == 1 and os.environ.get("COREG_SINGLE_DEVICE", "0") != "1"
-                   and _lib.device_count() > 1)
+                   and _lib.device_count() > 1 and not mi)  # (the histograms are the single-device handle's)
         if use_all:
             h = _lib.shared_multi_handle()
         else:
@@ -467,6 +529,8 @@ class Alignment:
         # (the helioprojective sweep runs ONE launch whatever the lag set; the others one per (cdelt, crota) combination)
         per_combo = self.coordinate_frame != "final_helioprojective"
         mode = parallel.lag_sharding(lags.shape, world, per_combo)
+        if mi and mode == "points":
+            mode = "slices"  # (six sums can be all-reduced; per-rank histograms are not part of the library)
         self.last_sharding = mode
         my_lags, lo, hi = lags, 0, lags.size
         combos = None  # (c_lo, c_hi): this rank's run of (cdelt1, cdelt2, crota) combinations, None = all of them
@@ -534,6 +598,13 @@ class Alignment:
                     return h.sweep_helioprojective(t, self.hdr_small, my_lags, order=self.order, method=method,
                                                    cdelt_semantics=sem, lag_begin=lo, lag_end=hi)
             finite_pixels()
+            if mi and kk == 0:
+                edges = self._bins
+                if isinstance(edges, int):
+                    edges = default_edges(self._small_pixels_on_host(), self.small_fov_value_min, self.small_fov_value_max,
+                                          h.get_reference_on_grid((grid.n_lat, grid.n_lon), np.float64), edges)
+                h.sweep_set_bins(*edges)
+                self.last_bins = edges
             # (the sample counts of this rank's share are gathered the way its coefficients are)
             if mode == "points":
                 part = parallel.point_sharded_sweep(h, run, lags.size)

@@ -18,7 +18,7 @@ import numpy as np
 
 from .. import _lib
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
-from .alignment import Alignment, apply_min_overlap, library_method
+from .alignment import Alignment, apply_min_overlap, library_method, parse_bins
 
 
 def _angstrom(v):
@@ -71,9 +71,12 @@ class AlignmentSpice(Alignment):
         return self._wrap(results, return_type, restore_units=True)
 
     def align_using_carrington(self, lonlims, latlims, size_deg_carrington=None, shape=None, reference_date=None,
-                               method="correlation", return_type="AlignmentResults", coefficient_l3=None):
-        """alignment_spice.py:122-180.  (The reference reads hdr_small before it is loaded when only
+                               method="correlation", return_type="AlignmentResults", coefficient_l3=None, bins=None):
+        """alignment_spice.py:122-180.  `method="mutual_information"` and its `bins`: as on
+        `Alignment.align_using_carrington` -- the score for a SPICE line against an imager passband of another temperature.
+        (The reference reads hdr_small before it is loaded when only
         `size_deg_carrington` is given; here the SPICE header is loaded first.)"""
+        self._bins = parse_bins(method, bins)  # (refused before anything is loaded)
         self.reference_date = reference_date
         self.extend_pixel_size = False
         self.method = method

@@ -37,7 +37,7 @@ from ..hdrshift.alignment import apply_min_overlap, library_method, min_overlap_
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
 
 _RETURN_TYPES = ("corr", "PixelAlignmentResults")
-MUTUAL_INFORMATION = "mutual_information"  # a method of the pixel-lag sweep only: hdrshift's `library_method` has none
+MUTUAL_INFORMATION = "mutual_information"  # hdrshift's `library_method` has none: `align_using_carrington` knows it beside those
 DEFAULT_BINS, MAX_BINS = 16, 32
 
 

@@ -44,8 +44,9 @@ extern "C" {
  * Meant to be read with the per-lag sample counts (coreg_last_counts). */
 #define COREG_METHOD_RESIDUS_MASKED 2
 /* Mutual information of the joint histogram of the two images over given bins, in nats; best entry = maximum.  A score of
- * the integer pixel-lag sweep only (coreg_pixels_set_bins, coreg_pixels_sweep_method, coreg_pixels_sweep_tiles below); the
- * header-shift sweeps refuse it like any unknown method. */
+ * the integer pixel-lag sweep (coreg_pixels_set_bins, coreg_pixels_sweep_method, coreg_pixels_sweep_tiles below) and of
+ * coreg_sweep_carrington (coreg_sweep_set_bins below, which states its rule); coreg_sweep_helioprojective and
+ * coreg_sweep_context return COREG_ENOTIMPL for it: their noise-decided samples are corrected as slabs of Pearson sums. */
 #define COREG_METHOD_MUTUAL_INFORMATION 3
 
 /* CDELT lag semantics */
@@ -308,6 +309,32 @@ int coreg_set_small_rotation(coreg_handle* h, const coreg_diffrot* rot);
 int coreg_sweep_carrington(coreg_handle* h, const coreg_wcs2d* hdr_small, const coreg_carr_grid* grid,
                            double solar_r, const coreg_lags* lags, int order, int method, int cdelt_semantics,
                            int64_t lag_begin, int64_t lag_end, double* corr_out, int out_on_device);
+/* COREG_METHOD_MUTUAL_INFORMATION of coreg_sweep_carrington: the edge lists, edges_small[n_small] for the samples of the
+ * image to align, edges_large[n_large] for the reference on the Carrington grid; each 1 to 31 entries, finite, strictly
+ * increasing (n + 1 bins), else COREG_EINVAL and the lists set before stay.  State of the handle, apart from
+ * coreg_pixels_set_bins': the lists hold for every later sweep until set again, whatever images are set.
+ * The score of a lag-point, A the reference on the grid, B the image to align resampled through the lag-point's header
+ * (the coordinates, bounds rule, mirrored taps and NaN poisoning of the Pearson sweep at that order):
+ *   kept pairs  isfinite(A) & isfinite(B) -- exactly the pairs of the Pearson sums, so the counts (coreg_last_counts) of a
+ *               mutual-information sweep equal those of a COREG_METHOD_CORRELATION sweep of the same inputs, entry for
+ *               entry.  (The pixel-lag sweep keeps an infinite pixel; this one does not.)
+ *   bins        i = the number of edges_small entries <= B, j = the number of edges_large entries <= A
+ *               (np.searchsorted(edges, v, side="right")), of the RAW values: the reference-on-grid value as stored, the
+ *               sample as interpolated -- never a value a pivot was subtracted from and added to again
+ *   score       n_ij the count of kept pairs in cell (i, j), r_i, c_j, n its row sums, column sums and total:
+ *               MI = sum over n_ij > 0 of (n_ij / n) log((n_ij n) / (r_i c_j)), float64, natural logarithm (nats), the terms
+ *               of a row added in the order of j and the rows in the order of i (csrc/pixels_bins.hpp); best entry =
+ *               maximum; NaN for n = 0, and the count is then 0
+ * Integer counters only (no floating-point atomics): the bits of a lag-point depend on the images, the grid, the edges and
+ * that lag-point alone -- not on its slot or batch, a lag_begin / lag_end slice, a combination range, or how the grid
+ * points were dealt to workgroups ("mi_chunks").  Never re-evaluated ("refine"), like the residus methods.
+ * coreg_sweep_carrington with this method: COREG_ESTATE before coreg_sweep_set_bins; COREG_ENOTIMPL on a grid share
+ * ("shard_world" > 1: six sums can be all-reduced, per-rank histograms are not) and from the coreg_multi_* sweeps;
+ * lag_begin / lag_end, "combo_begin" / "combo_end", out_on_device, coreg_last_counts and the rotation tables work as for
+ * the other methods. */
+int coreg_sweep_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small, const double* edges_large,
+                         int32_t n_large);
+
 /* hdr_target: header whose pixel grid the reference image lives on (the unshifted small header in the
  * parallelism=True path, alignment.py:1000; the large header in the serial path, quirk Q1).  Both headers TAN
  * (helioprojective), or both CAR: Carrington maps, align_using_initial_carrington (alignment.py:344-399), hdr_target =
@@ -434,6 +461,8 @@ int coreg_last_sweep_variant(coreg_handle* h, int32_t* v7);
  *   "lds_bytes"    dynamic LDS per workgroup for the float64 gather window (default and max 159 KiB)
  *   "pitch"        -1 (default, auto): compile-time LDS row pitch of the order-2 / order-3 Carrington kernels; 0 per-visit
  *   "skew"         accepted and ignored (a row skew against bank conflicts, measured slower in round 2)
+ *   "mi_chunks"    0 (default: the planner's choice, csrc/sweep_mi_plan.hpp) or 1..64: chunks the tile list of a
+ *                  mutual-information launch is cut in per group of 16 lag slots (bit-identical results at any value)
  *   "patch_w"      0 (default, auto) or the maximum width, in CRVAL1 lags, of a workgroup's lag patch
  *   "taper_frac"   -1 (default, automatic) / 0 equal shares of the grid points per tile group / n: the last n/1024 of the
  *                  groups get linearly smaller shares (down to "taper_min"/1024, default 128) and the others more;
