@@ -354,7 +354,21 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
         if (MODE == MODE_CAR) apply_car_vec(hm, cu, b0, b1, isa, nx, ny);  // (b0, b1, isa) = unit vector
         else apply_map<MODE>(hm, cu, b0, b1, nx, ny);
     }
-    if (INTERIOR || ((nx >= 0.0) & (nx <= wmax) & (ny >= 0.0) & (ny <= hmax))) {
+    // The bounds rule 0 <= n <= max.  On the LDS path of the translation it is ONE unsigned compare of bit patterns per
+    // axis: non-negative doubles order like their bit patterns, and a set sign bit (negative) or an all-ones exponent
+    // (NaN: the padding lanes) lies above the pattern of any finite max >= 0.  The one value the two forms disagree on is
+    // -0.0 (>= 0, sign bit set), and a sum is -0.0 under round-to-nearest only when BOTH terms are: the lane origin
+    // never is -- the planner writes it as (crpix - 1) - d, a difference, which is -0.0 only for (-0.0) - (+0.0), and
+    // crpix - 1 is itself a difference with a non-zero subtrahend (sweep_plan.hpp, plan_carrington).  The mapped modes
+    // can produce -0.0 (a product) and keep the four compares, as does the global-memory path.
+    bool inb;
+    if constexpr (MODE == MODE_TRANSLATE && LDS) {
+        inb = (__builtin_bit_cast(unsigned long long, nx) <= __builtin_bit_cast(unsigned long long, wmax)) &
+              (__builtin_bit_cast(unsigned long long, ny) <= __builtin_bit_cast(unsigned long long, hmax));
+    } else {
+        inb = (nx >= 0.0) & (nx <= wmax) & (ny >= 0.0) & (ny <= hmax);
+    }
+    if (INTERIOR || inb) {
         int sx, sy;
         double wx[N], wy[N];
         double v = 0.0;

@@ -621,6 +621,8 @@ inline SweepPlan plan_carrington(const SweepCall& call, const coreg_wcs2d& hdr_s
             const double v2 = hdr_small.crval2 + lags->crval2[slots.i2[s]];  // alignment.py:412
             const double dx = rc * v1 + rs * v2;
             const double dy = -rs * v1 + rc * v2;
+            // (never -0.0: a difference whose minuend, itself a difference, is not -0.0 -- k_sweep's bounded loop tests
+            // the bounds rule on the bit pattern of X0 + t0 and relies on it, kernels_sweep.hpp point_lag)
             const double x0 = (hc.crpix1 - 1) - dx / hc.cdelt1;
             const double y0 = (hc.crpix2 - 1) - dy / hc.cdelt2;
             params[pbase + s] = x0;
