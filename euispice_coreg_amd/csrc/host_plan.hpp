@@ -129,7 +129,8 @@ int launch_precompute(coreg_handle* h, const PrecomputeArgs& a, int n_tiles, int
     (void)with_prologue;
     hipLaunchKernelGGL(k_tile_list, dim3(1), dim3(1024), 0, h->stream, (const int*)a.tile_count, n_tiles, n_groups,
                        h->tile_list.as<int>(), h->tile_cum.as<int>(), h->group_first.as<int>(),
-                       h->tile_info.as<long long>(), tmin, tfrac);
+                       h->tile_info.as<long long>(), tmin, tfrac, (const double*)a.tile_bbox,
+                       h->visit_rec.as<VisitRec>());
     // (no closing event: the sweep launch that follows opens with one, and that is where this interval ends --
     // collect_stats; one marker packet less between the kernels of a sweep)
     ev->b_is_next_sweep = true;
@@ -150,6 +151,7 @@ int reserve_tiles(coreg_handle* h, int n_tiles) {
     HIPCHK(h->group_first.reserve(2 * 1024 * sizeof(int) + 64));  // [0, 1024): first list entry; [1024, ...): first unit
     HIPCHK(h->tile_info.reserve(8 * sizeof(long long)));
     HIPCHK(h->tile_bbox.reserve((size_t)n_tiles * 4 * sizeof(double)));
+    HIPCHK(h->visit_rec.reserve(((size_t)n_tiles + 1) * sizeof(VisitRec)));  // one per list entry + the sentinel
     return COREG_OK;
 }
 

@@ -104,6 +104,7 @@ struct coreg_handle {
     int pin_img_next = 0;
     // precompute outputs
     DevBuf pts, tile_count, tile_list, tile_cum, group_first, tile_info, tile_bbox;
+    DevBuf visit_rec;  // [non-empty tiles + 1] VisitRec: what k_sweep reads per tile visit (k_tile_list)
     DevBuf rf_fix_slab;  // [kNumSums][n_slots]: a launch's noise-decided samples about the flagged slots' own pivots
     DevBuf counters;  // [0]: lag-points re-evaluated by k_finalize during the sweep in flight (reset by its prologue)
     // sweep

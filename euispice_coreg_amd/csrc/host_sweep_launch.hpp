@@ -88,6 +88,7 @@ SweepArgs sweep_args(const coreg_handle* h, const SweepLaunchSpec& L, int n_grou
     a.group_first = h->group_first.as<int>();
     a.tile_info = h->tile_info.as<long long>();
     a.tile_bbox = h->tile_bbox.as<double>();
+    a.visit_rec = h->visit_rec.as<VisitRec>();
     a.lane_params = L.params_dev(h);
     a.n_slots = L.n_slots();
     a.n_batches = L.n_batches;

@@ -376,8 +376,19 @@ __global__ void __launch_bounds__(256) k_precompute(const PrecomputeArgs a) {
 //   kChunk * kPointGroups points (tile_cum[n_nonempty] = total);  group_first[g] = list entry in which the units of
 //   tile group g start when the total is cut in n_groups equal shares;
 //   info[0] = non-empty tiles, info[1] = kept points, info[2] = work units;  info[3..6] = 0: k_sweep adds its tile
-//   visits there (all, LDS-staged, interior, all-finite interior -- coreg_last_visit_counts).
+//   visits there (all, LDS-staged, interior, all-finite interior -- coreg_last_visit_counts);
+//   visit_rec[k] = list entry k as one record for k_sweep (VisitRec below), visit_rec[n_nonempty] = the sentinel.
 constexpr int kUnitPts = kChunk * kPointGroups;
+// What k_sweep needs to open the visit of list entry k, in one aligned 64-byte record (one scalar-cache line, read ahead
+// of the visit through the scalar path): tile_cum[k], tile_list[k], tile_count[tile] and tile_bbox[tile].  Entry n_list
+// is a sentinel whose tile_cum is the total: no group's share reaches it, so the reader needs no bounds test on k.
+// The separate arrays stay for k_sweep_mi, k_refine and the fix kernels.
+struct alignas(64) VisitRec {
+    int tile_cum, tile, count, pad;
+    double bbox[4];  // min0, max0, min1, max1 (k_precompute)
+    double fill[2];
+};
+static_assert(sizeof(VisitRec) == 64, "one record per 64-byte line");
 // Where tile group g's share of the `total` work units starts.  taper_frac = 0: equal shares.  Otherwise the last
 // taper_frac / 1024 of the groups get linearly smaller shares, down to taper_min / 1024 of a full one, and the others
 // proportionally more: the groups are dispatched in increasing order, so small late workgroups even out the end of a
@@ -401,7 +412,8 @@ __host__ __device__ inline long long group_start(int g, long long total, int n_g
 }
 __global__ void __launch_bounds__(1024) k_tile_list(const int* __restrict__ tile_count, int n_tiles, int n_groups,
                                                     int* tile_list, int* tile_cum, int* group_first, long long* info,
-                                                    int taper_min, int taper_frac) {
+                                                    int taper_min, int taper_frac,
+                                                    const double* __restrict__ tile_bbox, VisitRec* visit_rec) {
     __shared__ int wcnt[16];
     __shared__ int wunits[16];
     __shared__ long long wpts[16];
@@ -442,6 +454,16 @@ __global__ void __launch_bounds__(1024) k_tile_list(const int* __restrict__ tile
         if (nz) {
             tile_list[off + rank] = t;
             tile_cum[off + rank] = uoff + uincl - units;
+            // (k_precompute, the launch before this one, wrote the box of every non-empty tile)
+            VisitRec r;
+            r.tile_cum = uoff + uincl - units;
+            r.tile = t;
+            r.count = c;
+            r.pad = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r.bbox[k] = tile_bbox[(size_t)t * 4 + k];
+            r.fill[0] = r.fill[1] = 0.0;
+            visit_rec[off + rank] = r;
         }
         __syncthreads();
         if (threadIdx.x == 0) {
@@ -461,6 +483,9 @@ __global__ void __launch_bounds__(1024) k_tile_list(const int* __restrict__ tile
     const int n_list = s_base, total = s_units;
     if (threadIdx.x == 0) {
         tile_cum[n_list] = total;
+        VisitRec r = {};
+        r.tile_cum = total;  // sentinel: >= the end of every group's share
+        visit_rec[n_list] = r;
         info[0] = n_list;
         info[1] = s_pts;
         info[2] = total;

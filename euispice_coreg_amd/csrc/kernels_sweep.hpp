@@ -12,6 +12,7 @@ struct SweepArgs {
     const int* group_first;      // first list entry of each tile group
     long long* tile_info;  // [0] = non-empty tiles, [1] = kept points, [2] = work units, [3..6] visit counters
     const double* tile_bbox;
+    const VisitRec* visit_rec;  // [non-empty tiles + 1]: the four arrays above per list entry, what a tile visit reads
     const double* lane_params;  // SoA [NP][n_slots]; TRANSLATE: X0, Y0; HOMOGRAPHY: h0..h8
     long long n_slots;          // n_batches * 256
     int n_batches;
@@ -505,6 +506,90 @@ __device__ __forceinline__ void load_pt_uniform(const Pt* __restrict__ p, Pt& ou
 #endif
 }
 
+// The visit record of one tile-list entry (k_tile_list) through the scalar data path, like a point above: the address is
+// wave-uniform, and read through the constant address space the eleven dwords in use come as scalar loads
+// (s_load_dwordx2 + s_load_dword + s_load_dwordx8 on this compiler) that the compiler tracks: it places their s_waitcnt
+// itself, and csrc/check_isa.py's rule for s_load_dwordx8 holds for them as for any other.
+#ifndef COREG_VISIT_LAGBOX
+#define COREG_VISIT_LAGBOX 1  // MODE_TRANSLATE: lag extents reduced once per launch (0: the per-visit box reduction)
+#endif
+#ifndef COREG_VISIT_FMA
+#define COREG_VISIT_FMA 1  // order 2: one fma per staged element (0: subtract the pivot, then scale)
+#endif
+struct Visit {
+    int ubase, tile, cnt;
+    double bx0, bx1, by0, by1;
+};
+__device__ __forceinline__ void load_visit_uniform(const VisitRec* __restrict__ p, Visit& out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) int* ConstI32;
+    typedef const __attribute__((address_space(4))) double* ConstF64;
+    ConstI32 qi = (ConstI32)(const int*)p;
+    ConstF64 qd = (ConstF64)(const double*)p;
+    out.ubase = qi[0];
+    out.tile = qi[1];
+    out.cnt = qi[2];
+    out.bx0 = qd[2];
+    out.bx1 = qd[3];
+    out.by0 = qd[4];
+    out.by1 = qd[5];
+#else
+    out.ubase = p->tile_cum;
+    out.tile = p->tile;
+    out.cnt = p->count;
+    out.bx0 = p->bbox[0];
+    out.bx1 = p->bbox[1];
+    out.by0 = p->bbox[2];
+    out.by1 = p->bbox[3];
+#endif
+}
+// A record read ahead has to outlive the sample loop of the visit in between, and k_sweep has no SGPR to spare (the
+// allocator would spill it, or something the loop uses, into vector lanes).  It is parked by hand: eleven dwords in
+// lanes 0..10 of ONE VGPR, written once the scalar load has landed and read back at the head of the next visit.
+template <int LANE>
+__device__ __forceinline__ void write_lane(unsigned& w, unsigned x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("v_writelane_b32 %0, %1, %2" : "+v"(w) : "s"(x), "n"(LANE));
+#else
+    (void)w;
+    (void)x;
+#endif
+}
+__device__ __forceinline__ unsigned park_visit(const Visit& v, unsigned park) {
+    const unsigned long long b[4] = {__builtin_bit_cast(unsigned long long, v.bx0), __builtin_bit_cast(unsigned long long, v.bx1),
+                                     __builtin_bit_cast(unsigned long long, v.by0), __builtin_bit_cast(unsigned long long, v.by1)};
+    unsigned w = park;
+    write_lane<0>(w, (unsigned)v.ubase);
+    write_lane<1>(w, (unsigned)v.tile);
+    write_lane<2>(w, (unsigned)v.cnt);
+    write_lane<3>(w, (unsigned)b[0]);
+    write_lane<4>(w, (unsigned)(b[0] >> 32));
+    write_lane<5>(w, (unsigned)b[1]);
+    write_lane<6>(w, (unsigned)(b[1] >> 32));
+    write_lane<7>(w, (unsigned)b[2]);
+    write_lane<8>(w, (unsigned)(b[2] >> 32));
+    write_lane<9>(w, (unsigned)b[3]);
+    write_lane<10>(w, (unsigned)(b[3] >> 32));
+    return w;
+}
+__device__ __forceinline__ void unpark_visit(unsigned park, Visit& v) {
+    const int w = (int)park;
+    v.ubase = __builtin_amdgcn_readlane(w, 0);
+    v.tile = __builtin_amdgcn_readlane(w, 1);
+    v.cnt = __builtin_amdgcn_readlane(w, 2);
+    double b[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane(w, 3 + 2 * k);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane(w, 4 + 2 * k);
+        b[k] = __builtin_bit_cast(double, ((unsigned long long)hi << 32) | (unsigned long long)lo);
+    }
+    v.bx0 = b[0];
+    v.bx1 = b[1];
+    v.by0 = b[2];
+    v.by1 = b[3];
+}
+
 // Walk this point-group's share of the compacted points of one tile: chunks of kChunk points, chunk c belongs to
 // point-group (c % kPointGroups).  Point data are wave-uniform: the loads below use uniform addresses (scalar loads).
 template <int MODE, int ORDER, typename TS, bool LDS, bool ROUND, bool RESID, bool INTERIOR = false, int PITCH = 0,
@@ -673,6 +758,7 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
     // (a wave can only write slot k again after the barrier of the visit in between, which every wave reaches after
     // it has read slot k)
     // (only the first kBlock / 64 waves write: the kPointGroups copies of each lag are identical)
+    // (MODE_TRANSLATE: slot 0 holds the lag extents of the workgroup, written once before the tile loop -- kLagBox)
     constexpr int kLagWaves = kBlock / 64;
     __shared__ double wred2[2][kLagWaves][4];
     // "this wave staged a NaN or an infinity", per visit parity like the boxes (written before the barrier that ends the
@@ -726,7 +812,6 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
     // this tile group's share of the work: units [u_lo, u_hi) of the concatenated compacted points
     const int u_lo = a.group_first[1024 + group];  // (k_tile_list: group_start)
     const int u_hi = a.group_first[1024 + group + 1];
-    const int n_list = (int)a.tile_info[0];
     const double pivot_b = a.pivots[1];
     // LDS byte address of the window (through the LDS address space: the generic pointer's null check would otherwise
     // be re-evaluated with every sample's address)
@@ -736,20 +821,74 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
     const unsigned win = 0;
 #endif
 
-    for (int tl = a.group_first[group]; tl < n_list && u_lo < u_hi; ++tl) {
-        const int ubase = a.tile_cum[tl];
+    // MODE_TRANSLATE: the box of a visit is (box of the tile's points) + (extent of this workgroup's lags), and the second
+    // term does not change during the launch: it is reduced ONCE, here, with the NaN-ignoring fmin / fmax (padding lanes
+    // carry NaN and drop out; a workgroup of padding lanes only keeps NaN, and every visit is culled as before).  Per
+    // visit the box is then four additions.  Rounding a sum is monotone in either term, so
+    // min_l fl(b + x_l) = fl(b + min_l x_l) and likewise for max: the box is the one the per-visit reduction over
+    // fl(b + x_l) gave, except that a zero can come out with the other sign -- which no use below can see: the
+    // comparisons with 0.0, W - 1, H - 1 and kClear treat -0.0 as 0.0, and floor(fmax(., 0.0)) converts either to 0.
+    constexpr bool kLagBox = MODE == MODE_TRANSLATE && COREG_VISIT_LAGBOX;
+    double lx0 = 0.0, lx1 = 0.0, ly0 = 0.0, ly1 = 0.0;
+    if constexpr (kLagBox) {
+        lx0 = lx1 = px0;
+        ly0 = ly1 = py0;
+        for (int o = 32; o > 0; o >>= 1) {
+            lx0 = fmin(lx0, __shfl_xor(lx0, o));
+            lx1 = fmax(lx1, __shfl_xor(lx1, o));
+            ly0 = fmin(ly0, __shfl_xor(ly0, o));
+            ly1 = fmax(ly1, __shfl_xor(ly1, o));
+        }
+        // (the kPointGroups copies of each lag are identical: the waves of point-group 0 cover every lag)
+        if (lane == 0 && pg == 0) {
+            wred2[0][lw][0] = lx0;
+            wred2[0][lw][1] = lx1;
+            wred2[0][lw][2] = ly0;
+            wred2[0][lw][3] = ly1;
+        }
+        __syncthreads();  // (wred2 is not written again in this mode)
+        lx0 = fmin(fmin(wred2[0][0][0], wred2[0][1][0]), fmin(wred2[0][2][0], wred2[0][3][0]));
+        lx1 = fmax(fmax(wred2[0][0][1], wred2[0][1][1]), fmax(wred2[0][2][1], wred2[0][3][1]));
+        ly0 = fmin(fmin(wred2[0][0][2], wred2[0][1][2]), fmin(wred2[0][2][2], wred2[0][3][2]));
+        ly1 = fmax(fmax(wred2[0][0][3], wred2[0][1][3]), fmax(wred2[0][2][3], wred2[0][3][3]));
+    }
+
+    // Tile visits.  What opens a visit -- work units before the list entry, tile, point count, box of the tile's points
+    // -- is one VisitRec (k_tile_list).  The record of entry tl + 1 is read through the scalar path while visit tl is
+    // staged and parked in a VGPR (park_visit) until visit tl + 1 opens: no dependent load stands before a visit's
+    // first row loads.  The sentinel record after the last entry ends the walk of the last group (ubase = total >= u_hi).
+    int tl = a.group_first[group];
+    unsigned park = 0;
+    {
+        Visit first;
+        load_visit_uniform(a.visit_rec + tl, first);
+        park = park_visit(first, park);
+    }
+    for (; u_lo < u_hi; ++tl) {
+        Visit cur;
+        unpark_visit(park, cur);
+        const int ubase = cur.ubase;
         if (ubase >= u_hi) break;
-        const int tile = a.tile_list[tl];
-        const int cnt = a.tile_count[tile];
+        Visit nxt;  // (the break above keeps tl + 1 <= the sentinel's index)
+        load_visit_uniform(a.visit_rec + tl + 1, nxt);
+        const int tile = cur.tile;
+        const int cnt = cur.cnt;
         const int p_begin = max(u_lo - ubase, 0) * kUnitPts;
         const int p_end = min((u_hi - ubase) * kUnitPts, cnt);
-        if (p_begin >= p_end) continue;
-        const double* bb = a.tile_bbox + (size_t)tile * 4;
-        const double bx0 = bb[0], bx1 = bb[1], by0 = bb[2], by1 = bb[3];
+        if (p_begin >= p_end) {
+            park = park_visit(nxt, park);
+            continue;
+        }
+        const double bx0 = cur.bx0, bx1 = cur.bx1, by0 = cur.by0, by1 = cur.by1;
 
         // bounding box, in small-image pixels, of (tile points) x (this workgroup's lags)
         double mnx, mxx, mny, mxy;
-        if (MODE == MODE_TRANSLATE) {
+        if constexpr (kLagBox) {
+            mnx = bx0 + lx0;
+            mxx = bx1 + lx1;
+            mny = by0 + ly0;
+            mxy = by1 + ly1;
+        } else if (MODE == MODE_TRANSLATE) {
             mnx = bx0 + px0;
             mxx = bx1 + px0;
             mny = by0 + py0;
@@ -778,29 +917,40 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
                 mxy += margin;
             }
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            mnx = fmin(mnx, __shfl_xor(mnx, o));
-            mxx = fmax(mxx, __shfl_xor(mxx, o));
-            mny = fmin(mny, __shfl_xor(mny, o));
-            mxy = fmax(mxy, __shfl_xor(mxy, o));
-        }
-        double(*wred)[4] = wred2[visit & 1];
         int* wdirt = wdirty[visit & 1];
-        ++visit;
-        if (lane == 0 && pg == 0) {
-            wred[lw][0] = mnx;
-            wred[lw][1] = mxx;
-            wred[lw][2] = mny;
-            wred[lw][3] = mxy;
+        if constexpr (!kLagBox) {
+            for (int o = 32; o > 0; o >>= 1) {
+                mnx = fmin(mnx, __shfl_xor(mnx, o));
+                mxx = fmax(mxx, __shfl_xor(mxx, o));
+                mny = fmin(mny, __shfl_xor(mny, o));
+                mxy = fmax(mxy, __shfl_xor(mxy, o));
+            }
+            double(*wred)[4] = wred2[visit & 1];
+            if (lane == 0 && pg == 0) {
+                wred[lw][0] = mnx;
+                wred[lw][1] = mxx;
+                wred[lw][2] = mny;
+                wred[lw][3] = mxy;
+            }
+            __syncthreads();  // every wave has left the previous tile's LDS window; the boxes of this visit are in place
+            // the kPointGroups copies of each lag are identical: the waves of point-group 0 cover every lag
+            mnx = fmin(fmin(wred[0][0], wred[1][0]), fmin(wred[2][0], wred[3][0]));
+            mxx = fmax(fmax(wred[0][1], wred[1][1]), fmax(wred[2][1], wred[3][1]));
+            mny = fmin(fmin(wred[0][2], wred[1][2]), fmin(wred[2][2], wred[3][2]));
+            mxy = fmax(fmax(wred[0][3], wred[1][3]), fmax(wred[2][3], wred[3][3]));
         }
-        __syncthreads();  // every wave has left the previous tile's LDS window; the boxes of this visit are in place
-        // the kPointGroups copies of each lag are identical: the waves of point-group 0 cover every lag
-        mnx = fmin(fmin(wred[0][0], wred[1][0]), fmin(wred[2][0], wred[3][0]));
-        mxx = fmax(fmax(wred[0][1], wred[1][1]), fmax(wred[2][1], wred[3][1]));
-        mny = fmin(fmin(wred[0][2], wred[1][2]), fmin(wred[2][2], wred[3][2]));
-        mxy = fmax(fmax(wred[0][3], wred[1][3]), fmax(wred[2][3], wred[3][3]));
+        ++visit;
         // no in-bounds sample possible for this (tile, batch)?  (uniform)
-        if (!(mxx >= 0.0) || !(mnx <= (double)(W - 1)) || !(mxy >= 0.0) || !(mny <= (double)(H - 1))) continue;
+        if (!(mxx >= 0.0) || !(mnx <= (double)(W - 1)) || !(mxy >= 0.0) || !(mny <= (double)(H - 1))) {
+            park = park_visit(nxt, park);
+            continue;
+        }
+        // kLagBox: every wave took the decision above from the same numbers (the record and the launch's lag extents), so
+        // a culled visit needs no barrier; a visit that goes on does: every wave has left the previous tile's LDS window.
+        // wdirty: a wave writes slot (visit & 1) after this barrier and before the one that ends the staging, and reads
+        // it right after that one; whichever visit writes the slot next does so after its own barrier here, which no
+        // wave passes before every wave has arrived, its reads of the earlier visit done.
+        if constexpr (kLagBox) __syncthreads();
         // every (point, lag) of this visit inside the image?  (uniform; the box covers all non-padding lanes.)  The box is
         // made of mapped CORNERS: a pixel between them can come out a few ulp beyond (a whole-pixel lag under an unrotated
         // header puts column 0 at x = -3e-16 between corners at 0.0) -- such a visit must keep the per-sample bounds rule,
@@ -856,6 +1006,8 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
             constexpr int kStage = COREG_STAGE_ROWS, kCols = COREG_STAGE_COLS;
             // the quadratic spline uses doubled weights on both axes (see gather_o2)
             const double scale = ORDER == 2 ? 0.25 : 1.0;
+            constexpr bool kFmaStage = ORDER == 2 && !ROUND && COREG_VISIT_FMA;
+            const double npivot4 = -0.25 * pivot_b;
             // (the row index is wave-uniform: with it in an SGPR the row addresses are scalar arithmetic)
             const int wave_u = __builtin_amdgcn_readfirstlane(wave);
             double poison = 0.0;  // becomes NaN when this lane stages a NaN or an infinity (0 * e)
@@ -885,7 +1037,10 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
                             for (int k = 0; k < kStage; ++k) {
                                 const int r = r0 + k * kWaves;
                                 if (r < wh) {
-                                    const double e = (ROUND ? (double)v[k][j] : (double)v[k][j] - pivot_b) * scale;
+                                    // (order 2 without ROUND: (v - pivot) / 4 in one fma -- the scale is a power of two,
+                                    // so the single rounding of v/4 - pivot/4 is the rounding of v - pivot, scaled)
+                                    const double e = (kFmaStage ? fma((double)v[k][j], 0.25, npivot4)
+                                                                : (ROUND ? (double)v[k][j] : (double)v[k][j] - pivot_b) * scale);
                                     lds[r * pitch + c] = e;
                                     if (kCleanPath) poison = fma(e, 0.0, poison);
                                 }
@@ -894,6 +1049,7 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
                     }
                 }
             }
+            park = park_visit(nxt, park);  // (the next visit's record: its load had the staging to land)
             if (kCleanPath && interior) {
                 const int dirty = __ballot(poison != poison) != 0ull;  // (all lanes vote: outside the lane-0 branch)
                 if (lane == 0) wdirt[wave] = dirty;
@@ -937,6 +1093,7 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
           }
         }
         if (!swept) {
+            park = park_visit(nxt, park);
             tile_points<MODE, ORDER, TS, false, ROUND, RESID>(acc, win, img, 0, 0, 0, W, H, px0, py0, 0.0, 0.0, hm, a.car_inv, pts,
                                                               p_begin, p_end, pivot_b, pg);
         }
