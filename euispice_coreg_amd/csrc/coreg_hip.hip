@@ -147,6 +147,11 @@ int coreg_set_option(coreg_handle* h, const char* name, int64_t value) {
     } else if (n == "n_groups") {
         if (value < 0) return fail(h, COREG_EINVAL, "n_groups must be >= 0");
         h->opt_n_groups = value;
+    } else if (n == "sweep_wgs") {
+        // k_sweep's persistent workgroups: at most this many per launch (rounded up to a multiple of 8); 0: as many as
+        // the device holds at a time.  At or above the (group, batch) count every workgroup runs one item.
+        if (value < 0) return fail(h, COREG_EINVAL, "sweep_wgs must be >= 0");
+        h->opt_sweep_wgs = value;
     } else if (n == "skew") {
         (void)value;  // accepted for compatibility: the LDS row skew was measured to lose and is gone
     } else if (n == "shard_world") {

@@ -109,6 +109,18 @@ struct coreg_handle {
     DevBuf counters;  // [0]: lag-points re-evaluated by k_finalize during the sweep in flight (reset by its prologue)
     // sweep
     DevBuf lane_params, out_index, partials, out_dev, tmp_img;
+    // k_sweep's persistent workgroups (launch_sweep): the eight ticket counters of a launch, zeroed on the handle's stream
+    // before every launch; the compute units of the device; and how many workgroups of an instantiation one of them
+    // holds at a given dynamic-LDS size, asked of the runtime once per (kernel, bytes)
+    DevBuf sweep_queue;
+    int n_cus = 0;
+    struct SweepResidency {
+        const void* fn;
+        size_t lds_bytes;
+        int per_cu;
+    };
+    std::vector<SweepResidency> sweep_residency;
+    int64_t opt_sweep_wgs = 0;  // "sweep_wgs": workgroups a k_sweep launch may have resident; 0: CUs x workgroups per CU
     // per-lag sample counts of the last sweep / coreg_finalize_sums / coreg_sweep_context call, laid out like its output
     // (coreg_last_counts); counts_n < 0: no such call yet
     DevBuf counts;

@@ -59,7 +59,30 @@ int raise_dynamic_lds(coreg_handle* h, SweepKernel* k, size_t lds_bytes) {
     return COREG_OK;
 }
 
-int launch_k_sweep(coreg_handle* h, const SweepLaunchSpec& L, const SweepArgs& a, dim3 grid, size_t lds_bytes) {
+// Workgroups of a k_sweep launch of `items` (group, batch) pairs: as many as the device holds at a time -- CUs x the
+// workgroups of this instantiation one CU holds at this dynamic-LDS size, the runtime's figure, asked once per (kernel,
+// bytes) and handle -- or the "sweep_wgs" option, and never more than there are items; rounded up to a multiple of 8, the
+// XCD slots of the item numbering.  (items is a multiple of 8, so the grid never exceeds it.)
+int sweep_grid(coreg_handle* h, const SweepKernel* k, size_t lds_bytes, long long items, unsigned* grid) {
+    long long resident = h->opt_sweep_wgs;
+    if (resident <= 0) {
+        if (h->n_cus <= 0) HIPCHK(hipDeviceGetAttribute(&h->n_cus, hipDeviceAttributeMultiprocessorCount, h->device));
+        int per_cu = 0;
+        for (const coreg_handle::SweepResidency& r : h->sweep_residency)
+            if (r.fn == (const void*)k->fn && r.lds_bytes == lds_bytes) per_cu = r.per_cu;
+        if (per_cu <= 0) {
+            HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k->fn, kSweepThreads, lds_bytes));
+            if (per_cu <= 0) return fail(h, COREG_EHIP, "launch_sweep: the device holds no k_sweep workgroup of this LDS size");
+            h->sweep_residency.push_back({(const void*)k->fn, lds_bytes, per_cu});
+        }
+        resident = (long long)h->n_cus * per_cu;
+    }
+    *grid = (unsigned)(8 * ((std::min(items, resident) + 7) / 8));
+    return COREG_OK;
+}
+
+// `a` lacks only the item queue: n_groups8 x 8 groups of this launch, every batch of each
+int launch_k_sweep(coreg_handle* h, const SweepLaunchSpec& L, SweepArgs a, int n_groups8, size_t lds_bytes) {
     const SweepVariant v = sweep_variant::pick_sweep_variant(L.mode, L.order, h->small_f32, L.residus(), L.pitch_sel);
     const int at = sweep_variant::sweep_variant_index(v);
     if (at < 0) return fail(h, COREG_EINVAL, "launch_sweep: no k_sweep instantiation for this mode / order / pitch");
@@ -67,8 +90,18 @@ int launch_k_sweep(coreg_handle* h, const SweepLaunchSpec& L, const SweepArgs& a
     EventPair* ev = next_event(h, h->ev_sweep, h->ev_sweep_used);
     if (!ev) return fail(h, COREG_EHIP, "hipEventCreate failed");
     RETCHK(raise_dynamic_lds(h, k, lds_bytes));
+    a.items8 = n_groups8 * L.n_batches;
+    unsigned grid = 0;
+    RETCHK(sweep_grid(h, k, lds_bytes, 8LL * a.items8, &grid));
+    // The ticket counters are zeroed before EVERY launch, on the launch's stream: a plate-carree or 5-D sweep launches
+    // k_sweep several times behind one k_tile_list, and a launch that failed or a call that was abandoned leaves nothing
+    // the next one depends on.  (64 bytes; a base that moves on from launch to launch would save the memset and would
+    // have to be kept right across every way a call can end.)
+    HIPCHK(h->sweep_queue.reserve(8 * sizeof(unsigned)));
+    a.queue = h->sweep_queue.as<unsigned>();
+    HIPCHK(hipMemsetAsync(a.queue, 0, 8 * sizeof(unsigned), h->stream));
     HIPCHK(hipEventRecord(ev->a, h->stream));
-    hipLaunchKernelGGL(k->fn, grid, dim3(kSweepThreads), lds_bytes, h->stream, a);
+    hipLaunchKernelGGL(k->fn, dim3(grid), dim3(kSweepThreads), lds_bytes, h->stream, a);
     HIPCHK(hipEventRecord(ev->b, h->stream));
     HIPCHK(hipGetLastError());
     const int rec[7] = {at, v.mode, v.order, v.f32 ? 1 : 0, v.round ? 1 : 0, v.resid ? 1 : 0, v.pitch};
@@ -95,6 +128,8 @@ SweepArgs sweep_args(const coreg_handle* h, const SweepLaunchSpec& L, int n_grou
     a.n_groups = n_groups;
     a.group_lo = group_lo;
     a.partials = h->partials.as<double>();
+    a.queue = nullptr;  // (launch_k_sweep)
+    a.items8 = 0;
     a.pivots = h->pivots.as<double>();
     a.use_lds = h->opt_use_lds ? 1 : 0;
     a.clean_path = h->opt_clean_path ? 1 : 0;
@@ -225,7 +260,8 @@ int launch_sweep(coreg_handle* h, const SweepLaunchSpec& L) {
     const SweepArgs a = sweep_args(h, L, n_groups, g_lo, lds_bytes);
     RETCHK(join_small(h));  // the first kernel of the call that reads the image to align
     trace("launch_sweep: launching k_sweep");
-    RETCHK(launch_k_sweep(h, L, a, dim3((unsigned)((long long)g_per * L.n_batches)), lds_bytes));
+    if (g_per % 8 != 0) return fail(h, COREG_EINVAL, "launch_sweep: the groups of a launch must be a multiple of 8");
+    RETCHK(launch_k_sweep(h, L, a, g_per / 8, lds_bytes));
     h->stats.n_sweep_launches++;
     h->stats.used_lds = a.use_lds;
 

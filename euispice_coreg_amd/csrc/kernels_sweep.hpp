@@ -19,6 +19,10 @@ struct SweepArgs {
     int n_groups;  // multiple of 8: the compacted points are cut in n_groups equal shares
     int group_lo;  // first group this launch sweeps (multi-GPU point sharding: a rank's share of the groups; else 0)
     double* partials;  // [groups of this launch][kNumSums][n_slots]
+    // Items: (group, batch) pairs of this launch, numbered per XCD slot s = blockIdx.x & 7 (k_sweep).  A workgroup's first
+    // item is q = blockIdx.x >> 3; the later ones are gridDim.x / 8 + (ticket drawn from queue[s]), until q >= items8.
+    unsigned* queue;  // [8] ticket counters, zero when the launch starts
+    int items8;       // items per XCD slot: (groups of this launch / 8) * n_batches
     const double* pivots;  // device: [0] mean(reference) (already subtracted in aval), [1] mean(small image)
     int use_lds;
     int clean_path;    // 1: interior visits whose window holds only finite values skip the sample mask (point_lag, CLEAN)
@@ -767,16 +771,25 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
     // all-finite interior visits take the variant without the sample mask (point_lag, CLEAN); a float64 image rounded
     // to float32 (ROUND) could overflow to infinity in the rounding, so it keeps the mask
     constexpr bool kCleanPath = MODE != MODE_CAR && !RESID && ORDER != ORDER_RT && !(ROUND && sizeof(TS) == 8);
-    int visit = 0;
     int n_vis = 0, n_vis_lds = 0, n_vis_int = 0, n_vis_clean = 0;  // (uniform: tile visits of this workgroup by kind)
 
-    // XCD-aware block -> (group, batch): blocks with equal blockIdx % 8 share an XCD (round-robin dispatch), so all
-    // lag batches of one tile group land on one XCD and re-use its tiles / image window from that XCD's L2.
-    const int b = blockIdx.x;
-    const int slot8 = b & 7;
-    const int q = b >> 3;
-    const int batch = q % a.n_batches;
-    const int group = a.group_lo + (q / a.n_batches) * 8 + slot8;
+    // Persistent workgroups (round 10).  The launch has as many workgroups as the GPU holds at a time (launch_sweep), and
+    // each runs ITEMS, one after another: an item is one (group, batch) pair, what a workgroup of its own was before.
+    // XCD-aware item -> (group, batch): blocks with equal blockIdx % 8 share an XCD (round-robin dispatch) and draw their
+    // items from that slot's queue, so all lag batches of one tile group land on one XCD and re-use its tiles / image
+    // window from that XCD's L2; a slot's items are numbered batch-fastest, groups in the order of k_tile_list's tapered
+    // shares, as the blocks were.  The first item is static, q = blockIdx.x >> 3; the next is gridDim.x / 8 + a ticket
+    // that thread 0 draws from a.queue[slot] (atomicAdd) while the item's sums are reduced, and the workgroup ends with
+    // the first q >= a.items8.  Nothing waits for another workgroup, so no placement or order of dispatch can stall it;
+    // which workgroup runs an item has no part in the item's arithmetic, and every item writes a slab of its own.
+    // The ticket travels through next_q[item parity]: thread 0 writes it between the two barriers of the reduction
+    // below, every wave reads it after the second.  The slot is written again two items later, behind both barriers
+    // of the item in between, which no wave passes before every wave has read.  (One slot would not do: an item whose
+    // group has an empty share has no barrier before its reduction, and thread 0 could write while a wave still reads.)
+    __shared__ int next_q[2];
+    const int slot8 = blockIdx.x & 7;
+    int q = blockIdx.x >> 3;
+    int item_par = 0;
 
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     // wave w = kPointGroups * (lag-wave) + (point-group).  A CU places waves w, w + 4, w + 8, w + 12 of a 1024-thread
@@ -786,7 +799,25 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
     const int pg = __builtin_amdgcn_readfirstlane(wave % kPointGroups);  // point-group of this wave (uniform)
     const int lw = __builtin_amdgcn_readfirstlane(wave / kPointGroups);  // its lag-wave: lags 64 lw ... 64 lw + 63 of the batch
     const int ls = 64 * lw + lane;                                       // this lane's lag slot within the batch
+
+    const TS* __restrict__ img = (const TS*)a.img;
+    const int W = a.W, H = a.H;
+    const double inf = __builtin_inf();
+    const double pivot_b = a.pivots[1];
+    // LDS byte address of the window (through the LDS address space: the generic pointer's null check would otherwise
+    // be re-evaluated with every sample's address)
+#if defined(__HIP_DEVICE_COMPILE__)
+    const unsigned win = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_raw;
+#else
+    const unsigned win = 0;
+#endif
+
+    // ---- one item per turn (the body of the loop is not indented: it is what the kernel was) ---------------------------
+    while (q < a.items8) {
+    const int batch = q % a.n_batches;
+    const int group = a.group_lo + (q / a.n_batches) * 8 + slot8;
     const long long slot = (long long)batch * kBlock + ls;
+    int visit = 0;
 
     // this lane's lag
     double px0 = 0.0, py0 = 0.0;
@@ -806,23 +837,12 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
 
     Acc acc = {0, 0.0, 0.0, 0.0, 0.0, 0.0};
 
-    const TS* __restrict__ img = (const TS*)a.img;
-    const int W = a.W, H = a.H;
-    const double inf = __builtin_inf();
     // this tile group's share of the work: units [u_lo, u_hi) of the concatenated compacted points
     const int u_lo = a.group_first[1024 + group];  // (k_tile_list: group_start)
     const int u_hi = a.group_first[1024 + group + 1];
-    const double pivot_b = a.pivots[1];
-    // LDS byte address of the window (through the LDS address space: the generic pointer's null check would otherwise
-    // be re-evaluated with every sample's address)
-#if defined(__HIP_DEVICE_COMPILE__)
-    const unsigned win = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)lds_raw;
-#else
-    const unsigned win = 0;
-#endif
 
-    // MODE_TRANSLATE: the box of a visit is (box of the tile's points) + (extent of this workgroup's lags), and the second
-    // term does not change during the launch: it is reduced ONCE, here, with the NaN-ignoring fmin / fmax (padding lanes
+    // MODE_TRANSLATE: the box of a visit is (box of the tile's points) + (extent of this item's lags), and the second
+    // term does not change during the item: it is reduced ONCE, here, with the NaN-ignoring fmin / fmax (padding lanes
     // carry NaN and drop out; a workgroup of padding lanes only keeps NaN, and every visit is culled as before).  Per
     // visit the box is then four additions.  Rounding a sum is monotone in either term, so
     // min_l fl(b + x_l) = fl(b + min_l x_l) and likewise for max: the box is the one the per-visit reduction over
@@ -846,7 +866,11 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
             wred2[0][lw][2] = ly0;
             wred2[0][lw][3] = ly1;
         }
-        __syncthreads();  // (wred2 is not written again in this mode)
+        // wred2[0] is written again by the next item only: behind the two barriers of this item's reduction, which no
+        // wave passes before every wave has arrived there, its extents long in registers.  This barrier is also the one
+        // that keeps the next staging off the reduction scratch of the item before (see the end of the loop), whether or
+        // not the item's first visit is culled.
+        __syncthreads();
         lx0 = fmin(fmin(wred2[0][0][0], wred2[0][1][0]), fmin(wred2[0][2][0], wred2[0][3][0]));
         lx1 = fmax(fmax(wred2[0][0][1], wred2[0][1][1]), fmax(wred2[0][2][1], wred2[0][3][1]));
         ly0 = fmin(fmin(wred2[0][0][2], wred2[0][1][2]), fmin(wred2[0][2][2], wred2[0][3][2]));
@@ -1099,14 +1123,18 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
         }
     }
 
-    if (threadIdx.x == 0) {
-        atomicAdd((unsigned long long*)a.tile_info + 3, (unsigned long long)n_vis);
-        atomicAdd((unsigned long long*)a.tile_info + 4, (unsigned long long)n_vis_lds);
-        atomicAdd((unsigned long long*)a.tile_info + 5, (unsigned long long)n_vis_int);
-        atomicAdd((unsigned long long*)a.tile_info + 6, (unsigned long long)n_vis_clean);
-    }
-    // add the kPointGroups partial sums of every lag in a fixed order (deterministic), one slab per workgroup
+    // the next item's ticket: drawn before the reduction so that the atomic's round trip runs under its first barrier.
+    // (Drawing it at the head of the item's last visit, a whole sample loop earlier, measured the same: 2.8313 against
+    // 2.8344 ms per step, inside the spread -- profiles/r10_ab_persistent.log -- and is not built in.)
+    unsigned ticket = 0;
+    if (threadIdx.x == 0) ticket = atomicAdd(a.queue + slot8, 1u);
+    // add the kPointGroups partial sums of every lag in a fixed order (deterministic), one slab per item.
+    // The scratch is the window's LDS.  It is read after the second barrier by the waves of point-group 0; the next thing
+    // written there is the next item's staging, and a barrier stands before it in every mode: the lag-extent barrier at
+    // the head of the item (kLagBox), else the barrier that opens every visit, culled or not.  An item without a visit
+    // stages nothing and writes the scratch behind its own first barrier here.
     __syncthreads();  // the window is dead: reuse the LDS
+    if (threadIdx.x == 0) next_q[item_par] = (int)(gridDim.x >> 3) + (int)ticket;
     if (pg > 0) {
         double* st = lds + ((size_t)(pg - 1) * kNumSums) * kBlock + ls;
         st[0] = (double)acc.n;
@@ -1135,6 +1163,17 @@ __global__ void __launch_bounds__(kSweepThreads) k_sweep(const SweepArgs a) {
         out[3 * a.n_slots] = saa;
         out[4 * a.n_slots] = sbb;
         out[5 * a.n_slots] = sab;
+    }
+    q = __builtin_amdgcn_readfirstlane(next_q[item_par]);
+    item_par ^= 1;
+    }  // items
+
+    // the visit counters of all the workgroup's items, once
+    if (threadIdx.x == 0) {
+        atomicAdd((unsigned long long*)a.tile_info + 3, (unsigned long long)n_vis);
+        atomicAdd((unsigned long long*)a.tile_info + 4, (unsigned long long)n_vis_lds);
+        atomicAdd((unsigned long long*)a.tile_info + 5, (unsigned long long)n_vis_int);
+        atomicAdd((unsigned long long*)a.tile_info + 6, (unsigned long long)n_vis_clean);
     }
 }
 

@@ -458,6 +458,9 @@ int coreg_last_sweep_variant(coreg_handle* h, int32_t* v7);
  *   "tile_skip"    1 (default) Carrington precompute drops whole tiles that provably miss the cull box; 0 evaluates them
  *   "tile_w"       0 (default, auto) or a power of two in [4, 256]: grid-tile width in points (tile = 1024 pts)
  *   "n_groups"     0 (default, auto): tile groups (partial-sum slabs) per lag batch
+ *   "sweep_wgs"    0 (default): a sweep launch has as many workgroups as the device holds at a time, and each runs
+ *                  (tile group, lag batch) items one after another; n > 0: at most n workgroups (rounded up to a multiple
+ *                  of 8), and at or above the number of items one item per workgroup (bit-identical results at any value)
  *   "lds_bytes"    dynamic LDS per workgroup for the float64 gather window (default and max 159 KiB)
  *   "pitch"        -1 (default, auto): compile-time LDS row pitch of the order-2 / order-3 Carrington kernels; 0 per-visit
  *   "skew"         accepted and ignored (a row skew against bank conflicts, measured slower in round 2)
