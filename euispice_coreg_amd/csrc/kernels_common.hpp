@@ -1,6 +1,7 @@
 // Part of csrc/kernels.hpp (included from there in order; round 6 split by concern, no behaviour change): launch constants, argument structs, the per-lag maps (translation, homography, sphere rotation), scipy's spline weights.
 #pragma once
 #include "launch_uniforms.hpp"  // kTilePts, kBlock, MODE_*, LaunchU: what the host's planner shares with the kernels (no HIP in it)
+#include "spline_last.hpp"      // spline_last_o1 / _o2 / _o3: the last axis of a sample as a polynomial (no HIP in it)
 namespace coreg {
 
 #ifndef COREG_POINT_GROUPS
@@ -137,34 +138,37 @@ __device__ __forceinline__ void apply_map(const H9& m, const LaunchU& u, double 
     else apply_h(m, x, y, ox, oy);
 }
 
-// ---- spline weights of scipy's get_spline_interpolation_weights (ni_splines.c), orders 1 and 2 -----------------
+// ---- spline weights of scipy's get_spline_interpolation_weights (ni_splines.c), compile-time orders 1, 2, 3 ------
+// Spline<ORDER>: eval_x = first tap and weights of the x-axis at the scale the order's last-axis polynomial wants
+// (spline_last.hpp), frac = first tap and fraction of the y-axis, last = the sample from the row sums.
 template <int ORDER>
 struct Spline;
 template <>
 struct Spline<2> {
     static constexpr int N = 3;
-    // first tap index and weights for coordinate c
-    static __device__ __forceinline__ void eval(double c, int& start, double w[3]) {
+    // scipy: w1 = 0.75 - t^2, w0 = 0.5 (0.5 - t)^2, w2 = 1 - w0 - w1 (= 0.5 (0.5 + t)^2 = w0 + t), t = c - floor(c + 1/2);
+    // here HALF of them (spline_last_o2 works with doubled y-weights), in 5 operations, equal to half of scipy's values
+    // to ~1 ulp
+    static __device__ __forceinline__ void eval_x(double c, int& start, double w[3]) {
         const double f = floor(c + 0.5);
         const double t = c - f;
-        // scipy: w1 = 0.75 - t^2, w0 = 0.5 (0.5 - t)^2, w2 = 1 - w0 - w1 (= 0.5 (0.5 + t)^2 = w0 + t); evaluated here
-        // in 5 operations, equal to scipy's values to ~1 ulp
         const double u = t * t;
-        w[1] = 0.75 - u;
-        w[0] = fma(0.5, u, fma(-0.5, t, 0.125));
-        w[2] = w[0] + t;
+        w[1] = fma(-0.5, u, 0.375);
+        w[0] = fma(0.25, u, fma(-0.25, t, 0.0625));
+        w[2] = fma(0.5, t, w[0]);
         start = (int)f - 1;
     }
+    // first tap and the fraction spline_last_o2 takes, in [0, 1)
+    static __device__ __forceinline__ double frac(double c, int& start) {
+        const double h = c + 0.5, f = floor(h);
+        start = (int)f - 1;
+        return h - f;
+    }
+    // the sample from rows accumulated under spline_row_start<2>: r[1] holds R0 + R1
+    static __device__ __forceinline__ double last(const double* r, double f) { return spline_last_o2(r[0], r[1], r[2], f); }
 };
 template <int ORDER>
 __device__ __forceinline__ void spline_weights_t(double t, double* w);
-template <>
-__device__ __forceinline__ void spline_weights_t<2>(double t, double* w) {  // t in [-0.5, 0.5)
-    const double u = t * t;
-    w[1] = 0.75 - u;
-    w[0] = fma(0.5, u, fma(-0.5, t, 0.125));
-    w[2] = w[0] + t;
-}
 template <>
 __device__ __forceinline__ void spline_weights_t<1>(double t, double* w) {  // t in [0, 1)
     w[0] = 1.0 - t;
@@ -173,8 +177,8 @@ __device__ __forceinline__ void spline_weights_t<1>(double t, double* w) {  // t
 
 // cubic B-spline (scipy ni_splines.c, order 3), argument y in [0, 1): SIX times the weights -- 6 w0 = z^3, 6 w1 =
 // 3 y^2 (y - 2) + 4, 6 w2 = 3 z^2 (z - 2) + 4 with z = 1 - y, 6 w3 = 6 - the others (scipy: w3 = 1 - w0 - w1 - w2) -- so
-// that scipy's four divisions by 6 per axis become ONE multiplication of the sample by 1/36 (values equal to scipy's
-// to ~1 ulp; a float64 division costs ~30 instructions here)
+// that scipy's four divisions by 6 per axis become the constants of the last-axis polynomial (spline_last_o3; values
+// equal to scipy's to ~1 ulp; a float64 division costs ~30 instructions here)
 __device__ __forceinline__ void spline_weights6_o3(double y, double* w) {
     const double z = 1.0 - y;
     const double y2 = y * y, z2 = z * z;
@@ -184,32 +188,50 @@ __device__ __forceinline__ void spline_weights6_o3(double y, double* w) {
     w[3] = ((6.0 - w[0]) - w[1]) - w[2];
 }
 template <>
-__device__ __forceinline__ void spline_weights_t<3>(double y, double* w) {  // y in [0, 1)
-    spline_weights6_o3(y, w);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w[k] *= (1.0 / 6.0);
-}
-template <>
 struct Spline<3> {
     static constexpr int N = 4;
-    static __device__ __forceinline__ void eval(double c, int& start, double w[4]) {
+    // the six-fold weights: spline_last_o3 carries the 1/36 of both axes
+    static __device__ __forceinline__ void eval_x(double c, int& start, double w[4]) {
         const double f = floor(c);
-        spline_weights_t<3>(c - f, w);
+        spline_weights6_o3(c - f, w);
         start = (int)f - 1;
+    }
+    static __device__ __forceinline__ double frac(double c, int& start) {
+        const double f = floor(c);
+        start = (int)f - 1;
+        return c - f;
+    }
+    // the sample from rows accumulated under spline_row_start<3>: r[2] holds R0 + R2
+    static __device__ __forceinline__ double last(const double* r, double f) {
+        return spline_last_o3(r[0], r[1], r[2], r[3], f);
     }
 };
 
 template <>
 struct Spline<1> {
     static constexpr int N = 2;
-    static __device__ __forceinline__ void eval(double c, int& start, double w[2]) {
+    static __device__ __forceinline__ void eval_x(double c, int& start, double w[2]) {
         const double f = floor(c);
         const double t = c - f;
         w[0] = 1.0 - t;
         w[1] = t;
         start = (int)f;
     }
+    static __device__ __forceinline__ double frac(double c, int& start) {
+        const double f = floor(c);
+        start = (int)f;
+        return c - f;
+    }
+    static __device__ __forceinline__ double last(const double* r, double f) { return spline_last_o1(r[0], r[1], f); }
 };
+
+// What row r of a sample of the compile-time orders starts its accumulation from: nothing, or the sum of the row that
+// Spline<ORDER>::last wants it added to (spline_last.hpp, spline_chain_row; r is a constant of an unrolled loop)
+template <int ORDER>
+__device__ __forceinline__ double spline_row_start(const double* row, int r) {
+    const int k = spline_chain_row(ORDER, r);
+    return k >= 0 ? row[k] : 0.0;
+}
 
 __device__ __forceinline__ int mirror_idx(int i, int n) {  // scipy: reflect about the edge sample
     i = i < 0 ? -i : i;
@@ -377,24 +399,22 @@ __device__ __forceinline__ double spline_global(const TS* __restrict__ img, int 
     // (an out-of-bounds sample is discarded by every caller; it gathers from the crop's first pixels)
     const double cx = inb ? nx : (double)(cr.x0 + (cr.pitch > 0)), cy = inb ? ny : (double)(cr.y0 + (cr.pitch > 0));
     int sx, sy;
-    double wx[N], wy[N];
-    Spline<ORDER>::eval(cx, sx, wx);
-    Spline<ORDER>::eval(cy, sy, wy);
+    double wx[N], row[N];
+    Spline<ORDER>::eval_x(cx, sx, wx);
+    const double fy = Spline<ORDER>::frac(cy, sy);
     int ix[N], iy[N];
 #pragma unroll
     for (int k = 0; k < N; ++k) {
         ix[k] = mirror_tap<ORDER>(sx + k, W) - cr.x0;
         iy[k] = (mirror_tap<ORDER>(sy + k, H) - cr.y0) * pitch;
     }
-    double acc = 0.0;
 #pragma unroll
     for (int a = 0; a < N; ++a) {
-        double row = 0.0;
+        row[a] = spline_row_start<ORDER>(row, a);
 #pragma unroll
-        for (int b = 0; b < N; ++b) row = fma((double)img[iy[a] + ix[b]], wx[b], row);
-        acc = fma(row, wy[a], acc);
+        for (int b = 0; b < N; ++b) row[a] = fma((double)img[iy[a] + ix[b]], wx[b], row[a]);
     }
-    return acc;
+    return Spline<ORDER>::last(row, fy);  // the last axis as a polynomial in its fraction (spline_last.hpp)
 }
 
 // Same sample from an LDS window that already holds the mirrored one-pixel apron:
@@ -406,19 +426,17 @@ __device__ __forceinline__ double spline_lds(const TS* lds, int pitch, int ox, i
     inb = (nx >= 0.0) & (nx <= (double)(W - 1)) & (ny >= 0.0) & (ny <= (double)(H - 1));
     const double cx = inb ? nx : (double)(ox + 1), cy = inb ? ny : (double)(oy + 1);
     int sx, sy;
-    double wx[N], wy[N];
-    Spline<ORDER>::eval(cx, sx, wx);
-    Spline<ORDER>::eval(cy, sy, wy);
+    double wx[N], row[N];
+    Spline<ORDER>::eval_x(cx, sx, wx);
+    const double fy = Spline<ORDER>::frac(cy, sy);
     const TS* p = lds + (sy - oy) * pitch + (sx - ox);
-    double acc = 0.0;
 #pragma unroll
     for (int a = 0; a < N; ++a) {
-        double row = 0.0;
+        row[a] = spline_row_start<ORDER>(row, a);
 #pragma unroll
-        for (int b = 0; b < N; ++b) row = fma((double)p[a * pitch + b], wx[b], row);
-        acc = fma(row, wy[a], acc);
+        for (int b = 0; b < N; ++b) row[a] = fma((double)p[a * pitch + b], wx[b], row[a]);
     }
-    return acc;
+    return Spline<ORDER>::last(row, fy);
 }
 
 }  // namespace coreg

@@ -259,7 +259,7 @@ template <typename TS>
 __device__ __forceinline__ bool tap_end_lines_differ(const TS* __restrict__ img, int W, int H, int k, double c_other,
                                                      int order, bool near_is_x) {
     const int hw = (order + 1) / 2, half = (order - 1) / 2;
-    const int o0 = (int)floor(c_other) - half;  // first tap along the other axis (Spline<ORDER>::eval)
+    const int o0 = (int)floor(c_other) - half;  // first tap along the other axis (Spline<ORDER>::frac)
     const int n_near = near_is_x ? W : H, n_other = near_is_x ? H : W;
     bool end_lo = true, end_hi = true;  // "every pixel of that end line is finite"
     for (int t = 0; t <= order; ++t) {

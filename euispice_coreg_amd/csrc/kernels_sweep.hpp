@@ -53,11 +53,11 @@ struct Taps<3> {
               "=&v"(t[8])
             : "v"(a0), "v"(a1), "v"(a2));
     }
-    // the wait, placed after everything (w0..w5) depends on has been computed
-    __device__ __forceinline__ void wait_after(double& w0, double& w1, double& w2, double& w3, double& w4, double& w5) {
+    // the wait, placed after the x-weights (w0..w2) have been computed; the y-axis has no weights (spline_last_o2)
+    __device__ __forceinline__ void wait_after(double& w0, double& w1, double& w2) {
         asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
-                       "+v"(t[8]), "+v"(w0), "+v"(w1), "+v"(w2), "+v"(w3), "+v"(w4), "+v"(w5));
+                       "+v"(t[8]), "+v"(w0), "+v"(w1), "+v"(w2));
     }
     // same, and pins (fx, fy) to the issue point: arithmetic that starts from them (the spline weights) is scheduled
     // AFTER the reads have been issued and overlaps their latency
@@ -104,7 +104,6 @@ struct Taps<2> {
     __device__ __forceinline__ void issue_before(unsigned a0, unsigned a1, unsigned a2, double&, double&) {
         issue(a0, a1, a2);
     }
-    __device__ __forceinline__ void wait_after(double&, double&, double&, double&, double&, double&) { wait(); }
     __device__ __forceinline__ void wait() {
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
     }
@@ -151,19 +150,21 @@ struct Taps<4> {
               "n"(2 * P * 8 + 16), "n"(2 * P * 8 + 24), "n"(3 * P * 8), "n"(3 * P * 8 + 8), "n"(3 * P * 8 + 16),
               "n"(3 * P * 8 + 24));
     }
-    __device__ __forceinline__ void wait_after(double* wx, double* wy) {
+    // the wait, after the x-weights and the two multiples of fy that spline_last_o3 takes have been computed
+    __device__ __forceinline__ void wait_after(double* wx, double& f3, double& f12) {
         asm volatile("s_waitcnt lgkmcnt(0)"
                      : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
                        "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]),
-                       "+v"(t[15]), "+v"(wx[0]), "+v"(wx[1]), "+v"(wx[2]), "+v"(wx[3]), "+v"(wy[0]), "+v"(wy[1]),
-                       "+v"(wy[2]), "+v"(wy[3]));
+                       "+v"(t[15]), "+v"(wx[0]), "+v"(wx[1]), "+v"(wx[2]), "+v"(wx[3]), "+v"(f3), "+v"(f12));
     }
 };
 
 // Cubic B-spline sample (reprojection_order = 3, alignment.py:54) from the LDS window at the window-relative coordinate
 // (ux, uy) = coordinate - 1 - window origin: trunc(u) is the window index of the first of the four taps per axis,
-// fract(u) the spline argument.  Sixteen hand-issued reads, the weights (six-fold, see spline_weights6_o3) computed under
-// their latency, one multiplication by 1/36 at the end.
+// fract(u) the spline argument.  Sixteen hand-issued reads; the x-weights (six-fold, see spline_weights6_o3) and the two
+// multiples of the y-fraction are computed under their latency; the y-axis is a cubic in that fraction whose constants
+// carry the 1/36, written in R0, R1, R0 + R2, R3 -- row 2 starts its accumulation from row 0's sum (spline_last_o3: 12
+// instructions where six-fold y-weights, the column and the scale took 18).
 template <int PITCH, bool FOLDED = false>
 __device__ __forceinline__ double gather_o3(unsigned win, int pitch, double cx, double cy, double offx, double offy) {
     // floor and fraction of the COORDINATE itself, the (integer) window offset added afterwards: near the left / top edge
@@ -195,27 +196,29 @@ __device__ __forceinline__ double gather_o3(unsigned win, int pitch, double cx, 
         const unsigned a3 = a2 + 8u * (unsigned)pitch;
         tp.issue_before(a0, a1, a2, a3, fx, fy);
     }
-    double wx[4], wy[4];
+    double wx[4], row[4], f3, f12;
     spline_weights6_o3(fx, wx);
-    spline_weights6_o3(fy, wy);
-    tp.wait_after(wx, wy);
-    double v = 0.0;
+    spline_last_o3_fractions(fy, f3, f12);
+    tp.wait_after(wx, f3, f12);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        double row = 0.0;
+        row[r] = spline_row_start<3>(row, r);
 #pragma unroll
-        for (int c = 0; c < 4; ++c) row = fma(tp.t[r * 4 + c], wx[c], row);
-        v = fma(row, wy[r], v);
+        for (int c = 0; c < 4; ++c) row[r] = fma(tp.t[r * 4 + c], wx[c], row[r]);
     }
-    return v * (1.0 / 36.0);
+    return spline_last_o3(row[0], row[1], row[2], row[3], fy, f3, f12);
 }
 
 // Quadratic B-spline sample from the LDS window at the window-relative coordinate (ux, uy) = coordinate + 1/2 - 1 -
 // window origin: trunc(u) is the window index of the first tap, f = fract(u) = t + 1/2 the spline argument.  The weights
 // of scipy's quadratic B-spline, w0 = (1/2 - t)^2 / 2, w1 = 3/4 - t^2, w2 = (1/2 + t)^2 / 2, are g^2 / 2, 1/2 + f g,
-// f^2 / 2 with g = 1 - f; they are evaluated DOUBLED (5 operations per axis instead of 6) and the window of an order-2
-// visit holds the pixels times 1/4 (exact), which puts the factor 2 x 2 back.  The nine reads are issued before the
-// weight arithmetic and waited for after it.
+// f^2 / 2 with g = 1 - f; they are evaluated DOUBLED (5 operations instead of 6) and the window of an order-2
+// visit holds the pixels times 1/4 (exact), which puts the factor 2 x 2 back.  Only the x-axis has weights: they serve
+// three rows.  The y-axis, one sum of three terms, is the quadratic (R0 + R1) + fy (2 (R1 - R0) + fy (R0 - 2 R1 + R2))
+// in the row sums; row 1 starts its accumulation from row 0's sum, an fma in the place of its first multiplication,
+// and from R0, R0 + R1, R2 the quadratic takes 6 instructions where 5 of weights and 3 of column took 8
+// (spline_last_o2).  The nine reads are issued before the weight arithmetic and waited for after it; no row sum is
+// formed before the wait.
 template <int PITCH>
 __device__ __forceinline__ double gather_o2(unsigned win, int pitch, double ux, double uy) {
     const int c0 = (int)ux, r0 = (int)uy;
@@ -229,24 +232,20 @@ __device__ __forceinline__ double gather_o2(unsigned win, int pitch, double ux, 
         const unsigned a2 = a1 + 8u * (unsigned)pitch;
         tp.issue_before(a0, a1, a2, fx, fy);
     }
-    double wx[3], wy[3];
-    const double gx = 1.0 - fx, gy = 1.0 - fy;
+    double wx[3], row[3];
+    const double gx = 1.0 - fx;
     wx[0] = gx * gx;
     wx[2] = fx * fx;
     wx[1] = (2.0 - wx[0]) - wx[2];
-    wy[0] = gy * gy;
-    wy[2] = fy * fy;
-    wy[1] = (2.0 - wy[0]) - wy[2];
-    tp.wait_after(wx[0], wx[1], wx[2], wy[0], wy[1], wy[2]);
-    double v = 0.0;
+    tp.wait_after(wx[0], wx[1], wx[2]);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-        double row = 0.0;
+        row[r] = spline_row_start<2>(row, r);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) row = fma(tp.t[r * 3 + c], wx[c], row);
-        v = fma(row, wy[r], v);
+        for (int c = 0; c < 3; ++c) row[r] = fma(tp.t[r * 3 + c], wx[c], row[r]);
     }
-    return v;
+    // the y-axis: the same doubled weights as a polynomial in fy, no weight; row[1] holds R0 + R1 (spline_last.hpp)
+    return spline_last_o2(row[0], row[1], row[2], fy);
 }
 
 // One (grid point, lag) of alignment.py:519-531 for this lane's lag.  Everything is under the lane's own
@@ -306,19 +305,20 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
             const unsigned a0 = win + 8u * (unsigned)(__mul24(r0, pitch) + c0);
             const unsigned a1 = a0 + 8u * (unsigned)pitch;
             const unsigned a2 = a1 + 8u * (unsigned)pitch;
+            static_assert(ORDER == 1, "orders 2 and 3 have gathers of their own (the scale of their x-weights)");
             Taps<N> tp;
-            double wx[N], wy[N];
+            double wx[N], row[N];
             tp.issue(a0, a1, a2);
             spline_weights_t<ORDER>(__builtin_amdgcn_fract(ux), wx);
-            spline_weights_t<ORDER>(__builtin_amdgcn_fract(uy), wy);
+            const double fy = __builtin_amdgcn_fract(uy);
             tp.wait();
 #pragma unroll
             for (int r = 0; r < N; ++r) {
-                double row = 0.0;
+                row[r] = spline_row_start<ORDER>(row, r);
 #pragma unroll
-                for (int c = 0; c < N; ++c) row = fma(tp.t[r * N + c], wx[c], row);
-                v = fma(row, wy[r], v);
+                for (int c = 0; c < N; ++c) row[r] = fma(tp.t[r * N + c], wx[c], row[r]);
             }
+            v = Spline<ORDER>::last(row, fy);
         }
         double bm;
         if (ROUND) {
@@ -375,7 +375,7 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
     }
     if (INTERIOR || inb) {
         int sx, sy;
-        double wx[N], wy[N];
+        double wx[N], row[N];
         double v = 0.0;
         if constexpr (ORDER == ORDER_RT) {
             if constexpr (LDS) {
@@ -399,21 +399,23 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
             const unsigned a0 = win + 8u * (unsigned)(__mul24(r0, pitch) + c0);
             const unsigned a1 = a0 + 8u * (unsigned)pitch;
             const unsigned a2 = a1 + 8u * (unsigned)pitch;
+            static_assert(ORDER == 1, "orders 2 and 3 have gathers of their own (the scale of their x-weights)");
             Taps<N> tp;
             tp.issue(a0, a1, a2);
-            Spline<ORDER>::eval(nx, sx, wx);
-            Spline<ORDER>::eval(ny, sy, wy);
+            Spline<ORDER>::eval_x(nx, sx, wx);
+            const double fyl = Spline<ORDER>::frac(ny, sy);
             tp.wait();
 #pragma unroll
             for (int r = 0; r < N; ++r) {
-                double row = 0.0;
+                row[r] = spline_row_start<ORDER>(row, r);
 #pragma unroll
-                for (int c = 0; c < N; ++c) row = fma(tp.t[r * N + c], wx[c], row);
-                v = fma(row, wy[r], v);
+                for (int c = 0; c < N; ++c) row[r] = fma(tp.t[r * N + c], wx[c], row[r]);
             }
+            v = Spline<ORDER>::last(row, fyl);
         } else {
-            Spline<ORDER>::eval(nx, sx, wx);
-            Spline<ORDER>::eval(ny, sy, wy);
+            // (x-weights at the scale the last-axis polynomial of the order wants: halved at order 2, six-fold at 3)
+            Spline<ORDER>::eval_x(nx, sx, wx);
+            const double fyl = Spline<ORDER>::frac(ny, sy);
             int ix[N], iy[N];
 #pragma unroll
             for (int k = 0; k < N; ++k) {
@@ -422,11 +424,11 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
             }
 #pragma unroll
             for (int r = 0; r < N; ++r) {
-                double row = 0.0;
+                row[r] = spline_row_start<ORDER>(row, r);
 #pragma unroll
-                for (int c = 0; c < N; ++c) row = fma((double)img[iy[r] + ix[c]], wx[c], row);
-                v = fma(row, wy[r], v);
+                for (int c = 0; c < N; ++c) row[r] = fma((double)img[iy[r] + ix[c]], wx[c], row[r]);
             }
+            v = Spline<ORDER>::last(row, fyl);
         }
         double bm;
         if (ROUND) {
