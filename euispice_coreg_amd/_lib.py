@@ -253,6 +253,9 @@ SYMBOLS = [
     ("coreg_prepare_reference_helioprojective_from_device", C.c_int,
      [_P, _P, C.c_int, C.c_int32, C.c_int32, _WP, _WP, C.c_int]),
     ("coreg_get_reference_on_grid", C.c_int, [_P, _P, C.c_int]),
+    ("coreg_smooth_small", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    ("coreg_set_reference_smoothing", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    ("coreg_get_small", C.c_int, [_P, _P, C.c_int]),
     ("coreg_resample_carrington", C.c_int, [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.c_int, _P]),
     ("coreg_resample_helioprojective", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
     ("coreg_resample_helioprojective_f64", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
@@ -312,6 +315,9 @@ SYMBOLS = [
     ("coreg_pixels_last_tile_weights", C.c_int, [_P, _P]),
     ("coreg_pixels_get_large_box", C.c_int, [_P, _P]),
     ("coreg_pixels_get_rotated", C.c_int, [_P, C.c_int32, _P]),
+    ("coreg_pixels_smooth_large", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    ("coreg_pixels_smooth_small", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    ("coreg_pixels_get_image", C.c_int, [_P, C.c_int, _P]),
     ("coreg_pixels_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("coreg_pixels_destretch", C.c_int,
      [_P, _P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PixelsField), _P, _P]),
@@ -343,6 +349,8 @@ SYMBOLS = [
     ("coreg_multi_prepare_reference_carrington", C.c_int,
      [_P, _P, C.c_int, C.c_int32, C.c_int32, _WP, C.POINTER(CarrGrid), C.c_double, C.c_int]),
     ("coreg_multi_prepare_reference_helioprojective", C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _WP, _WP, C.c_int]),
+    ("coreg_multi_smooth_small", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    ("coreg_multi_set_reference_smoothing", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_multi_set_reference_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_multi_set_small_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_multi_sweep_carrington", C.c_int,
@@ -528,6 +536,31 @@ class _ImageIntake:
         arg = None if rot is None else C.byref(DiffRot(*(float(v) for v in rot)))
         self._chk(fn(getattr(self, self._ptr), arg))
 
+    @staticmethod
+    def _tables(tables):
+        """(wy, wx) as contiguous float64 vectors (the library checks their contents)."""
+        wy, wx = tables
+        return (np.ascontiguousarray(wy, dtype=np.float64).ravel(), np.ascontiguousarray(wx, dtype=np.float64).ravel())
+
+    def smooth_small(self, tables):
+        """NaN-aware smoothing of the resident image to align with the tables (wy, wx) (coreg_smooth_small: normalised
+        convolution, a non-finite pixel stays NaN and gives nothing to its neighbours); the image is float64 afterwards.
+        Call it after `threshold_small`."""
+        wy, wx = self._tables(tables)
+        self._chk(getattr(self._lib, self._prefix + "smooth_small")(getattr(self, self._ptr), wy.ctypes.data, len(wy),
+                                                                    wx.ctypes.data, len(wx)))
+
+    def set_reference_smoothing(self, tables):
+        """The tables (wy, wx) every reference preparation that follows smooths the source image with before its
+        resample (coreg_set_reference_smoothing); None for none (the default).  It stays until set again.  (A caller that
+        tags its prepared reference -- `reference_tag` -- names the tables in the tag.)"""
+        fn = getattr(self._lib, self._prefix + "set_reference_smoothing")
+        if tables is None:
+            self._chk(fn(getattr(self, self._ptr), None, 0, None, 0))
+            return
+        wy, wx = self._tables(tables)
+        self._chk(fn(getattr(self, self._ptr), wy.ctypes.data, len(wy), wx.ctypes.data, len(wx)))
+
     def prepare_reference_carrington(self, large, hdr_large, grid: Grid, solar_r, order=2):
         w = wcs_from_header(hdr_large, carrington=True)
         self.reference_tag = None
@@ -636,6 +669,13 @@ class CoregHandle(_ImageIntake):
         out = np.empty(shape, dtype=dtype)
         dt = COREG_F32 if out.dtype == np.float32 else COREG_F64
         self._chk(self._lib.coreg_get_reference_on_grid(self._h, out.ctypes.data, dt))
+        return out
+
+    def get_small(self, shape, dtype=np.float64):
+        """The resident image to align as it stands (coreg_get_small); `shape` is the caller's to know.  float64 serves
+        every image, float32 only one that is stored so."""
+        out = np.empty(shape, dtype=dtype)
+        self._chk(self._lib.coreg_get_small(self._h, out.ctypes.data, self._dev_dtype(out.dtype)))
         return out
 
     # -- single resamples
@@ -752,6 +792,21 @@ class CoregHandle(_ImageIntake):
 
     def pixels_shift_large(self, dx, dy):
         self._chk(self._lib.coreg_pixels_shift_large(self._h, float(dx), float(dy)))
+
+    def pixels_smooth_large(self, tables):
+        """coreg_pixels_smooth_large: the resident large image smoothed in place with the tables (wy, wx)."""
+        wy, wx = self._tables(tables)
+        self._chk(self._lib.coreg_pixels_smooth_large(self._h, wy.ctypes.data, len(wy), wx.ctypes.data, len(wx)))
+
+    def pixels_smooth_small(self, tables):
+        wy, wx = self._tables(tables)
+        self._chk(self._lib.coreg_pixels_smooth_small(self._h, wy.ctypes.data, len(wy), wx.ctypes.data, len(wx)))
+
+    def pixels_get_image(self, which, shape):
+        """coreg_pixels_get_image: the large ("large" / 0) or small ("small" / 1) image as it stands, float64."""
+        out = np.empty(shape, dtype=np.float64)
+        self._chk(self._lib.coreg_pixels_get_image(self._h, {"large": 0, "small": 1}.get(which, which), out.ctypes.data))
+        return out
 
     def pixels_set_bins(self, edges_small, edges_large):
         """coreg_pixels_set_bins: the edge lists of METHOD_MUTUAL_INFORMATION (1 to 31 finite, strictly increasing float64
@@ -1125,6 +1180,9 @@ class MultiHandle(_ImageIntake):
 
     def get_reference_on_grid(self, shape, dtype):
         return self.primary.get_reference_on_grid(shape, dtype)
+
+    def get_small(self, shape, dtype=np.float64):
+        return self.primary.get_small(shape, dtype)
 
     def last_counts(self):
         """Per-lag sample counts of the last sweep over all devices, laid out like its map (CoregHandle.last_counts)."""

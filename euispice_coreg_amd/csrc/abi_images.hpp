@@ -234,7 +234,10 @@ int coreg_set_reference_on_grid(coreg_handle* h, const void* ref, int dtype, int
 struct CropRect {
     int x0, y0, w, h;
 };
-static int reference_crop(coreg_handle* h, int mode, const ResampleArgs& a0, int order, CropRect* out) {
+// While the reference smoothing is set (grow_x, grow_y: the reach of its tables) the box is widened by that much before
+// it is clipped: every pixel the resample can read is then smoothed from the same taps as in the whole image.
+static int reference_crop(coreg_handle* h, int mode, const ResampleArgs& a0, int order, CropRect* out, int grow_x = 0,
+                          int grow_y = 0) {
     *out = {0, 0, a0.W, a0.H};
     if (!h->opt_crop_reference || a0.W < 64 || a0.H < 64) return COREG_OK;
     const int nb = 256;
@@ -272,6 +275,10 @@ static int reference_crop(coreg_handle* h, int mode, const ResampleArgs& a0, int
     // (taps that mirror at an image edge stay inside: the rectangle starts AT that edge and is at least 2 aprons wide)
     x1 = std::min(a0.W - 1, std::max(x1, x0 + 2 * apron));
     y1 = std::min(a0.H - 1, std::max(y1, y0 + 2 * apron));
+    x0 = std::max(0, x0 - grow_x);
+    x1 = std::min(a0.W - 1, x1 + grow_x);
+    y0 = std::max(0, y0 - grow_y);
+    y1 = std::min(a0.H - 1, y1 + grow_y);
     const long long area = (long long)(x1 - x0 + 1) * (y1 - y0 + 1);
     if (2 * area > (long long)a0.W * a0.H) return COREG_OK;  // not worth a strided copy
     *out = {x0, y0, x1 - x0 + 1, y1 - y0 + 1};
@@ -321,11 +328,23 @@ static int upload_reference_source(coreg_handle* h, const void* large, int W, in
 static int prepare_reference(coreg_handle* h, const void* large, const PixFmt& fmt, SrcKind kind, int mode, int order,
                              ResampleArgs& a, bool out_f32) {
     CropRect crop = {0, 0, a.W, a.H};
-    if (kind == SRC_HOST) RETCHK(reference_crop(h, mode, a, order, &crop));
+    const bool smooth = !h->ref_smooth_x.empty();
+    if (kind == SRC_HOST)
+        RETCHK(reference_crop(h, mode, a, order, &crop, smooth ? (int)h->ref_smooth_x.size() / 2 : 0,
+                              smooth ? (int)h->ref_smooth_y.size() / 2 : 0));
     const bool carr = mode == MODE_TRANSLATE;
     trace(carr ? "prepare_carrington: crop box known" : "prepare_helioprojective: crop box known");
     bool f32;
     RETCHK(upload_reference_source(h, large, a.W, a.H, fmt, &f32, kind, &a.img, crop));
+    if (smooth) {
+        // the pixels the resample reads (the rectangle, or the whole image where it lies: a device source stays as it is)
+        // smoothed into a buffer of the handle; the rim of a rectangle, smoothed without its outer taps, is never read
+        HIPCHK(h->sm_out.reserve((size_t)crop.w * crop.h * sizeof(double)));
+        RETCHK(smooth_image(h, a.img, f32, crop.h, crop.w, h->ref_smooth_y.data(), (long long)h->ref_smooth_y.size(),
+                            h->ref_smooth_x.data(), (long long)h->ref_smooth_x.size(), h->sm_out.as<double>()));
+        a.img = h->sm_out.p;
+        f32 = false;
+    }
     if (crop.w != a.W || crop.h != a.H) a.crop = {crop.x0, crop.y0, crop.w};
     HIPCHK(h->ref.reserve((size_t)a.gw * a.gh * (out_f32 ? sizeof(float) : sizeof(double))));
     a.out = h->ref.p;
@@ -497,6 +516,59 @@ int coreg_set_reference_rotation(coreg_handle* h, const coreg_diffrot* rot) {
 }
 int coreg_set_small_rotation(coreg_handle* h, const coreg_diffrot* rot) {
     return h ? set_rotation(h, rot, &h->rot_small, &h->has_rot_small) : COREG_EINVAL;
+}
+
+// NaN-aware smoothing of the resident image to align, in place as far as the caller sees: the float64 result is written to
+// a buffer of the handle, which then changes places with the image's.
+int coreg_smooth_small(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx) {
+    if (!h) return COREG_EINVAL;
+    if (!h->small.p) return fail(h, COREG_ESTATE, "coreg_set_small has not been called");
+    const SmoothPlan p = smooth_plan(h->sH, h->sW, wy, n_wy, wx, n_wx);
+    if (p.code != COREG_OK) return fail(h, p.code, p.msg);  // (before the join: a refused call changes nothing)
+    RETCHK(bind_device(h));                                 // (joins a pending upload: join_small)
+    const long long n = (long long)h->sW * h->sH;
+    HIPCHK(h->sm_out.reserve((size_t)n * sizeof(double)));
+    RETCHK(smooth_image(h, h->small.p, h->small_f32, h->sH, h->sW, wy, n_wy, wx, n_wx, h->sm_out.as<double>()));
+    std::swap(h->small, h->sm_out);
+    h->small_f32 = false;
+    HIPCHK(buffer_mean(h, h->small.p, false, n, h->pivots.as<double>() + 1, h->stream));
+    return COREG_OK;
+}
+
+int coreg_set_reference_smoothing(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx) {
+    if (!h) return COREG_EINVAL;
+    if (n_wy == 0 && n_wx == 0) {
+        h->ref_smooth_y.clear();
+        h->ref_smooth_x.clear();
+        return COREG_OK;
+    }
+    const char* why = smooth_table_refusal(wy, n_wy);
+    if (!why) why = smooth_table_refusal(wx, n_wx);
+    if (why) return fail(h, COREG_EINVAL, why);
+    h->ref_smooth_y.assign(wy, wy + n_wy);
+    h->ref_smooth_x.assign(wx, wx + n_wx);
+    return COREG_OK;
+}
+
+int coreg_get_small(coreg_handle* h, void* out, int dtype) {
+    if (!h) return COREG_EINVAL;
+    if (!h->small.p) return fail(h, COREG_ESTATE, "coreg_set_small has not been called");
+    // float32 pixels may be asked for as float64 (exact); float64 pixels only as they are
+    if (!out || !is_dtype(dtype) || (dtype == COREG_F32 && !h->small_f32))
+        return fail(h, COREG_EINVAL, "get_small: null pointer, or float32 asked of a float64 image");
+    RETCHK(bind_device(h));
+    const size_t n = (size_t)h->sW * h->sH;
+    if (h->small_f32 && dtype == COREG_F64) {
+        std::vector<float> tmp(n);
+        HIPCHK(hipMemcpyAsync(tmp.data(), h->small.p, n * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        for (size_t q = 0; q < n; ++q) ((double*)out)[q] = (double)tmp[q];
+        return COREG_OK;
+    }
+    HIPCHK(hipMemcpyAsync(out, h->small.p, n * (h->small_f32 ? sizeof(float) : sizeof(double)), hipMemcpyDeviceToHost,
+                          h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return COREG_OK;
 }
 
 int coreg_get_reference_on_grid(coreg_handle* h, void* out, int dtype) {

@@ -19,6 +19,21 @@ int coreg_pixels_shift_large(coreg_handle* h, double dx, double dy) {
     return pixels_shift_large(h, dx, dy);
 }
 
+int coreg_pixels_smooth_large(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx) {
+    if (!h) return COREG_EINVAL;
+    return pixels_smooth(h, 0, wy, n_wy, wx, n_wx);
+}
+
+int coreg_pixels_smooth_small(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx) {
+    if (!h) return COREG_EINVAL;
+    return pixels_smooth(h, 1, wy, n_wy, wx, n_wx);
+}
+
+int coreg_pixels_get_image(coreg_handle* h, int which, double* out) {
+    if (!h) return COREG_EINVAL;
+    return pixels_get_image(h, which, out);
+}
+
 int coreg_pixels_sweep_method(coreg_handle* h, const coreg_pixels_plan* plan, int method, double* out) {
     if (!h) return COREG_EINVAL;
     return pixels_sweep(h, plan, method, out);

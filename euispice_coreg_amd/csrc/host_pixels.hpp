@@ -111,6 +111,21 @@ int pixels_shift_large(coreg_handle* h, double dx, double dy) {
     return pixels_resample(h, PIX_AFFINE, a);
 }
 
+// NaN-aware smoothing (host_smooth.hpp) of the large (which = 0) or small (1) image, in place: both are float64 already
+int pixels_smooth(coreg_handle* h, int which, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx) {
+    PixelsState* st = pixels_state(h, false);
+    DevBuf* img = st ? (which ? &st->small : &st->large) : nullptr;
+    if (!img || !img->p) return fail(h, COREG_ESTATE, which ? "pixels: the small image is not set" : "pixels: the large image is not set");
+    const int W = which ? st->sW : st->lW, H = which ? st->sH : st->lH;
+    const SmoothPlan p = smooth_plan(H, W, wy, n_wy, wx, n_wx);
+    if (p.code != COREG_OK) return fail(h, p.code, p.msg);  // (a refused call changes nothing)
+    RETCHK(bind_device(h));
+    if (which) st->n_rot = 0;
+    else st->bW = st->bH = 0;
+    st->forget_last();
+    return smooth_image(h, img->p, false, H, W, wy, n_wy, wx, n_wx, img->as<double>());
+}
+
 // the edge lists of the mutual-information score (csrc/pixels_bins.hpp: 1 to 31 entries, finite, strictly increasing)
 int pixels_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small, const double* edges_large, int32_t n_large) {
     if (!bins_edges_ok(edges_small, n_small) || !bins_edges_ok(edges_large, n_large))
@@ -369,6 +384,15 @@ static int pixels_read(coreg_handle* h, const void* dev, size_t n, double* out) 
     HIPCHK(hipMemcpyAsync(out, dev, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return COREG_OK;
+}
+
+// the large (which = 0) or small (1) image as it stands: [ny][nx] float64
+int pixels_get_image(coreg_handle* h, int which, double* out) {
+    PixelsState* st = pixels_state(h, false);
+    if (which != 0 && which != 1) return fail(h, COREG_EINVAL, "pixels: which must be 0 (large) or 1 (small)");
+    DevBuf* img = st ? (which ? &st->small : &st->large) : nullptr;
+    if (!img || !img->p) return fail(h, COREG_ESTATE, "pixels: that image is not set");
+    return pixels_read(h, img->p, which ? (size_t)st->sW * st->sH : (size_t)st->lW * st->lH, out);
 }
 
 int pixels_get_large_box(coreg_handle* h, double* out) {

@@ -96,6 +96,11 @@ struct coreg_handle {
     // differential rotation per role (coreg_set_reference_rotation / coreg_set_small_rotation); has_* false: off
     coreg_diffrot rot_ref = {}, rot_small = {};
     bool has_rot_ref = false, has_rot_small = false;
+    // NaN-aware smoothing (host_smooth.hpp): the planes num and den of a call, the smoothed copy of an image (exchanged
+    // with `small` by coreg_smooth_small; what the resample reads while the reference smoothing is set), and the tables of
+    // coreg_set_reference_smoothing, which stay until set again or cleared
+    DevBuf sm_num, sm_den, sm_out;
+    std::vector<double> ref_smooth_y, ref_smooth_x;  // both empty: off
     CarrTables tabs;
     std::vector<double> tabs_key;
     bool tabs_uploaded = false;  // the device tables are those of `tabs`

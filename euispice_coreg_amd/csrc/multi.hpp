@@ -1009,6 +1009,15 @@ int coreg_multi_threshold_small(coreg_multi* m, int has_min, double vmin, int ha
     });
 }
 
+int coreg_multi_smooth_small(coreg_multi* m, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx) {
+    if (!m) return COREG_EINVAL;
+    return multi_run(m, [&](int k) { return coreg_smooth_small(m->h[k], wy, n_wy, wx, n_wx); });
+}
+int coreg_multi_set_reference_smoothing(coreg_multi* m, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx) {
+    if (!m) return COREG_EINVAL;
+    return multi_run(m, [&](int k) { return coreg_set_reference_smoothing(m->h[k], wy, n_wy, wx, n_wx); });
+}
+
 int coreg_multi_set_reference_on_grid(coreg_multi* m, const void* ref, int dtype, int32_t gy, int32_t gx) {
     if (!m) return COREG_EINVAL;
     return multi_run(m, [&](int k) { return coreg_set_reference_on_grid(m->h[k], ref, dtype, gy, gx); });

@@ -27,6 +27,12 @@ surface.  Differences, all deliberate and listed in DESIGN.md:
     two instruments whose intensities are not linearly related (include/coreg_hip.h: coreg_sweep_set_bins states the rule).
     The Carrington frame only: the other `align_using_*` raise NotImplementedError for it.  `self.last_bins` holds the
     edges used.
+  * `smooth_small=` / `smooth_large=` (every `align_using_*`, every method): a NaN-aware Gaussian smoothing of the image to
+    align (after its thresholds) and of the reference image (before its once-only resample) on the GPU, to bring the finer
+    image to the coarser one's resolution (include/coreg_hip.h: coreg_smooth_small states the rule).  A FWHM, a pair
+    (fwhm_y, fwhm_x) or a pair of weight tables (utils/smoothing.py: `smoothing_tables`), in pixels of each image's own grid
+    or, `smooth_unit="arcsec"`, converted with each image's own CDELT.  A non-finite pixel stays NaN and gives nothing to
+    its neighbours.  None (the default) changes nothing.
 There is no CPU fallback: without the HIP library / a GPU the sweep raises.
 """
 from __future__ import annotations
@@ -39,6 +45,7 @@ import numpy as np
 
 from .. import _lib, parallel
 from ..utils import diffrot, fits_io, header as hdrutil, wcs_tan
+from ..utils.smoothing import smoothing_tables
 from .alignment_results import AlignmentResults
 
 
@@ -133,7 +140,8 @@ class Alignment:
                  lag_crota, lag_solar_r=None, small_fov_value_min=None, parallelism=False, display_progress_bar=False,
                  small_fov_value_max=None, counts_cpu_max=40, large_fov_window=-1, small_fov_window=-1,
                  path_save_figure=None, reprojection_order=2, force_crota_0=False, unit_lag="arcsec",
-                 cdelt_semantics="intended", device=None, differential_rotation="reference", min_overlap=None):
+                 cdelt_semantics="intended", device=None, differential_rotation="reference", min_overlap=None,
+                 smooth_small=None, smooth_large=None, smooth_unit="pixel"):
         self.large_fov_known_pointing = large_fov_known_pointing
         self.small_fov_to_correct = small_fov_to_correct
         self.lag_crval1 = lag_crval1
@@ -174,6 +182,13 @@ class Alignment:
         if min_overlap is not None:
             min_overlap_floor(min_overlap)  # (its checks, before anything is loaded)
         self.min_overlap = min_overlap  # lag-points with fewer samples become NaN (apply_min_overlap); None: no floor
+        if smooth_unit not in ("pixel", "arcsec"):
+            raise ValueError("smooth_unit must be 'pixel' or 'arcsec'")
+        # (the form of both arguments, before anything is loaded; in arcsec the tables need the headers: `_smoothing`)
+        for arg, what in ((smooth_small, "smooth_small"), (smooth_large, "smooth_large")):
+            smoothing_tables(arg, what, (1.0, 1.0) if smooth_unit == "pixel" else (0.0, 0.0))
+        self.smooth_small, self.smooth_large, self.smooth_unit = smooth_small, smooth_large, smooth_unit
+        self._smooth_large_tables = None  # (wy, wx) of the sweep being run, None: none
         self.last_counts = None         # per-lag sample counts of the last sweep, shaped like its map
         self.last_bins = None           # (edges_small, edges_large) of the last "mutual_information" sweep
         self._bins = None               # `bins` of the sweep being run, as parse_bins leaves it
@@ -238,8 +253,22 @@ class Alignment:
 
     def _carrington_tag(self, solar_r, rot_large):
         """Identity of the reference image on the Carrington grid: a resident one prepared for another rotation (another
-        `reference_date`, another band) is not this one."""
-        return self._reference_tag("carrington", self.lonlims, self.latlims, self.shape, solar_r, rot_large or ())
+        `reference_date`, another band) or with another smoothing is not this one."""
+        return self._reference_tag("carrington", self.lonlims, self.latlims, self.shape, solar_r, rot_large or (),
+                                   *(self._smooth_large_tables or ()))
+
+    def _smoothing(self, which):
+        """(wy, wx) of `smooth_small` / `smooth_large` in pixels of that image's grid as its header stands, or None."""
+        arg = self.smooth_small if which == "small" else self.smooth_large
+        if arg is None:
+            return None
+        scale = (1.0, 1.0)
+        if self.smooth_unit == "arcsec":
+            hdr = self.hdr_small if which == "small" else self.hdr_large
+            arcsec = hdrutil.unit_to_deg("arcsec")
+            scale = (arcsec / abs(hdr["CDELT2"] * hdrutil.unit_to_deg(hdr["CUNIT2"])),
+                     arcsec / abs(hdr["CDELT1"] * hdrutil.unit_to_deg(hdr["CUNIT1"])))
+        return smoothing_tables(arg, "smooth_" + which, scale)
 
     def _rotations(self):
         """(rotation of the reference image, rotation of the image to align) of the Carrington frame, each
@@ -419,6 +448,16 @@ class Alignment:
         self.hdr_small = hg
 
     def _find_best_header_parameters(self, ang2pipi=True, fov_limits=None, remove_fov_limits=None):
+        """`_sweep`; the long-lived handle it ran on does not keep this object's reference smoothing, whatever happened."""
+        self._sweep_handle = None
+        try:
+            return self._sweep(ang2pipi, fov_limits, remove_fov_limits)
+        finally:
+            if self._sweep_handle is not None and self._smooth_large_tables is not None:
+                self._sweep_handle.set_reference_smoothing(None)
+            self._sweep_handle = None
+
+    def _sweep(self, ang2pipi=True, fov_limits=None, remove_fov_limits=None):
         """alignment.py:613-797 on the GPU.  Returns float64 [n_crval1, n_crval2, n_cdelt1, n_cdelt2, n_crota,
         n_solar_r]; lag-points the library could not evaluate are NaN, never 0 (quirk Q9)."""
         mi = self.method == MUTUAL_INFORMATION
@@ -469,6 +508,10 @@ class Alignment:
         if self.coordinate_frame == "final_carrington":
             h.set_rotation("reference", rot_large)
             h.set_rotation("small", rot_small)
+        # ... and its reference smoothing
+        self._smooth_large_tables = self._smoothing("large")
+        self._sweep_handle = h
+        h.set_reference_smoothing(self._smooth_large_tables)
         # alignment.py:844-861: thresholds, then the box to remove, then the sub-FOV re-grid
         on_device = (remove_fov_limits is None) and (fov_limits is None)
         n_finite = None
@@ -504,15 +547,22 @@ class Alignment:
                 self._select_fov_in_small_data(fov_limits, h)
             n_finite = int(np.isfinite(self.data_small).sum())
             upload_small(self.data_small)
+        smooth_small = self._smoothing("small")  # (of the header the image now has: a sub-FOV re-grid changes CDELT)
         self._set_initial_header_values(ang2pipi)
 
         def finite_pixels():
-            """alignment.py:654-656, after the first reference preparation (the check itself reads the uploaded pixels)."""
-            nonlocal n_finite
+            """alignment.py:654-656, after the first reference preparation (the check itself reads the uploaded pixels).
+            The smoothing of the image to align follows its thresholds: a masked pixel cannot bleed."""
+            nonlocal n_finite, smooth_small
             if n_finite is None:
                 n_finite = h.threshold_small(self.small_fov_value_min, self.small_fov_value_max)
             if n_finite == 0:
                 raise ValueError("minimum or maximum value have set all small FOV to nan")
+            if smooth_small is not None:
+                h.smooth_small(smooth_small)
+                smoothed_small[0], smooth_small = True, None
+
+        smoothed_small = [False]
 
         if n_finite is not None:
             finite_pixels()
@@ -590,7 +640,13 @@ class Alignment:
                     prepare("helioprojective", self.hdr_large, self.hdr_small, self.order)
                     target = self.hdr_small
                 else:
-                    h.set_reference_on_grid(np.asarray(self._large_pixels(), dtype=np.float64))  # quirk Q1: float64
+                    big = np.asarray(self._large_pixels(), dtype=np.float64)  # quirk Q1: float64
+                    if self._smooth_large_tables is not None:
+                        # no resample here, so no preparation to smooth in: the pixel-lag sweep's image slot serves
+                        h.pixels_set_large(big)
+                        h.pixels_smooth_large(self._smooth_large_tables)
+                        big = h.pixels_get_image("large", big.shape)
+                    h.set_reference_on_grid(big)
                     target = self.hdr_large
 
                 def run(t=target):
@@ -601,8 +657,12 @@ class Alignment:
             if mi and kk == 0:
                 edges = self._bins
                 if isinstance(edges, int):
-                    edges = default_edges(self._small_pixels_on_host(), self.small_fov_value_min, self.small_fov_value_max,
-                                          h.get_reference_on_grid((grid.n_lat, grid.n_lon), np.float64), edges)
+                    ref_on_grid = h.get_reference_on_grid((grid.n_lat, grid.n_lon), np.float64)
+                    if smoothed_small[0]:  # the smoothed image, read back (its thresholds are in it)
+                        edges = default_edges(h.get_small(tuple(np.shape(self.data_small))), None, None, ref_on_grid, edges)
+                    else:
+                        edges = default_edges(self._small_pixels_on_host(), self.small_fov_value_min,
+                                              self.small_fov_value_max, ref_on_grid, edges)
                 h.sweep_set_bins(*edges)
                 self.last_bins = edges
             # (the sample counts of this rank's share are gathered the way its coefficients are)

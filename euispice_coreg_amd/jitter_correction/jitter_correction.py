@@ -63,8 +63,9 @@ def jitter_correction_imagers(list_files_input, path_files_output, lonlims=None,
                               plot_all_figures=False, parallelism=True, cpu_count=None, small_fov_value_max=None,
                               small_fov_value_min=None, alignement_method="carrington", device=None, prefetch=2,
                               pipeline_depth=2, differential_rotation="reference", method="correlation",
-                              min_overlap=None, bins=None):
-    """See the module docstring.  `method`, `min_overlap`: as on hdrshift.Alignment -- "residus_masked" with a floor on
+                              min_overlap=None, bins=None, smooth_small=None, smooth_large=None, smooth_unit="pixel"):
+    """See the module docstring.  `smooth_small`, `smooth_large`, `smooth_unit`: as on hdrshift.Alignment (the resident
+    reference of a sublist is prepared smoothed, once).  `method`, `min_overlap`: as on hdrshift.Alignment -- "residus_masked" with a floor on
     the overlap is the sharper score for frames of one instrument; `bins`: of method "mutual_information"
     (alignement_method "carrington" only), as `Alignment.align_using_carrington` takes it.  Returns the list of (index_to_align, index_ref, AlignmentResults) this rank
     produced, in processing order (the reference returns None; the corrected files are the product)."""
@@ -109,6 +110,7 @@ def jitter_correction_imagers(list_files_input, path_files_output, lonlims=None,
             parallelism=parallelism, alignement_method=alignement_method, small_fov_value_max=small_fov_value_max,
             small_fov_value_min=small_fov_value_min, unit_lag=unit_lag, device=dev,
             differential_rotation=differential_rotation, method=method, min_overlap=min_overlap, bins=bins,
+            smooth_small=smooth_small, smooth_large=smooth_large, smooth_unit=smooth_unit,
             _preloaded_small=fut_image.result(), _return_corr=True, _handle_slot=slot0 + slots.id, **kwargs_carrington)
         out_path = os.path.join(path_files_output, os.path.basename(list_files_input[index_to_align]))
         # sub-lag Gaussian fit + corrected FITS in a writer thread: the GPU is already on the next image
@@ -187,14 +189,16 @@ def _align_hrieuv_with_hrieuv(large_fov_fits_path, large_fov_window, small_fov_p
                               small_fov_value_max=None, small_fov_value_min=None, method_carrington_reprojection="fa",
                               alignement_method="carrington", path_output_figures=None, fov_limits=None, device=None,
                               _preloaded_small=None, _return_corr=False, _handle_slot=0,
-                              differential_rotation="reference", method="correlation", min_overlap=None, bins=None):
+                              differential_rotation="reference", method="correlation", min_overlap=None, bins=None,
+                              smooth_small=None, smooth_large=None, smooth_unit="pixel"):
     """jitter_correction.py:177-256: one image against the sublist's reference.  `_return_corr`: hand back
     (Alignment, raw correlation array) so that the caller can build the AlignmentResults off the critical path."""
     A = Alignment(large_fov_known_pointing=large_fov_fits_path, large_fov_window=large_fov_window,
                   small_fov_to_correct=small_fov_path, small_fov_window=window_to_align, display_progress_bar=False,
                   small_fov_value_max=small_fov_value_max, small_fov_value_min=small_fov_value_min,
                   parallelism=parallelism, counts_cpu_max=cpu_count, unit_lag=unit_lag, device=device,
-                  differential_rotation=differential_rotation, min_overlap=min_overlap, **parameter_alignment)
+                  differential_rotation=differential_rotation, min_overlap=min_overlap, smooth_small=smooth_small,
+                  smooth_large=smooth_large, smooth_unit=smooth_unit, **parameter_alignment)
     A.shard_lags = False
     A._preloaded_small = _preloaded_small
     A._handle_slot = _handle_slot

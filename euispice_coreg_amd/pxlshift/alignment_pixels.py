@@ -27,6 +27,13 @@ Differences from the reference, all deliberate:
   * a lag whose window leaves the sub-resolved image raises the reference's ValueError before any work is done (the
     reference raises it when its loop gets there);
   * an unknown `unit_rot` raises ValueError (the reference dies on an unbound name).
+
+`smooth_large=` / `smooth_small=` (`find_best_parameters`, `find_local_shifts`; not in the reference): a NaN-aware
+Gaussian smoothing of either image on the GPU, right after its pixels are set and before the solar-rotation shift and
+the sub-resolution -- the anti-alias filter the order-1 point sampling of the large image lacks.  A FWHM, a pair
+(fwhm_y, fwhm_x) or a pair of weight tables, in pixels of the image's own grid (utils/smoothing.py: `smoothing_tables`;
+include/coreg_hip.h: coreg_pixels_smooth_large states the rule).  Default mutual-information edges are then the quantiles
+of the smoothed images.
 """
 from __future__ import annotations
 
@@ -35,6 +42,7 @@ import numpy as np
 from .. import _lib
 from ..hdrshift.alignment import apply_min_overlap, library_method, min_overlap_floor
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
+from ..utils.smoothing import smoothing_tables  # noqa: F401  (the tables of `smooth_large=` / `smooth_small=`)
 
 _RETURN_TYPES = ("corr", "PixelAlignmentResults")
 MUTUAL_INFORMATION = "mutual_information"  # hdrshift's `library_method` has none: `align_using_carrington` knows it beside those
@@ -220,7 +228,7 @@ class AlignmentPixels:
 
     def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
                   method="correlation", min_overlap=None, tile_shape=None, bins=None, tile_step=None,
-                  apodization=None) -> dict:
+                  apodization=None, smooth_large=None, smooth_small=None) -> dict:
         """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU); with
         `tile_shape` = (rows, columns), of a `find_local_shifts` call: the plan then holds the tile grid too.
         `bins` (method "mutual_information" only, ValueError with any other): an integer 2 <= B <= 32 (default 16) --
@@ -229,7 +237,12 @@ class AlignmentPixels:
         `check_edges` takes them; the plan holds the pair as `plan["bins"]`.
         `tile_step` (with `tile_shape`; `tile_grid`): the plan holds it next to the shape and the grid.  `apodization` (with
         `tile_shape`, method "correlation" only, ValueError with any other; `apodization_tables`): the plan holds the two
-        weight tables as `plan["window"]` = (wy, wx), None without."""
+        weight tables as `plan["window"]` = (wy, wx), None without.  `smooth_large`, `smooth_small` (`smoothing_tables`, in
+        pixels of each image's own grid): the plan holds the table pairs under those names, None without; with either,
+        `bins` as a number cannot be turned into edges here -- they are quantiles of the smoothed images, which the GPU
+        makes -- and the plan holds the number as `plan["bins_pending"]` and `plan["bins"]` = None until the call has them."""
+        smooth = {"smooth_large": smoothing_tables(smooth_large, "smooth_large"),
+                  "smooth_small": smoothing_tables(smooth_small, "smooth_small")}
         if method == MUTUAL_INFORMATION:
             method_code = _lib.METHOD_MUTUAL_INFORMATION
         else:
@@ -266,9 +279,16 @@ class AlignmentPixels:
         plan = {"lag_dx": dx, "lag_dy": dy, "lag_drot": drot, "lag_drot_rad": drot_rad, "unit_rot": unit_rot,
                 "ratio_res_1": float(ratio1), "ratio_res_2": float(ratio2), "sub_shape": sub, "slc_small_ref": tuple(l),
                 "xc": round(w / 2), "yc": round(h / 2), "shift_large": None, "method": method,
-                "method_code": method_code, "min_overlap": min_overlap, "small_shape": (h, w)}
+                "method_code": method_code, "min_overlap": min_overlap, "small_shape": (h, w), **smooth}
         if method == MUTUAL_INFORMATION:
-            plan["bins"] = self._bin_edges(DEFAULT_BINS if bins is None else bins, plan)
+            bins = DEFAULT_BINS if bins is None else bins
+            if (isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_))
+                    and (smooth["smooth_large"] is not None or smooth["smooth_small"] is not None)):
+                if not 2 <= bins <= MAX_BINS:
+                    raise ValueError(f"bins as a number must lie in [2, {MAX_BINS}]")
+                plan["bins"], plan["bins_pending"] = None, int(bins)
+            else:
+                plan["bins"] = self._bin_edges(bins, plan)
         if tile_shape is None:
             if tile_step is not None or apodization is not None:
                 raise ValueError("tile_step and apodization belong to a tile_shape")
@@ -282,14 +302,17 @@ class AlignmentPixels:
             plan["shift_large"] = self._shift_large_fov_displacement()
         return plan
 
-    def _bin_edges(self, bins, plan):
-        """(edges_small, edges_large) of a `bins` argument (see `host_plan`)."""
+    def _bin_edges(self, bins, plan, small=None, large=None):
+        """(edges_small, edges_large) of a `bins` argument (see `host_plan`); `small`, `large`: the images a number of
+        bins is the quantiles of (default: the file's pixels)."""
         if isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_)):
             if not 2 <= bins <= MAX_BINS:
                 raise ValueError(f"bins as a number must lie in [2, {MAX_BINS}]")
+            small = self.data_small if small is None else small
+            large = self.data_large if large is None else large
             win = zero_lag_window(self.data_large.shape, self.data_small.shape, plan["slc_small_ref"],
                                   plan["ratio_res_1"], plan["ratio_res_2"])
-            return quantile_edges(self.data_small, int(bins)), quantile_edges(self.data_large[win], int(bins))
+            return quantile_edges(small, int(bins)), quantile_edges(large[win], int(bins))
         if isinstance(bins, (bool, np.bool_, float, np.floating, str)):
             raise ValueError("bins must be an integer or a pair (edges_small, edges_large)")
         try:
@@ -298,30 +321,43 @@ class AlignmentPixels:
             raise ValueError("bins must be an integer or a pair (edges_small, edges_large)") from None
         return check_edges(es, "edges_small"), check_edges(el, "edges_large")
 
+    def _set_images(self, hnd, plan):
+        """Every call starts from the file's pixels: both images up, smoothed where the plan says so (and the pending
+        default bins taken from them), then the solar-rotation shift of the large one."""
+        hnd.pixels_set_large(self.data_large)
+        hnd.pixels_set_small(self.data_small)
+        if plan["smooth_large"] is not None:
+            hnd.pixels_smooth_large(plan["smooth_large"])
+        if plan["smooth_small"] is not None:
+            hnd.pixels_smooth_small(plan["smooth_small"])
+        if plan.get("bins_pending") is not None:
+            large = None if plan["smooth_large"] is None else hnd.pixels_get_image("large", self.data_large.shape)
+            small = None if plan["smooth_small"] is None else hnd.pixels_get_image("small", self.data_small.shape)
+            plan["bins"] = self._bin_edges(plan["bins_pending"], plan, small, large)
+        if plan["shift_large"] is not None:
+            dx, dy = plan["shift_large"]
+            hnd.pixels_shift_large(dx, dy)
+            print(f"corrected solar rotation on FSI on CRVAL1: {dx=}, {dy=}")
+
     def find_best_parameters(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
-                             method="correlation", min_overlap=None, return_type="corr", bins=None):
+                             method="correlation", min_overlap=None, return_type="corr", bins=None, smooth_large=None,
+                             smooth_small=None):
         """alignment_pixels.py:57-84: correlation cube [len(lag_dx), len(lag_dy), len(lag_drot)], float64.
         method: "correlation" (best = maximum), "residus_masked" (best = minimum) or "mutual_information" (best =
         maximum; `bins` as `host_plan` takes it).  `self.last_counts`: the samples
         behind every entry, shaped like the cube (before `min_overlap`).  min_overlap: None, a count >= 1 or a fraction
         in (0, 1) of the sweep's largest count; entries of fewer samples become NaN, ValueError when none is left.
-        return_type: "corr" (the cube) or "PixelAlignmentResults"."""
+        return_type: "corr" (the cube) or "PixelAlignmentResults".  smooth_large, smooth_small: see the module docstring."""
         if return_type not in _RETURN_TYPES:
             raise ValueError(f"return_type must be one of {_RETURN_TYPES}")
         plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
-                              bins=bins)
+                              bins=bins, smooth_large=smooth_large, smooth_small=smooth_small)
         self.lag_dx, self.lag_dy, self.lag_drot, self.unit_rot = lag_dx, lag_dy, lag_drot, unit_rot
         self.ratio_res_1, self.ratio_res_2 = plan["ratio_res_1"], plan["ratio_res_2"]
         l, (h, w) = plan["slc_small_ref"], self.data_small.shape
         self.slc_small_ref = (slice(l[0], l[0] + h), slice(l[1], l[1] + w))
         hnd = _lib.shared_handle(-1 if self.device is None else self.device)
-        # every call starts from the file's pixels
-        hnd.pixels_set_large(self.data_large)
-        hnd.pixels_set_small(self.data_small)
-        if plan["shift_large"] is not None:
-            dx, dy = plan["shift_large"]
-            hnd.pixels_shift_large(dx, dy)
-            print(f"corrected solar rotation on FSI on CRVAL1: {dx=}, {dy=}")
+        self._set_images(hnd, plan)
         corr = hnd.pixels_sweep(plan, plan["method_code"])
         self.last_timing = hnd.pixels_last_timing()
         self.last_counts = hnd.pixels_last_counts(corr.shape)
@@ -337,7 +373,7 @@ class AlignmentPixels:
 
     def find_local_shifts(self, lag_dx, lag_dy, lag_drot=(0.0,), tile_shape=None, unit_rot="degree",
                           shift_solar_rotation_dx_large=False, method="correlation", min_overlap=None, min_fill=0.5,
-                          sub_lag=True, bins=None, tile_step=None, apodization=None):
+                          sub_lag=True, bins=None, tile_step=None, apodization=None, smooth_large=None, smooth_small=None):
         """The local shift field: the small image is cut into tiles of `tile_shape` = (rows, columns) pixels (the last
         ones ragged) and every tile gets the lag cube of `find_best_parameters` on its own rectangle -- a rotated plane
         is still rotated about the whole image's centre -- with its sample counts, best entry and sub-lag fit.  Returns a
@@ -353,14 +389,10 @@ class AlignmentPixels:
         if tile_shape is None:
             raise ValueError("tile_shape = (rows, columns) is needed")
         plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
-                              tile_shape=tile_shape, bins=bins, tile_step=tile_step, apodization=apodization)
+                              tile_shape=tile_shape, bins=bins, tile_step=tile_step, apodization=apodization,
+                              smooth_large=smooth_large, smooth_small=smooth_small)
         hnd = _lib.shared_handle(-1 if self.device is None else self.device)
-        hnd.pixels_set_large(self.data_large)
-        hnd.pixels_set_small(self.data_small)
-        if plan["shift_large"] is not None:
-            dx, dy = plan["shift_large"]
-            hnd.pixels_shift_large(dx, dy)
-            print(f"corrected solar rotation on FSI on CRVAL1: {dx=}, {dy=}")
+        self._set_images(hnd, plan)
         corr = hnd.pixels_sweep_tiles(plan, plan["method_code"])
         self.last_timing = hnd.pixels_last_timing()
         counts = hnd.pixels_last_tile_counts(corr.shape)

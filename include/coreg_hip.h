@@ -269,6 +269,29 @@ int coreg_prepare_reference_helioprojective_from_device(coreg_handle* h, const v
 /* Copy the resident reference-on-grid back (tests / figures). out: [gy][gx] of `dtype` (must match). */
 int coreg_get_reference_on_grid(coreg_handle* h, void* out, int dtype);
 
+/* NaN-aware Gaussian (or any separable, non-negative) smoothing of an image on the device: normalised convolution.
+ * With m = isfinite(v), z = m ? v : 0 and the tables wy[2 ry + 1], wx[2 rx + 1]:
+ *     num = C_y(C_x(z)),  den = C_y(C_x(m)),  C_x(a)[j,i] = sum_k wx[k] a[j, i + k - rx],  C_y alike along y,
+ *     out[j,i] = num / den where m[j,i] and den > 0, else NaN
+ * (taps outside the image add nothing; x pass first; float64 arithmetic in a fixed tap order, no atomics: a pixel's value
+ * depends on the image and the tables alone).  A pixel that is not finite stays NaN and gives nothing to its neighbours;
+ * image borders renormalise like a hole.  A table has an odd number of entries from 1 to 129, all finite and >= 0, with
+ * a positive sum: COREG_EINVAL otherwise, and a refused call leaves everything as it was.  The table {1.0} on both axes
+ * is the identity, bit for bit, on every finite pixel.
+ *   coreg_smooth_small             the resident image to align, in place; it is float64 afterwards and its pivot is
+ *                                  recomputed as by coreg_threshold_small.  Call it after the thresholds, so that a
+ *                                  saturated pixel is masked before it can bleed.  COREG_ESTATE without an image
+ *   coreg_set_reference_smoothing  stays until set again; n_wy = n_wx = 0 clears it.  While set, every
+ *                                  coreg_prepare_reference_* call smooths the source image's pixels before the once-only
+ *                                  resample (host, _f32, _fits, _tiled and _from_device sources; a device source is not
+ *                                  modified).  The crop box of "crop_reference" is widened by (rx, ry): crop on or off
+ *                                  gives the same bits
+ *   coreg_get_small                the image to align as it stands, out: [ny][nx] of `dtype`; a float32 image may be
+ *                                  asked for as float64, a float64 image (any smoothed one) only as float64 */
+int coreg_smooth_small(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
+int coreg_set_reference_smoothing(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
+int coreg_get_small(coreg_handle* h, void* out, int dtype);
+
 /* One resample of the small image through ONE header (= function_to_apply of one lag-point):
  * carrington:      alignment.py:889-901   out float64 [n_lat][n_lon], NaN outside
  * helioprojective: alignment.py:1018-1029 out float32 [hdr_target.naxis2][hdr_target.naxis1] */
@@ -718,6 +741,12 @@ int coreg_pixels_sweep_windows(coreg_handle* h, const coreg_pixels_plan* plan, i
                                const double* wx /* NULL or [tile_nx] */, double* out);
 int coreg_pixels_last_tile_weights(coreg_handle* h, double* dst);
 int coreg_pixels_get_large_box(coreg_handle* h, double* out);
+/* coreg_smooth_small's rule on the resident large / small image of the pixel-lag sweep, in place (both are float64);
+ * each forgets the last box, planes and counts, as coreg_pixels_shift_large does.  coreg_pixels_get_image reads an image
+ * back as it stands: which = 0 the large one [ny][nx], 1 the small one. */
+int coreg_pixels_smooth_large(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
+int coreg_pixels_smooth_small(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
+int coreg_pixels_get_image(coreg_handle* h, int which, double* out);
 int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out);
 int coreg_pixels_last_timing(coreg_handle* h, double* ms);
 typedef struct coreg_pixels_field {
@@ -785,6 +814,9 @@ int coreg_multi_prepare_reference_carrington(coreg_multi* m, const void* large, 
                                              int order);
 int coreg_multi_prepare_reference_helioprojective(coreg_multi* m, const void* large, int dtype, int32_t ny, int32_t nx,
                                                   const coreg_wcs2d* hdr_large, const coreg_wcs2d* hdr_small, int order);
+/* coreg_smooth_small / coreg_set_reference_smoothing on every device's context */
+int coreg_multi_smooth_small(coreg_multi* m, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
+int coreg_multi_set_reference_smoothing(coreg_multi* m, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
 /* coreg_set_reference_rotation / coreg_set_small_rotation on every device's context */
 int coreg_multi_set_reference_rotation(coreg_multi* m, const coreg_diffrot* rot);
 int coreg_multi_set_small_rotation(coreg_multi* m, const coreg_diffrot* rot);

@@ -1,0 +1,42 @@
+"""
+The planner of the NaN-aware smoothing (csrc/smooth_plan.hpp) on the host, plain and under AddressSanitizer +
+UndefinedBehaviorSanitizer (tests/native/smooth_rules.cpp): every table refusal either side of each limit, and the launch
+geometry of both passes -- every pixel written exactly once, nothing outside the image or the LDS a work item asks for --
+for the shapes 1x1, 1x300, 300x1, 257x3, 5x5 with r = 0, 1, 8, 64.
+"""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+
+
+def _build(tmp_path, name, extra):
+    exe = str(tmp_path / name)
+    cc = subprocess.run(["g++", "-std=c++17", "-O1", "-g", *extra, "-Wall", "-Wextra",
+                         os.path.join(HERE, "native", "smooth_rules.cpp"), "-o", exe], capture_output=True, text=True)
+    return exe, cc
+
+
+def _run(exe):
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "ok: smooth rules" in r.stdout, (r.stdout + r.stderr)[-3000:]
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_smooth_rules(tmp_path):
+    """The plain build: runs wherever there is a host compiler."""
+    exe, cc = _build(tmp_path, "smooth_rules", [])
+    assert cc.returncode == 0, cc.stderr[-2000:]
+    _run(exe)
+
+
+@pytest.mark.skipif(shutil.which("g++") is None, reason="no g++")
+def test_smooth_rules_under_asan_ubsan(tmp_path):
+    exe, cc = _build(tmp_path, "smooth_rules_san", ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"])
+    if cc.returncode != 0 and "sanitize" in cc.stderr and "cannot find" in cc.stderr:
+        pytest.skip("no sanitizer runtime for g++ here")
+    assert cc.returncode == 0, cc.stderr[-2000:]
+    _run(exe)
