@@ -59,6 +59,25 @@ class DiffRot(C.Structure):
     _fields_ = [("delta_t_days", C.c_double), ("c0", C.c_double), ("c1", C.c_double), ("c2", C.c_double)]
 
 
+class DespikeParams(C.Structure):
+    """coreg_despike_params (include/coreg_hip.h): the median/MAD despiking rule."""
+    _fields_ = [("radius", C.c_int32), ("n_iter", C.c_int32), ("min_neighbours", C.c_int32), ("sign", C.c_int32),
+                ("replace", C.c_int32), ("reserved", C.c_int32), ("nsigma", C.c_double), ("floor", C.c_double)]
+    SIGN = {"positive": 0, "both": 1}
+    REPLACE = {"nan": 0, "median": 1}
+
+    @classmethod
+    def of(cls, params):
+        """From a dict as utils.despiking.despike_params returns it (missing keys: its defaults; `sign` and `replace` by
+        name or by number).  The library checks the values."""
+        if isinstance(params, cls):
+            return params
+        p = dict(radius=2, n_iter=2, min_neighbours=5, sign="positive", replace="nan", nsigma=5.0, floor=0.0)
+        p.update(params)
+        return cls(int(p["radius"]), int(p["n_iter"]), int(p["min_neighbours"]), int(cls.SIGN.get(p["sign"], p["sign"])),
+                   int(cls.REPLACE.get(p["replace"], p["replace"])), 0, float(p["nsigma"]), float(p["floor"]))
+
+
 class Stats(C.Structure):
     _fields_ = [("sweep_kernel_ms", C.c_double), ("precompute_ms", C.c_double), ("total_gpu_ms", C.c_double),
                 ("n_lags", C.c_int64), ("n_grid_points", C.c_int64), ("n_active_points", C.c_int64),
@@ -256,6 +275,9 @@ SYMBOLS = [
     ("coreg_smooth_small", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_set_reference_smoothing", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_get_small", C.c_int, [_P, _P, C.c_int]),
+    ("coreg_despike_small", C.c_int, [_P, C.POINTER(DespikeParams), C.POINTER(C.c_int64)]),
+    ("coreg_set_reference_despike", C.c_int, [_P, C.POINTER(DespikeParams)]),
+    ("coreg_last_reference_despike", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("coreg_resample_carrington", C.c_int, [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.c_int, _P]),
     ("coreg_resample_helioprojective", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
     ("coreg_resample_helioprojective_f64", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
@@ -318,6 +340,8 @@ SYMBOLS = [
     ("coreg_pixels_smooth_large", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_pixels_smooth_small", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_pixels_get_image", C.c_int, [_P, C.c_int, _P]),
+    ("coreg_pixels_despike_large", C.c_int, [_P, C.POINTER(DespikeParams), C.POINTER(C.c_int64)]),
+    ("coreg_pixels_despike_small", C.c_int, [_P, C.POINTER(DespikeParams), C.POINTER(C.c_int64)]),
     ("coreg_pixels_last_timing", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("coreg_pixels_destretch", C.c_int,
      [_P, _P, C.c_int, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PixelsField), _P, _P]),
@@ -351,6 +375,8 @@ SYMBOLS = [
     ("coreg_multi_prepare_reference_helioprojective", C.c_int, [_P, _P, C.c_int, C.c_int32, C.c_int32, _WP, _WP, C.c_int]),
     ("coreg_multi_smooth_small", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_multi_set_reference_smoothing", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
+    ("coreg_multi_despike_small", C.c_int, [_P, C.POINTER(DespikeParams), C.POINTER(C.c_int64)]),
+    ("coreg_multi_set_reference_despike", C.c_int, [_P, C.POINTER(DespikeParams)]),
     ("coreg_multi_set_reference_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_multi_set_small_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_multi_sweep_carrington", C.c_int,
@@ -560,6 +586,26 @@ class _ImageIntake:
             return
         wy, wx = self._tables(tables)
         self._chk(fn(getattr(self, self._ptr), wy.ctypes.data, len(wy), wx.ctypes.data, len(wx)))
+
+    def _despike(self, fn, params):
+        """One despiking call `fn(pointer, params, counts)`; the pixels flagged per pass as a list of int."""
+        p = DespikeParams.of(params)
+        counts = (C.c_int64 * 8)()
+        self._chk(fn(getattr(self, self._ptr), C.byref(p), counts))
+        return [int(v) for v in counts[:max(0, min(8, p.n_iter))]]
+
+    def despike_small(self, params):
+        """NaN-aware median/MAD despiking of the resident image to align (coreg_despike_small; the rule:
+        include/coreg_hip.h): `params` is a dict of radius, n_iter, nsigma, floor, min_neighbours, sign, replace (missing
+        keys: the defaults).  Call it after `threshold_small` and before `smooth_small`.  Returns the pixels flagged per
+        pass."""
+        return self._despike(getattr(self._lib, self._prefix + "despike_small"), params)
+
+    def set_reference_despike(self, params):
+        """The despiking every reference preparation that follows applies to the source image before its smoothing and
+        resample (coreg_set_reference_despike); None for none (the default).  It stays until set again."""
+        fn = getattr(self._lib, self._prefix + "set_reference_despike")
+        self._chk(fn(getattr(self, self._ptr), None if params is None else C.byref(DespikeParams.of(params))))
 
     def prepare_reference_carrington(self, large, hdr_large, grid: Grid, solar_r, order=2):
         w = wcs_from_header(hdr_large, carrington=True)
@@ -801,6 +847,20 @@ class CoregHandle(_ImageIntake):
     def pixels_smooth_small(self, tables):
         wy, wx = self._tables(tables)
         self._chk(self._lib.coreg_pixels_smooth_small(self._h, wy.ctypes.data, len(wy), wx.ctypes.data, len(wx)))
+
+    def pixels_despike_large(self, params):
+        """coreg_pixels_despike_large: the resident large image despiked in place; the pixels flagged per pass."""
+        return self._despike(self._lib.coreg_pixels_despike_large, params)
+
+    def pixels_despike_small(self, params):
+        return self._despike(self._lib.coreg_pixels_despike_small, params)
+
+    def last_reference_despike(self):
+        """coreg_last_reference_despike: the pixels the last reference preparation flagged per pass (8 entries, zero past
+        its n_iter; they cover the pixels that were processed, the crop box when one was used)."""
+        counts = (C.c_int64 * 8)()
+        self._chk(self._lib.coreg_last_reference_despike(self._h, counts))
+        return [int(v) for v in counts]
 
     def pixels_get_image(self, which, shape):
         """coreg_pixels_get_image: the large ("large" / 0) or small ("small" / 1) image as it stands, float64."""
@@ -1183,6 +1243,9 @@ class MultiHandle(_ImageIntake):
 
     def get_small(self, shape, dtype=np.float64):
         return self.primary.get_small(shape, dtype)
+
+    def last_reference_despike(self):
+        return self.primary.last_reference_despike()
 
     def last_counts(self):
         """Per-lag sample counts of the last sweep over all devices, laid out like its map (CoregHandle.last_counts)."""

@@ -329,13 +329,24 @@ static int prepare_reference(coreg_handle* h, const void* large, const PixFmt& f
                              ResampleArgs& a, bool out_f32) {
     CropRect crop = {0, 0, a.W, a.H};
     const bool smooth = !h->ref_smooth_x.empty();
+    // (a pixel's despiked value depends on the source pixels within n_iter x radius of it: the box grows by that much too)
+    const int despike_reach = h->has_ref_despike ? h->ref_despike.n_iter * h->ref_despike.radius : 0;
     if (kind == SRC_HOST)
-        RETCHK(reference_crop(h, mode, a, order, &crop, smooth ? (int)h->ref_smooth_x.size() / 2 : 0,
-                              smooth ? (int)h->ref_smooth_y.size() / 2 : 0));
+        RETCHK(reference_crop(h, mode, a, order, &crop, despike_reach + (smooth ? (int)h->ref_smooth_x.size() / 2 : 0),
+                              despike_reach + (smooth ? (int)h->ref_smooth_y.size() / 2 : 0)));
     const bool carr = mode == MODE_TRANSLATE;
     trace(carr ? "prepare_carrington: crop box known" : "prepare_helioprojective: crop box known");
     bool f32;
     RETCHK(upload_reference_source(h, large, a.W, a.H, fmt, &f32, kind, &a.img, crop));
+    h->ref_despike_passes = 0;
+    if (h->has_ref_despike) {
+        // the pixels the smoothing or the resample reads, despiked into a buffer of the handle (a device source stays as it
+        // is); the rim of a rectangle, despiked from a window the rectangle cuts, is never read
+        DevBuf* done = nullptr;
+        RETCHK(despike_image(h, a.img, f32, crop.h, crop.w, &h->ref_despike, DESPIKE_SLOT_REFERENCE, &done));
+        a.img = done->p;
+        h->ref_despike_passes = h->ref_despike.n_iter;
+    }
     if (smooth) {
         // the pixels the resample reads (the rectangle, or the whole image where it lies: a device source stays as it is)
         // smoothed into a buffer of the handle; the rim of a rectangle, smoothed without its outer taps, is never read
@@ -548,6 +559,43 @@ int coreg_set_reference_smoothing(coreg_handle* h, const double* wy, int32_t n_w
     h->ref_smooth_y.assign(wy, wy + n_wy);
     h->ref_smooth_x.assign(wx, wx + n_wx);
     return COREG_OK;
+}
+
+// Median/MAD despiking of the resident image to align, in place as far as the caller sees: the passes write buffers of the
+// handle, the last of which then changes places with the image's.  The image keeps the dtype it is held in.
+int coreg_despike_small(coreg_handle* h, const coreg_despike_params* params, int64_t* n_flagged) {
+    if (!h) return COREG_EINVAL;
+    if (!h->small.p) return fail(h, COREG_ESTATE, "coreg_set_small has not been called");
+    const DespikePlan p = despike_plan(h->sH, h->sW, params);
+    if (p.code != COREG_OK) return fail(h, p.code, p.msg);  // (before the join: a refused call changes nothing)
+    RETCHK(bind_device(h));                                 // (joins a pending upload: join_small)
+    DevBuf* done = nullptr;
+    RETCHK(despike_image(h, h->small.p, h->small_f32, h->sH, h->sW, params, DESPIKE_SLOT_IMAGE, &done));
+    std::swap(h->small, *done);
+    HIPCHK(buffer_mean(h, h->small.p, h->small_f32, (long long)h->sW * h->sH, h->pivots.as<double>() + 1, h->stream));
+    if (n_flagged) RETCHK(despike_read_counts(h, DESPIKE_SLOT_IMAGE, params->n_iter, n_flagged));
+    return COREG_OK;
+}
+
+int coreg_set_reference_despike(coreg_handle* h, const coreg_despike_params* params) {
+    if (!h) return COREG_EINVAL;
+    if (!params) {
+        h->has_ref_despike = false;
+        return COREG_OK;
+    }
+    if (const char* why = despike_params_refusal(params)) return fail(h, COREG_EINVAL, why);
+    h->ref_despike = *params;
+    h->has_ref_despike = true;
+    return COREG_OK;
+}
+
+int coreg_last_reference_despike(coreg_handle* h, int64_t* n_flagged8) {
+    if (!h) return COREG_EINVAL;
+    if (!n_flagged8) return fail(h, COREG_EINVAL, "last_reference_despike: null pointer");
+    for (int i = 0; i < kDespikeMaxIter; ++i) n_flagged8[i] = 0;
+    if (h->ref_despike_passes < 1) return COREG_OK;  // the last preparation despiked nothing
+    RETCHK(bind_device_nowait(h));
+    return despike_read_counts(h, DESPIKE_SLOT_REFERENCE, h->ref_despike_passes, n_flagged8);
 }
 
 int coreg_get_small(coreg_handle* h, void* out, int dtype) {

@@ -29,6 +29,16 @@ int coreg_pixels_smooth_small(coreg_handle* h, const double* wy, int32_t n_wy, c
     return pixels_smooth(h, 1, wy, n_wy, wx, n_wx);
 }
 
+int coreg_pixels_despike_large(coreg_handle* h, const coreg_despike_params* params, int64_t* n_flagged) {
+    if (!h) return COREG_EINVAL;
+    return pixels_despike(h, 0, params, n_flagged);
+}
+
+int coreg_pixels_despike_small(coreg_handle* h, const coreg_despike_params* params, int64_t* n_flagged) {
+    if (!h) return COREG_EINVAL;
+    return pixels_despike(h, 1, params, n_flagged);
+}
+
 int coreg_pixels_get_image(coreg_handle* h, int which, double* out) {
     if (!h) return COREG_EINVAL;
     return pixels_get_image(h, which, out);

@@ -38,6 +38,7 @@ using namespace coreg;
 #include "host_state.hpp"        // FixLaunch, coreg_handle
 #include "host_upload.hpp"       // uploads, FITS decode, reference crop
 #include "host_smooth.hpp"       // NaN-aware separable smoothing of a resident image: plan + two launches
+#include "host_despike.hpp"      // median/MAD despiking of a resident image: plan + one launch per pass
 #include "host_plan.hpp"         // lag checks, the planners' view of the handle, tile groups, precompute
 #include "host_fix_launch.hpp"   // re-evaluation work space, k_finalize, fix kernels of a launch
 #include "sweep_variant.hpp"     // the list of k_sweep instantiations and the rule that picks one (no HIP in it)

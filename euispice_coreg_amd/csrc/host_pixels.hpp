@@ -126,6 +126,26 @@ int pixels_smooth(coreg_handle* h, int which, const double* wy, int32_t n_wy, co
     return smooth_image(h, img->p, false, H, W, wy, n_wy, wx, n_wx, img->as<double>());
 }
 
+// median/MAD despiking (host_despike.hpp) of the large (which = 0) or small (1) image, in place as far as the caller sees:
+// the buffer of the last pass changes places with the image's (both float64)
+int pixels_despike(coreg_handle* h, int which, const coreg_despike_params* params, int64_t* n_flagged) {
+    PixelsState* st = pixels_state(h, false);
+    DevBuf* img = st ? (which ? &st->small : &st->large) : nullptr;
+    if (!img || !img->p) return fail(h, COREG_ESTATE, which ? "pixels: the small image is not set" : "pixels: the large image is not set");
+    const int W = which ? st->sW : st->lW, H = which ? st->sH : st->lH;
+    const DespikePlan p = despike_plan(H, W, params);
+    if (p.code != COREG_OK) return fail(h, p.code, p.msg);  // (a refused call changes nothing)
+    RETCHK(bind_device(h));
+    if (which) st->n_rot = 0;
+    else st->bW = st->bH = 0;
+    st->forget_last();
+    DevBuf* done = nullptr;
+    RETCHK(despike_image(h, img->p, false, H, W, params, DESPIKE_SLOT_IMAGE, &done));
+    std::swap(*img, *done);
+    if (n_flagged) RETCHK(despike_read_counts(h, DESPIKE_SLOT_IMAGE, params->n_iter, n_flagged));
+    return COREG_OK;
+}
+
 // the edge lists of the mutual-information score (csrc/pixels_bins.hpp: 1 to 31 entries, finite, strictly increasing)
 int pixels_set_bins(coreg_handle* h, const double* edges_small, int32_t n_small, const double* edges_large, int32_t n_large) {
     if (!bins_edges_ok(edges_small, n_small) || !bins_edges_ok(edges_large, n_large))

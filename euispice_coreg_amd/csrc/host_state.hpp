@@ -101,6 +101,14 @@ struct coreg_handle {
     // coreg_set_reference_smoothing, which stay until set again or cleared
     DevBuf sm_num, sm_den, sm_out;
     std::vector<double> ref_smooth_y, ref_smooth_x;  // both empty: off
+    // median/MAD despiking (host_despike.hpp): the two buffers its passes write in turn (the last one is exchanged with
+    // `small` by coreg_despike_small; what the smoothing or the resample reads while the reference despiking is set), the
+    // flagged counts uint64 [2][8] on the device (image / last reference preparation), the parameters of
+    // coreg_set_reference_despike, which stay until set again or cleared, and the passes of the last preparation
+    DevBuf ds_a, ds_b, ds_counts;
+    coreg_despike_params ref_despike = {};
+    bool has_ref_despike = false;
+    int ref_despike_passes = 0;
     CarrTables tabs;
     std::vector<double> tabs_key;
     bool tabs_uploaded = false;  // the device tables are those of `tabs`

@@ -32,3 +32,4 @@
 #include "kernels_pixels_mi.hpp" // ... its mutual-information score: joint histograms in LDS, one pass
 #include "kernels_pixels_lct.hpp" // ... its apodized windows: weighted Pearson sums, two passes
 #include "kernels_smooth.hpp"     // NaN-aware separable smoothing: row pass (num, den), column pass (num / den)
+#include "kernels_despike.hpp"    // median/MAD despiking: one pass per launch, window in LDS, median and MAD by sorting network

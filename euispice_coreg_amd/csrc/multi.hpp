@@ -1018,6 +1018,16 @@ int coreg_multi_set_reference_smoothing(coreg_multi* m, const double* wy, int32_
     return multi_run(m, [&](int k) { return coreg_set_reference_smoothing(m->h[k], wy, n_wy, wx, n_wx); });
 }
 
+// (every device holds the same image and flags the same pixels: the counts are those of the first device)
+int coreg_multi_despike_small(coreg_multi* m, const coreg_despike_params* params, int64_t* n_flagged) {
+    if (!m) return COREG_EINVAL;
+    return multi_run(m, [&](int k) { return coreg_despike_small(m->h[k], params, k == 0 ? n_flagged : nullptr); });
+}
+int coreg_multi_set_reference_despike(coreg_multi* m, const coreg_despike_params* params) {
+    if (!m) return COREG_EINVAL;
+    return multi_run(m, [&](int k) { return coreg_set_reference_despike(m->h[k], params); });
+}
+
 int coreg_multi_set_reference_on_grid(coreg_multi* m, const void* ref, int dtype, int32_t gy, int32_t gx) {
     if (!m) return COREG_EINVAL;
     return multi_run(m, [&](int k) { return coreg_set_reference_on_grid(m->h[k], ref, dtype, gy, gx); });

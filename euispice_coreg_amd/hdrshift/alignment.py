@@ -33,6 +33,13 @@ surface.  Differences, all deliberate and listed in DESIGN.md:
     (fwhm_y, fwhm_x) or a pair of weight tables (utils/smoothing.py: `smoothing_tables`), in pixels of each image's own grid
     or, `smooth_unit="arcsec"`, converted with each image's own CDELT.  A non-finite pixel stays NaN and gives nothing to
     its neighbours.  None (the default) changes nothing.
+  * `despike_small=` / `despike_large=` (every `align_using_*`, every method): a NaN-aware median/MAD despiking of the
+    image to align (after its thresholds, before its smoothing) and of the reference image (before its smoothing and its
+    once-only resample) on the GPU: cosmic-ray hits and hot pixels, which a global `small_fov_value_max` either misses or
+    cuts together with bright real structure (include/coreg_hip.h: coreg_despike_small states the rule).  True (the
+    defaults), a number of sigmas, or a dict of radius, nsigma, floor, min_neighbours, sign, replace, n_iter
+    (utils/despiking.py: `despike_params`).  `self.last_despiked` = {"small": [...], "large": [...]} holds the pixels
+    flagged per pass (those of the reference image cover the rectangle that was uploaded).  None changes nothing.
 There is no CPU fallback: without the HIP library / a GPU the sweep raises.
 """
 from __future__ import annotations
@@ -45,6 +52,7 @@ import numpy as np
 
 from .. import _lib, parallel
 from ..utils import diffrot, fits_io, header as hdrutil, wcs_tan
+from ..utils.despiking import despike_params, despike_tag
 from ..utils.smoothing import smoothing_tables
 from .alignment_results import AlignmentResults
 
@@ -141,7 +149,7 @@ class Alignment:
                  small_fov_value_max=None, counts_cpu_max=40, large_fov_window=-1, small_fov_window=-1,
                  path_save_figure=None, reprojection_order=2, force_crota_0=False, unit_lag="arcsec",
                  cdelt_semantics="intended", device=None, differential_rotation="reference", min_overlap=None,
-                 smooth_small=None, smooth_large=None, smooth_unit="pixel"):
+                 smooth_small=None, smooth_large=None, smooth_unit="pixel", despike_small=None, despike_large=None):
         self.large_fov_known_pointing = large_fov_known_pointing
         self.small_fov_to_correct = small_fov_to_correct
         self.lag_crval1 = lag_crval1
@@ -189,6 +197,10 @@ class Alignment:
             smoothing_tables(arg, what, (1.0, 1.0) if smooth_unit == "pixel" else (0.0, 0.0))
         self.smooth_small, self.smooth_large, self.smooth_unit = smooth_small, smooth_large, smooth_unit
         self._smooth_large_tables = None  # (wy, wx) of the sweep being run, None: none
+        # (their checks, before anything is loaded) the rule of each image as a dict, None: none
+        self.despike_small = despike_params(despike_small, "despike_small")
+        self.despike_large = despike_params(despike_large, "despike_large")
+        self.last_despiked = None       # {"small": [...], "large": [...]}: pixels flagged per pass in the last sweep
         self.last_counts = None         # per-lag sample counts of the last sweep, shaped like its map
         self.last_bins = None           # (edges_small, edges_large) of the last "mutual_information" sweep
         self._bins = None               # `bins` of the sweep being run, as parse_bins leaves it
@@ -253,9 +265,11 @@ class Alignment:
 
     def _carrington_tag(self, solar_r, rot_large):
         """Identity of the reference image on the Carrington grid: a resident one prepared for another rotation (another
-        `reference_date`, another band) or with another smoothing is not this one."""
-        return self._reference_tag("carrington", self.lonlims, self.latlims, self.shape, solar_r, rot_large or (),
-                                   *(self._smooth_large_tables or ()))
+        `reference_date`, another band) or with another smoothing or despiking is not this one.  (Without
+        `despike_large` the tag is what it was before that keyword existed.)"""
+        tag = self._reference_tag("carrington", self.lonlims, self.latlims, self.shape, solar_r, rot_large or (),
+                                  *(self._smooth_large_tables or ()))
+        return tag if tag is None or self.despike_large is None else tag + (despike_tag(self.despike_large),)
 
     def _smoothing(self, which):
         """(wy, wx) of `smooth_small` / `smooth_large` in pixels of that image's grid as its header stands, or None."""
@@ -448,13 +462,16 @@ class Alignment:
         self.hdr_small = hg
 
     def _find_best_header_parameters(self, ang2pipi=True, fov_limits=None, remove_fov_limits=None):
-        """`_sweep`; the long-lived handle it ran on does not keep this object's reference smoothing, whatever happened."""
+        """`_sweep`; the long-lived handle it ran on keeps neither this object's reference smoothing nor its reference
+        despiking, whatever happened."""
         self._sweep_handle = None
         try:
             return self._sweep(ang2pipi, fov_limits, remove_fov_limits)
         finally:
             if self._sweep_handle is not None and self._smooth_large_tables is not None:
                 self._sweep_handle.set_reference_smoothing(None)
+            if self._sweep_handle is not None and self.despike_large is not None:
+                self._sweep_handle.set_reference_despike(None)
             self._sweep_handle = None
 
     def _sweep(self, ang2pipi=True, fov_limits=None, remove_fov_limits=None):
@@ -512,6 +529,10 @@ class Alignment:
         self._smooth_large_tables = self._smoothing("large")
         self._sweep_handle = h
         h.set_reference_smoothing(self._smooth_large_tables)
+        # ... and its reference despiking (set only where the keyword is: None runs no new code)
+        if self.despike_large is not None:
+            h.set_reference_despike(self.despike_large)
+        self.last_despiked = {"small": [], "large": []}
         # alignment.py:844-861: thresholds, then the box to remove, then the sub-FOV re-grid
         on_device = (remove_fov_limits is None) and (fov_limits is None)
         n_finite = None
@@ -552,17 +573,22 @@ class Alignment:
 
         def finite_pixels():
             """alignment.py:654-656, after the first reference preparation (the check itself reads the uploaded pixels).
-            The smoothing of the image to align follows its thresholds: a masked pixel cannot bleed."""
-            nonlocal n_finite, smooth_small
+            The despiking of the image to align follows its thresholds and its smoothing follows both: a masked pixel
+            is no neighbour and cannot bleed, a spike is cut before it can be spread."""
+            nonlocal n_finite, smooth_small, despike_small
             if n_finite is None:
                 n_finite = h.threshold_small(self.small_fov_value_min, self.small_fov_value_max)
             if n_finite == 0:
                 raise ValueError("minimum or maximum value have set all small FOV to nan")
+            if despike_small is not None:
+                self.last_despiked["small"] = h.despike_small(despike_small)
+                smoothed_small[0], despike_small = True, None
             if smooth_small is not None:
                 h.smooth_small(smooth_small)
                 smoothed_small[0], smooth_small = True, None
 
-        smoothed_small = [False]
+        smoothed_small = [False]  # the resident image is no longer the thresholded file's: despiked, smoothed or both
+        despike_small = self.despike_small
 
         if n_finite is not None:
             finite_pixels()
@@ -607,6 +633,7 @@ class Alignment:
 
         out = np.full(lags.shape + (len(solar_rs),), np.nan)
         counts = np.full(out.shape, np.nan)
+        on_grid_despiked = False  # the reference was despiked in the pixel-lag sweep's image slot, its counts are taken
         for kk, solar_r in enumerate(solar_rs):
             if self.coordinate_frame == "final_carrington":
                 grid = _lib.Grid(self.lonlims, self.latlims, self.shape, numpy_lat_trig=True)
@@ -641,11 +668,15 @@ class Alignment:
                     target = self.hdr_small
                 else:
                     big = np.asarray(self._large_pixels(), dtype=np.float64)  # quirk Q1: float64
-                    if self._smooth_large_tables is not None:
-                        # no resample here, so no preparation to smooth in: the pixel-lag sweep's image slot serves
+                    if self._smooth_large_tables is not None or self.despike_large is not None:
+                        # no resample here, so no preparation to despike or smooth in: the pixel-lag sweep's image slot serves
                         h.pixels_set_large(big)
-                        h.pixels_smooth_large(self._smooth_large_tables)
+                        if self.despike_large is not None:
+                            self.last_despiked["large"] = h.pixels_despike_large(self.despike_large)
+                        if self._smooth_large_tables is not None:
+                            h.pixels_smooth_large(self._smooth_large_tables)
                         big = h.pixels_get_image("large", big.shape)
+                        on_grid_despiked = True
                     h.set_reference_on_grid(big)
                     target = self.hdr_large
 
@@ -681,6 +712,9 @@ class Alignment:
             out[..., kk] = np.asarray(part).reshape(lags.shape)
             counts[..., kk] = np.asarray(n_part).reshape(lags.shape)
         self.last_counts = counts
+        if self.despike_large is not None and not on_grid_despiked:
+            # (of the last preparation: the one this sweep ran, or the one that left the resident reference it re-used)
+            self.last_despiked["large"] = h.last_reference_despike()[:self.despike_large["n_iter"]]
         out = apply_min_overlap(out, counts, self.min_overlap)
         self.last_stats = h.last_stats()
         if hasattr(h, "drop_small_keepalive"):

@@ -32,7 +32,7 @@ class AlignmentSpice(Alignment):
                  small_fov_window=-1, parallelism=False, counts_cpu_max=40, display_progress_bar=False,
                  path_save_figure=None, wavelength_interval_to_sum="all", sub_fov_window="all", level=None,
                  cdelt_semantics="intended", device=None, differential_rotation="reference", min_overlap=None,
-                 smooth_small=None, smooth_large=None, smooth_unit="pixel"):
+                 smooth_small=None, smooth_large=None, smooth_unit="pixel", despike_small=None, despike_large=None):
         super().__init__(large_fov_known_pointing=large_fov_known_pointing, small_fov_to_correct=small_fov_to_correct,
                          lag_crval1=lag_crval1, lag_crval2=lag_crval2, lag_cdelt1=lag_cdelt1, lag_cdelt2=lag_cdelt2,
                          lag_crota=lag_crota, display_progress_bar=display_progress_bar, lag_solar_r=lag_solar_r,
@@ -40,7 +40,7 @@ class AlignmentSpice(Alignment):
                          small_fov_window=small_fov_window, path_save_figure=path_save_figure,
                          cdelt_semantics=cdelt_semantics, device=device, differential_rotation=differential_rotation,
                          min_overlap=min_overlap, smooth_small=smooth_small, smooth_large=smooth_large,
-                         smooth_unit=smooth_unit)
+                         smooth_unit=smooth_unit, despike_small=despike_small, despike_large=despike_large)
         self.sub_fov_window = sub_fov_window
         self.extend_pixel_size = None
         self.cut_from_center = None

@@ -36,6 +36,7 @@ import numpy as np
 from .. import _lib, parallel
 from ..hdrshift.alignment import Alignment
 from ..utils import fits_io
+from ..utils.despiking import despike_params
 
 
 def build_sublists(n_files: int, sublist_length: int, overlap: int):
@@ -63,14 +64,17 @@ def jitter_correction_imagers(list_files_input, path_files_output, lonlims=None,
                               plot_all_figures=False, parallelism=True, cpu_count=None, small_fov_value_max=None,
                               small_fov_value_min=None, alignement_method="carrington", device=None, prefetch=2,
                               pipeline_depth=2, differential_rotation="reference", method="correlation",
-                              min_overlap=None, bins=None, smooth_small=None, smooth_large=None, smooth_unit="pixel"):
-    """See the module docstring.  `smooth_small`, `smooth_large`, `smooth_unit`: as on hdrshift.Alignment (the resident
-    reference of a sublist is prepared smoothed, once).  `method`, `min_overlap`: as on hdrshift.Alignment -- "residus_masked" with a floor on
+                              min_overlap=None, bins=None, smooth_small=None, smooth_large=None, smooth_unit="pixel",
+                              despike_small=None, despike_large=None):
+    """See the module docstring.  `smooth_small`, `smooth_large`, `smooth_unit`, `despike_small`, `despike_large`: as on
+    hdrshift.Alignment (the resident reference of a sublist is prepared despiked and smoothed, once).  `method`, `min_overlap`: as on hdrshift.Alignment -- "residus_masked" with a floor on
     the overlap is the sharper score for frames of one instrument; `bins`: of method "mutual_information"
     (alignement_method "carrington" only), as `Alignment.align_using_carrington` takes it.  Returns the list of (index_to_align, index_ref, AlignmentResults) this rank
     produced, in processing order (the reference returns None; the corrected files are the product)."""
     if overlap == 0:
         raise ValueError("number of overlapping images between sublists can not be equal to 0.")
+    despike_params(despike_small, "despike_small")  # (their checks, before any file is read)
+    despike_params(despike_large, "despike_large")
     list_files_input = list(list_files_input)
     dates = [fits_io.read_header(p, window_files_input)["DATE-AVG"] for p in list_files_input]
     parameter_alignment = {"lag_crval1": lag_crval1, "lag_crval2": lag_crval2, "lag_cdelt1": lag_cdelt1,
@@ -111,6 +115,7 @@ def jitter_correction_imagers(list_files_input, path_files_output, lonlims=None,
             small_fov_value_min=small_fov_value_min, unit_lag=unit_lag, device=dev,
             differential_rotation=differential_rotation, method=method, min_overlap=min_overlap, bins=bins,
             smooth_small=smooth_small, smooth_large=smooth_large, smooth_unit=smooth_unit,
+            despike_small=despike_small, despike_large=despike_large,
             _preloaded_small=fut_image.result(), _return_corr=True, _handle_slot=slot0 + slots.id, **kwargs_carrington)
         out_path = os.path.join(path_files_output, os.path.basename(list_files_input[index_to_align]))
         # sub-lag Gaussian fit + corrected FITS in a writer thread: the GPU is already on the next image
@@ -190,7 +195,8 @@ def _align_hrieuv_with_hrieuv(large_fov_fits_path, large_fov_window, small_fov_p
                               alignement_method="carrington", path_output_figures=None, fov_limits=None, device=None,
                               _preloaded_small=None, _return_corr=False, _handle_slot=0,
                               differential_rotation="reference", method="correlation", min_overlap=None, bins=None,
-                              smooth_small=None, smooth_large=None, smooth_unit="pixel"):
+                              smooth_small=None, smooth_large=None, smooth_unit="pixel", despike_small=None,
+                              despike_large=None):
     """jitter_correction.py:177-256: one image against the sublist's reference.  `_return_corr`: hand back
     (Alignment, raw correlation array) so that the caller can build the AlignmentResults off the critical path."""
     A = Alignment(large_fov_known_pointing=large_fov_fits_path, large_fov_window=large_fov_window,
@@ -198,7 +204,8 @@ def _align_hrieuv_with_hrieuv(large_fov_fits_path, large_fov_window, small_fov_p
                   small_fov_value_max=small_fov_value_max, small_fov_value_min=small_fov_value_min,
                   parallelism=parallelism, counts_cpu_max=cpu_count, unit_lag=unit_lag, device=device,
                   differential_rotation=differential_rotation, min_overlap=min_overlap, smooth_small=smooth_small,
-                  smooth_large=smooth_large, smooth_unit=smooth_unit, **parameter_alignment)
+                  smooth_large=smooth_large, smooth_unit=smooth_unit, despike_small=despike_small,
+                  despike_large=despike_large, **parameter_alignment)
     A.shard_lags = False
     A._preloaded_small = _preloaded_small
     A._handle_slot = _handle_slot

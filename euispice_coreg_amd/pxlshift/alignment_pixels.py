@@ -34,6 +34,13 @@ the sub-resolution -- the anti-alias filter the order-1 point sampling of the la
 (fwhm_y, fwhm_x) or a pair of weight tables, in pixels of the image's own grid (utils/smoothing.py: `smoothing_tables`;
 include/coreg_hip.h: coreg_pixels_smooth_large states the rule).  Default mutual-information edges are then the quantiles
 of the smoothed images.
+
+`despike_large=` / `despike_small=` (the same two calls; not in the reference): a NaN-aware median/MAD despiking of either
+image on the GPU, right after its pixels are set and before the smoothing, the solar-rotation shift and the
+sub-resolution.  True (the defaults), a number of sigmas or a dict (utils/despiking.py: `despike_params`;
+include/coreg_hip.h: coreg_despike_small states the rule).  `self.last_despiked` = {"small": [...], "large": [...]} holds
+the pixels flagged per pass.  Default mutual-information edges are the quantiles of the images as the sweep sees them:
+despiked, then smoothed.
 """
 from __future__ import annotations
 
@@ -42,6 +49,7 @@ import numpy as np
 from .. import _lib
 from ..hdrshift.alignment import apply_min_overlap, library_method, min_overlap_floor
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
+from ..utils.despiking import despike_params
 from ..utils.smoothing import smoothing_tables  # noqa: F401  (the tables of `smooth_large=` / `smooth_small=`)
 
 _RETURN_TYPES = ("corr", "PixelAlignmentResults")
@@ -196,6 +204,7 @@ class AlignmentPixels:
         self.ratio_res_1 = self.ratio_res_2 = None
         self.last_timing = None
         self.last_counts = None
+        self.last_despiked = None  # {"small": [...], "large": [...]}: pixels flagged per pass in the last call
 
     # ------------------------------------------------------------------------------------------------------------
     def _return_shift_large_fov_solar_rotation(self):
@@ -228,7 +237,7 @@ class AlignmentPixels:
 
     def host_plan(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
                   method="correlation", min_overlap=None, tile_shape=None, bins=None, tile_step=None,
-                  apodization=None, smooth_large=None, smooth_small=None) -> dict:
+                  apodization=None, smooth_large=None, smooth_small=None, despike_large=None, despike_small=None) -> dict:
         """Everything of a `find_best_parameters` call that is decided on the host (numpy only, no GPU); with
         `tile_shape` = (rows, columns), of a `find_local_shifts` call: the plan then holds the tile grid too.
         `bins` (method "mutual_information" only, ValueError with any other): an integer 2 <= B <= 32 (default 16) --
@@ -240,9 +249,13 @@ class AlignmentPixels:
         weight tables as `plan["window"]` = (wy, wx), None without.  `smooth_large`, `smooth_small` (`smoothing_tables`, in
         pixels of each image's own grid): the plan holds the table pairs under those names, None without; with either,
         `bins` as a number cannot be turned into edges here -- they are quantiles of the smoothed images, which the GPU
-        makes -- and the plan holds the number as `plan["bins_pending"]` and `plan["bins"]` = None until the call has them."""
+        makes -- and the plan holds the number as `plan["bins_pending"]` and `plan["bins"]` = None until the call has them.
+        `despike_large`, `despike_small` (`despike_params`): held under those names as dicts, None without; what is said of
+        `bins` with a smoothing holds with a despiking too."""
         smooth = {"smooth_large": smoothing_tables(smooth_large, "smooth_large"),
-                  "smooth_small": smoothing_tables(smooth_small, "smooth_small")}
+                  "smooth_small": smoothing_tables(smooth_small, "smooth_small"),
+                  "despike_large": despike_params(despike_large, "despike_large"),
+                  "despike_small": despike_params(despike_small, "despike_small")}
         if method == MUTUAL_INFORMATION:
             method_code = _lib.METHOD_MUTUAL_INFORMATION
         else:
@@ -283,7 +296,7 @@ class AlignmentPixels:
         if method == MUTUAL_INFORMATION:
             bins = DEFAULT_BINS if bins is None else bins
             if (isinstance(bins, (int, np.integer)) and not isinstance(bins, (bool, np.bool_))
-                    and (smooth["smooth_large"] is not None or smooth["smooth_small"] is not None)):
+                    and any(v is not None for v in smooth.values())):
                 if not 2 <= bins <= MAX_BINS:
                     raise ValueError(f"bins as a number must lie in [2, {MAX_BINS}]")
                 plan["bins"], plan["bins_pending"] = None, int(bins)
@@ -322,17 +335,24 @@ class AlignmentPixels:
         return check_edges(es, "edges_small"), check_edges(el, "edges_large")
 
     def _set_images(self, hnd, plan):
-        """Every call starts from the file's pixels: both images up, smoothed where the plan says so (and the pending
-        default bins taken from them), then the solar-rotation shift of the large one."""
+        """Every call starts from the file's pixels: both images up, despiked and then smoothed where the plan says so
+        (and the pending default bins taken from them), then the solar-rotation shift of the large one."""
         hnd.pixels_set_large(self.data_large)
         hnd.pixels_set_small(self.data_small)
+        self.last_despiked = {"small": [], "large": []}
+        if plan["despike_large"] is not None:
+            self.last_despiked["large"] = hnd.pixels_despike_large(plan["despike_large"])
+        if plan["despike_small"] is not None:
+            self.last_despiked["small"] = hnd.pixels_despike_small(plan["despike_small"])
         if plan["smooth_large"] is not None:
             hnd.pixels_smooth_large(plan["smooth_large"])
         if plan["smooth_small"] is not None:
             hnd.pixels_smooth_small(plan["smooth_small"])
         if plan.get("bins_pending") is not None:
-            large = None if plan["smooth_large"] is None else hnd.pixels_get_image("large", self.data_large.shape)
-            small = None if plan["smooth_small"] is None else hnd.pixels_get_image("small", self.data_small.shape)
+            large = (None if plan["smooth_large"] is None and plan["despike_large"] is None
+                     else hnd.pixels_get_image("large", self.data_large.shape))
+            small = (None if plan["smooth_small"] is None and plan["despike_small"] is None
+                     else hnd.pixels_get_image("small", self.data_small.shape))
             plan["bins"] = self._bin_edges(plan["bins_pending"], plan, small, large)
         if plan["shift_large"] is not None:
             dx, dy = plan["shift_large"]
@@ -341,17 +361,19 @@ class AlignmentPixels:
 
     def find_best_parameters(self, lag_dx, lag_dy, lag_drot, unit_rot="degree", shift_solar_rotation_dx_large=False,
                              method="correlation", min_overlap=None, return_type="corr", bins=None, smooth_large=None,
-                             smooth_small=None):
+                             smooth_small=None, despike_large=None, despike_small=None):
         """alignment_pixels.py:57-84: correlation cube [len(lag_dx), len(lag_dy), len(lag_drot)], float64.
         method: "correlation" (best = maximum), "residus_masked" (best = minimum) or "mutual_information" (best =
         maximum; `bins` as `host_plan` takes it).  `self.last_counts`: the samples
         behind every entry, shaped like the cube (before `min_overlap`).  min_overlap: None, a count >= 1 or a fraction
         in (0, 1) of the sweep's largest count; entries of fewer samples become NaN, ValueError when none is left.
-        return_type: "corr" (the cube) or "PixelAlignmentResults".  smooth_large, smooth_small: see the module docstring."""
+        return_type: "corr" (the cube) or "PixelAlignmentResults".  smooth_large, smooth_small, despike_large,
+        despike_small: see the module docstring."""
         if return_type not in _RETURN_TYPES:
             raise ValueError(f"return_type must be one of {_RETURN_TYPES}")
         plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
-                              bins=bins, smooth_large=smooth_large, smooth_small=smooth_small)
+                              bins=bins, smooth_large=smooth_large, smooth_small=smooth_small, despike_large=despike_large,
+                              despike_small=despike_small)
         self.lag_dx, self.lag_dy, self.lag_drot, self.unit_rot = lag_dx, lag_dy, lag_drot, unit_rot
         self.ratio_res_1, self.ratio_res_2 = plan["ratio_res_1"], plan["ratio_res_2"]
         l, (h, w) = plan["slc_small_ref"], self.data_small.shape
@@ -373,7 +395,8 @@ class AlignmentPixels:
 
     def find_local_shifts(self, lag_dx, lag_dy, lag_drot=(0.0,), tile_shape=None, unit_rot="degree",
                           shift_solar_rotation_dx_large=False, method="correlation", min_overlap=None, min_fill=0.5,
-                          sub_lag=True, bins=None, tile_step=None, apodization=None, smooth_large=None, smooth_small=None):
+                          sub_lag=True, bins=None, tile_step=None, apodization=None, smooth_large=None, smooth_small=None,
+                          despike_large=None, despike_small=None):
         """The local shift field: the small image is cut into tiles of `tile_shape` = (rows, columns) pixels (the last
         ones ragged) and every tile gets the lag cube of `find_best_parameters` on its own rectangle -- a rotated plane
         is still rotated about the whole image's centre -- with its sample counts, best entry and sub-lag fit.  Returns a
@@ -390,7 +413,8 @@ class AlignmentPixels:
             raise ValueError("tile_shape = (rows, columns) is needed")
         plan = self.host_plan(lag_dx, lag_dy, lag_drot, unit_rot, shift_solar_rotation_dx_large, method, min_overlap,
                               tile_shape=tile_shape, bins=bins, tile_step=tile_step, apodization=apodization,
-                              smooth_large=smooth_large, smooth_small=smooth_small)
+                              smooth_large=smooth_large, smooth_small=smooth_small, despike_large=despike_large,
+                              despike_small=despike_small)
         hnd = _lib.shared_handle(-1 if self.device is None else self.device)
         self._set_images(hnd, plan)
         corr = hnd.pixels_sweep_tiles(plan, plan["method_code"])

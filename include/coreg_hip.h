@@ -292,6 +292,58 @@ int coreg_smooth_small(coreg_handle* h, const double* wy, int32_t n_wy, const do
 int coreg_set_reference_smoothing(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
 int coreg_get_small(coreg_handle* h, void* out, int dtype);
 
+/* NaN-aware median/MAD despiking of an image on the device: cosmic-ray hits and hot pixels, which a global threshold
+ * either misses (on a dark pixel) or cuts together with bright real structure.  One pass over an image v[H][W] (float32 or
+ * float64), for every pixel (j, i) with isfinite(v[j,i]), with R = radius:
+ *   1. N = the finite pixels of the window [j-R, j+R] x [i-R, i+R], clipped to the image (no mirroring), the centre left
+ *      out, taken as float64; k = |N|.  If k < min_neighbours the pixel is kept.
+ *   2. With s = N sorted ascending, med = s[k/2] for odd k, else (s[k/2 - 1] + s[k/2]) * 0.5; mad is the same selection
+ *      over |n - med|, n in N.
+ *   3. scale = max(1.4826 * mad, floor), d = v[j,i] - med.  The pixel is flagged when scale > 0 and d > nsigma * scale
+ *      (sign = COREG_DESPIKE_BOTH: |d| > nsigma * scale).
+ *   4. A flagged pixel becomes NaN (replace = COREG_DESPIKE_MEDIAN: med, rounded to the dtype the image is held in).
+ * All decisions of a pass are taken on the pass's input, so the result depends on no order.  A non-finite pixel (NaN,
+ * +-Inf) is never a neighbour and is never changed.  The image keeps the dtype it is held in on the device (float64 pixels
+ * that are all float32-exact are held as float32).  n_iter passes run, each on the result of the one before.  The four
+ * float operations (* 0.5, 1.4826 *, -, nsigma *) are each rounded on their own and everything else is selection and
+ * comparison: the result is that of the rule evaluated in IEEE float64 anywhere, bit for bit.  (Zeros of either sign are
+ * one value to the selection; which sign a median of zeros carries is not promised.)
+ * Limits, COREG_EINVAL with a message otherwise, before any GPU work and with everything left as it was: radius 1..3,
+ * n_iter 1..8, nsigma finite and > 0, floor finite and >= 0, min_neighbours 1..(2 radius + 1)^2 - 1, sign and replace one
+ * of their two constants; an image has at least one and at most 2^31 - 1 pixels.
+ * Order in the intake: image to align: thresholds -> despike -> smoothing; reference image: despike -> smoothing ->
+ * resample.
+ *   coreg_despike_small            the resident image to align, in place; its pivot is recomputed as by
+ *                                  coreg_threshold_small.  Call it after the thresholds and before coreg_smooth_small (a
+ *                                  spike smoothed is a spike spread).  n_flagged: NULL, or [n_iter] pixels flagged per
+ *                                  pass.  COREG_ESTATE without an image
+ *   coreg_set_reference_despike    stays until set again; NULL clears it.  While set, every coreg_prepare_reference_*
+ *                                  call despikes the source image's pixels into a buffer of the handle before the
+ *                                  reference smoothing and the once-only resample (host, _f32, _fits, _tiled and
+ *                                  _from_device sources; a device source is not modified).  The crop box of
+ *                                  "crop_reference" is widened by n_iter * radius on top of the smoothing's reach: crop on
+ *                                  or off gives the same bits of the prepared reference
+ *   coreg_last_reference_despike   pixels flagged per pass by the last preparation, n_flagged8: [8] (zero past its n_iter,
+ *                                  all zero when it despiked nothing).  The counts cover the pixels that were processed
+ *                                  (the crop box, when one was used): only the prepared pixels are promised equal */
+#define COREG_DESPIKE_POSITIVE 0
+#define COREG_DESPIKE_BOTH 1
+#define COREG_DESPIKE_NAN 0
+#define COREG_DESPIKE_MEDIAN 1
+typedef struct coreg_despike_params {
+    int32_t radius;         /* R: the window is (2R + 1) x (2R + 1); default of the Python layer: 2 */
+    int32_t n_iter;         /* passes; 2 */
+    int32_t min_neighbours; /* 5 */
+    int32_t sign;           /* COREG_DESPIKE_POSITIVE */
+    int32_t replace;        /* COREG_DESPIKE_NAN */
+    int32_t reserved;
+    double nsigma; /* 5.0 */
+    double floor;  /* 0.0 */
+} coreg_despike_params;
+int coreg_despike_small(coreg_handle* h, const coreg_despike_params* params, int64_t* n_flagged /* [n_iter] or NULL */);
+int coreg_set_reference_despike(coreg_handle* h, const coreg_despike_params* params /* NULL: none */);
+int coreg_last_reference_despike(coreg_handle* h, int64_t* n_flagged8);
+
 /* One resample of the small image through ONE header (= function_to_apply of one lag-point):
  * carrington:      alignment.py:889-901   out float64 [n_lat][n_lon], NaN outside
  * helioprojective: alignment.py:1018-1029 out float32 [hdr_target.naxis2][hdr_target.naxis1] */
@@ -747,6 +799,10 @@ int coreg_pixels_get_large_box(coreg_handle* h, double* out);
 int coreg_pixels_smooth_large(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
 int coreg_pixels_smooth_small(coreg_handle* h, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
 int coreg_pixels_get_image(coreg_handle* h, int which, double* out);
+/* coreg_despike_small's rule on the resident large / small image of the pixel-lag sweep, in place (both are float64);
+ * each forgets the last box, planes and counts.  n_flagged: NULL or [n_iter]. */
+int coreg_pixels_despike_large(coreg_handle* h, const coreg_despike_params* params, int64_t* n_flagged);
+int coreg_pixels_despike_small(coreg_handle* h, const coreg_despike_params* params, int64_t* n_flagged);
 int coreg_pixels_get_rotated(coreg_handle* h, int32_t k, double* out);
 int coreg_pixels_last_timing(coreg_handle* h, double* ms);
 typedef struct coreg_pixels_field {
@@ -817,6 +873,9 @@ int coreg_multi_prepare_reference_helioprojective(coreg_multi* m, const void* la
 /* coreg_smooth_small / coreg_set_reference_smoothing on every device's context */
 int coreg_multi_smooth_small(coreg_multi* m, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
 int coreg_multi_set_reference_smoothing(coreg_multi* m, const double* wy, int32_t n_wy, const double* wx, int32_t n_wx);
+/* coreg_despike_small / coreg_set_reference_despike on every device's context (the counts are the first device's) */
+int coreg_multi_despike_small(coreg_multi* m, const coreg_despike_params* params, int64_t* n_flagged);
+int coreg_multi_set_reference_despike(coreg_multi* m, const coreg_despike_params* params);
 /* coreg_set_reference_rotation / coreg_set_small_rotation on every device's context */
 int coreg_multi_set_reference_rotation(coreg_multi* m, const coreg_diffrot* rot);
 int coreg_multi_set_small_rotation(coreg_multi* m, const coreg_diffrot* rot);
