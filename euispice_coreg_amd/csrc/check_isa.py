@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Build-time check of the hand-issued LDS gathers of k_sweep (kernels.hpp, struct Taps).
 
-The nine (four) `ds_read_b64` of a sample and their `s_waitcnt lgkmcnt(N)` live in two separate inline-asm statements so
-that the spline weights -- and, in the software-pipelined interior loop, the previous sample's arithmetic -- run under
-the LDS latency (N = 9: the next sample's reads stay in flight; LDS operations return in order).  The compiler does not track memory operations inside
-inline asm: were it to place a copy, a spill or any other use of a tap register between the reads and the wait, that
-instruction would see stale data.  This script disassembles the built library and fails if any instruction between a
-group of hand-issued reads and the wait that follows it names one of the group's destination registers.
+The nine (four, sixteen) `ds_read_b64` of a sample are one inline-asm statement; their `s_waitcnt lgkmcnt(0)` stands
+apart from it, so that the spline weights run under the LDS latency.  Since round 12 the wait is the compiler's own
+instruction between two scheduling barriers and no longer an asm statement that names the tap registers (a vector
+instruction that reads a register defined by the asm statement before it costs an `s_nop` on gfx940 and later), so
+nothing in the source ties a tap to its wait any more: this check is what does.  The compiler does not track memory
+operations inside inline asm: were it to place a copy, a spill or any other use of a tap register between the reads and
+the wait, that instruction would see stale data.  This script disassembles the built library and fails if any
+instruction between a group of hand-issued reads and the wait that follows it names one of the group's destination
+registers.  The same holds for the scalar point loads (check_scalar_loads): reading a register of a pending load sees
+stale data, writing one (the allocator handing out a dword no code uses) races with the load.
 
 usage: check_isa.py libcoreg_hip.so   (needs llvm-objdump / clang-offload-bundler from /opt/rocm/lib/llvm/bin)
 """

@@ -35,10 +35,34 @@ struct Acc {
     double a, b, aa, bb, ab;
 };
 
+// Ordering round the hand-issued memory operations of k_sweep (the LDS reads of Taps, the scalar point loads of
+// spt_load).  An inline-asm statement orders the code round it only through the registers it names as outputs, and on
+// gfx940 and later that has a price: a vector instruction that reads a register the statement just before it DEFINES
+// gets an `s_nop 0` in front.  The compiler cannot see into the statement, assumes a vector write whose result is
+// forwarded late (the dst_sel / op_sel forwarding hazard, one wait state) and pads.  A statement that only READS the
+// register costs nothing, and gfx90a has no such rule.  None of these statements holds a vector
+// instruction, so the padding bought nothing, and "+v" / "+s" ties on the waits and the issue points cost two to three
+// scalar-unit slots per sample.  So the statements define only what their instructions write, and the order comes from
+// the compiler's own means: a scheduling barrier that nothing crosses (sched_barrier(0): a boundary for both machine
+// schedulers) after each issue, and the s_waitcnt as the compiler's instruction between two of them.  csrc/check_isa.py
+// holds the built code to the same rule as before: no register of a pending read or load is named before its wait.
+__device__ __forceinline__ void issue_fence() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+__device__ __forceinline__ void wait_lgkm0() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0) alone: vmcnt 63, expcnt 7 (the gfx9 encoding)
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+
 // The N x N float64 taps of one sample, from LDS, as N*N separate ds_read_b64.  hipcc would fuse neighbouring 8-byte
 // reads into ds_read2_b64, which occupies the LDS for 8 cycles against 2 + 2 for two ds_read_b64
-// (MI355X_MICROARCH.md, LDS table), so the reads are issued by hand; wait() / wait_after() are the matching s_waitcnt
-// and tie the values to it so that no use can be scheduled above the wait.
+// (MI355X_MICROARCH.md, LDS table), so the reads are issued by hand; wait() / wait_after() are the matching s_waitcnt,
+// fenced so that no use of a tap can be scheduled above the wait.
 template <int N>
 struct Taps;
 template <>
@@ -53,28 +77,22 @@ struct Taps<3> {
               "=&v"(t[8])
             : "v"(a0), "v"(a1), "v"(a2));
     }
-    // the wait, placed after the x-weights (w0..w2) have been computed; the y-axis has no weights (spline_last_o2)
-    __device__ __forceinline__ void wait_after(double& w0, double& w1, double& w2) {
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
-                       "+v"(t[8]), "+v"(w0), "+v"(w1), "+v"(w2));
-    }
-    // same, and pins (fx, fy) to the issue point: arithmetic that starts from them (the spline weights) is scheduled
-    // AFTER the reads have been issued and overlaps their latency
+    // the wait, placed after the x-weights have been computed; the y-axis has no weights (spline_last_o2)
+    __device__ __forceinline__ void wait_after(double&, double&, double&) { wait_lgkm0(); }
+    // same, with the fence behind the issue point: arithmetic that starts from (fx, fy) (the spline weights) is
+    // scheduled AFTER the reads have been issued and overlaps their latency; the statement reads them, so they are
+    // computed before it
     __device__ __forceinline__ void issue_before(unsigned a0, unsigned a1, unsigned a2, double& fx, double& fy) {
         asm volatile(
             "ds_read_b64 %0, %11\n\tds_read_b64 %1, %11 offset:8\n\tds_read_b64 %2, %11 offset:16\n\t"
             "ds_read_b64 %3, %12\n\tds_read_b64 %4, %12 offset:8\n\tds_read_b64 %5, %12 offset:16\n\t"
             "ds_read_b64 %6, %13\n\tds_read_b64 %7, %13 offset:8\n\tds_read_b64 %8, %13 offset:16"
             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
-              "=&v"(t[8]), "+v"(fx), "+v"(fy)
-            : "v"(a0), "v"(a1), "v"(a2));
+              "=&v"(t[8])
+            : "v"(fx), "v"(fy), "v"(a0), "v"(a1), "v"(a2));
+        issue_fence();
     }
-    __device__ __forceinline__ void wait() {
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
-                       "+v"(t[8]));
-    }
+    __device__ __forceinline__ void wait() { wait_lgkm0(); }
     // compile-time window pitch P (elements): the three rows are immediate offsets of ONE address register, which
     // saves the two row-address additions per sample
     template <int P>
@@ -85,9 +103,10 @@ struct Taps<3> {
             "ds_read_b64 %3, %11 offset:%12\n\tds_read_b64 %4, %11 offset:%13\n\tds_read_b64 %5, %11 offset:%14\n\t"
             "ds_read_b64 %6, %11 offset:%15\n\tds_read_b64 %7, %11 offset:%16\n\tds_read_b64 %8, %11 offset:%17"
             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
-              "=&v"(t[8]), "+v"(fx), "+v"(fy)
-            : "v"(a0), "n"(P * 8), "n"(P * 8 + 8), "n"(P * 8 + 16), "n"(2 * P * 8), "n"(2 * P * 8 + 8),
+              "=&v"(t[8])
+            : "v"(fx), "v"(fy), "v"(a0), "n"(P * 8), "n"(P * 8 + 8), "n"(P * 8 + 16), "n"(2 * P * 8), "n"(2 * P * 8 + 8),
               "n"(2 * P * 8 + 16));
+        issue_fence();
     }
 };
 template <>
@@ -104,16 +123,14 @@ struct Taps<2> {
     __device__ __forceinline__ void issue_before(unsigned a0, unsigned a1, unsigned a2, double&, double&) {
         issue(a0, a1, a2);
     }
-    __device__ __forceinline__ void wait() {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]));
-    }
+    __device__ __forceinline__ void wait() { wait_lgkm0(); }
 };
 
 template <>
 struct Taps<4> {
     double t[16];
-    // the sixteen reads of a cubic sample; (fx, fy) pinned to the issue point so that the weight arithmetic that starts
-    // from them is scheduled after the reads and overlaps their latency
+    // the sixteen reads of a cubic sample; the fence behind them keeps the weight arithmetic that starts from (fx, fy)
+    // after the reads, where it overlaps their latency
     __device__ __forceinline__ void issue_before(unsigned a0, unsigned a1, unsigned a2, unsigned a3, double& fx,
                                                  double& fy) {
         asm volatile(
@@ -127,8 +144,9 @@ struct Taps<4> {
             "ds_read_b64 %15, %21 offset:24"
             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
               "=&v"(t[8]), "=&v"(t[9]), "=&v"(t[10]), "=&v"(t[11]), "=&v"(t[12]), "=&v"(t[13]), "=&v"(t[14]),
-              "=&v"(t[15]), "+v"(fx), "+v"(fy)
-            : "v"(a0), "v"(a1), "v"(a2), "v"(a3));
+              "=&v"(t[15])
+            : "v"(fx), "v"(fy), "v"(a0), "v"(a1), "v"(a2), "v"(a3));
+        issue_fence();
     }
     // compile-time window pitch P: the four rows are immediate offsets of one address register
     template <int P>
@@ -145,18 +163,14 @@ struct Taps<4> {
             "ds_read_b64 %15, %18 offset:%30"
             : "=&v"(t[0]), "=&v"(t[1]), "=&v"(t[2]), "=&v"(t[3]), "=&v"(t[4]), "=&v"(t[5]), "=&v"(t[6]), "=&v"(t[7]),
               "=&v"(t[8]), "=&v"(t[9]), "=&v"(t[10]), "=&v"(t[11]), "=&v"(t[12]), "=&v"(t[13]), "=&v"(t[14]),
-              "=&v"(t[15]), "+v"(fx), "+v"(fy)
-            : "v"(a0), "n"(P * 8), "n"(P * 8 + 8), "n"(P * 8 + 16), "n"(P * 8 + 24), "n"(2 * P * 8), "n"(2 * P * 8 + 8),
-              "n"(2 * P * 8 + 16), "n"(2 * P * 8 + 24), "n"(3 * P * 8), "n"(3 * P * 8 + 8), "n"(3 * P * 8 + 16),
-              "n"(3 * P * 8 + 24));
+              "=&v"(t[15])
+            : "v"(fx), "v"(fy), "v"(a0), "n"(P * 8), "n"(P * 8 + 8), "n"(P * 8 + 16), "n"(P * 8 + 24), "n"(2 * P * 8),
+              "n"(2 * P * 8 + 8), "n"(2 * P * 8 + 16), "n"(2 * P * 8 + 24), "n"(3 * P * 8), "n"(3 * P * 8 + 8),
+              "n"(3 * P * 8 + 16), "n"(3 * P * 8 + 24));
+        issue_fence();
     }
     // the wait, after the x-weights and the two multiples of fy that spline_last_o3 takes have been computed
-    __device__ __forceinline__ void wait_after(double* wx, double& f3, double& f12) {
-        asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]), "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
-                       "+v"(t[8]), "+v"(t[9]), "+v"(t[10]), "+v"(t[11]), "+v"(t[12]), "+v"(t[13]), "+v"(t[14]),
-                       "+v"(t[15]), "+v"(wx[0]), "+v"(wx[1]), "+v"(wx[2]), "+v"(wx[3]), "+v"(f3), "+v"(f12));
-    }
+    __device__ __forceinline__ void wait_after(double*, double&, double&) { wait_lgkm0(); }
 };
 
 // Cubic B-spline sample (reprojection_order = 3, alignment.py:54) from the LDS window at the window-relative coordinate
@@ -472,16 +486,20 @@ __device__ __forceinline__ void point_lag(Acc& acc, unsigned win, const TS* __re
 #endif
 // COREG_PT_SCALAR == 2: explicit s_load_dwordx8 of a whole Pt, issued a point ahead (tile_points)
 typedef unsigned SPt __attribute__((ext_vector_type(8)));
-// `anchor`: a per-lane value the point's FIRST vector instruction reads; naming it as an in/out operand keeps the load
-// above that instruction (the scheduler would otherwise sink it below the coordinate arithmetic and shorten the time
-// the load has before the gather's wait)
+// `anchor`: a per-lane value the point's FIRST vector instruction reads; the statement reads it and a fence follows,
+// which keeps the load above that instruction (the scheduler would otherwise sink it below the coordinate arithmetic
+// and shorten the time the load has before the gather's wait)
+// OFF: byte offset from `p`, the instruction's immediate (a chunk's prefetches all name the group's one running pointer)
+template <int OFF = 0>
 __device__ __forceinline__ SPt spt_load(const Pt* __restrict__ p, double& anchor) {
+    static_assert(OFF >= 0 && OFF < (1 << 20), "the immediate offset of a scalar load has 21 signed bits");
     SPt r;
 #if defined(__HIP_DEVICE_COMPILE__)
 #if COREG_PT_ANCHOR
-    asm volatile("s_load_dwordx8 %0, %2, 0x0" : "=s"(r), "+v"(anchor) : "s"(p));
+    asm volatile("s_load_dwordx8 %0, %2, %3" : "=s"(r) : "v"(anchor), "s"(p), "n"(OFF));
+    issue_fence();
 #else
-    asm volatile("s_load_dwordx8 %0, %1, 0x0" : "=s"(r) : "s"(p));
+    asm volatile("s_load_dwordx8 %0, %1, %2" : "=s"(r) : "s"(p), "n"(OFF));
 #endif
 #else
     r = (SPt)(0u);
@@ -490,10 +508,28 @@ __device__ __forceinline__ SPt spt_load(const Pt* __restrict__ p, double& anchor
 #endif
     return r;
 }
+// The point of the code from which a prefetched point may be used.  DRAINED: an s_waitcnt lgkmcnt(0) that every wave
+// executes lies between the load and here (the wait that ends an unconditional gather: SMEM and LDS share the
+// counter), so no instruction is issued and only the fence stands: no use of the registers is scheduled above it.
+// The empty statement READS all eight registers: they stay allocated to the load until it has landed (a dword no code
+// uses, a pad, would otherwise be handed out as a temporary while the load is still in flight).
+template <bool DRAINED = false>
 __device__ __forceinline__ void spt_wait(SPt& r) {
+    if constexpr (DRAINED) issue_fence();
+    else wait_lgkm0();
 #if defined(__HIP_DEVICE_COMPILE__)
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(r));
+    asm volatile("" : : "s"(r));
 #endif
+}
+// The prefetch issued under point k of the chunk at q: point k + 1 of that chunk, or the first point of the group's next
+// one (k is a constant once the chunk's loop is unrolled).
+__device__ __forceinline__ SPt spt_load_next(const Pt* __restrict__ q, int k, double& anchor) {
+    static_assert(kChunk == 4 && sizeof(Pt) == sizeof(SPt), "one case per point of a chunk, one s_load_dwordx8 per point");
+    constexpr int kPtBytes = (int)sizeof(Pt);
+    if (k == 0) return spt_load<kPtBytes>(q, anchor);
+    if (k == 1) return spt_load<2 * kPtBytes>(q, anchor);
+    if (k == 2) return spt_load<3 * kPtBytes>(q, anchor);
+    return spt_load<kPointGroups * kChunk * kPtBytes>(q, anchor);
 }
 __device__ __forceinline__ double spt_f64(const SPt& r, int i) {
     const unsigned long long u = ((unsigned long long)r[2 * i + 1] << 32) | (unsigned long long)r[2 * i];
@@ -633,15 +669,15 @@ __device__ __forceinline__ void tile_points(Acc& acc, unsigned win, const TS* __
             int c = p_begin / kChunk + pg;
             if (c < n_full) {
                 double& anchor = hv.h[7];
-                SPt cur = spt_load(pts + c * kChunk, anchor);
+                const Pt* __restrict__ q = pts + c * kChunk;  // (the group's running pointer, as in the loop below)
+                SPt cur = spt_load(q, anchor);
                 spt_wait(cur);
-                for (; c < n_full; c += kPointGroups) {
-                    const Pt* __restrict__ q = pts + c * kChunk;
+                for (; c < n_full; c += kPointGroups, q += kPointGroups * kChunk) {
                     const bool run = cur[7] != 0u;  // (pad of the chunk's first point = 1.0 / 0.0: uniform, SGPR test)
                     double xn = 0.0, yn = 0.0, ww = 0.0;  // ww: eps (series) or w
 #pragma unroll
                     for (int k = 0; k < kChunk; ++k) {
-                        SPt nxt = spt_load(k + 1 < kChunk ? q + k + 1 : q + kPointGroups * kChunk, anchor);
+                        SPt nxt = spt_load_next(q, k, anchor);
                         const double x = spt_f64(cur, 0), y = spt_f64(cur, 1);
                         if (k == 0 || !run) {
                             xn = fma(hv.h[0], x, fma(hv.h[1], y, hv.h[2]));
@@ -672,7 +708,7 @@ __device__ __forceinline__ void tile_points(Acc& acc, unsigned win, const TS* __
                             if (k == 2) acc.aa += spt_f64(cur, 3);
                             if (k == kChunk - 1) acc.n += kChunk;
                         }
-                        spt_wait(nxt);
+                        spt_wait<true>(nxt);  // (kIncr: an interior LDS visit, the gather's wait has drained it)
                         cur = nxt;
                     }
                 }
@@ -699,15 +735,18 @@ __device__ __forceinline__ void tile_points(Acc& acc, unsigned win, const TS* __
             // (lane value read first by the point's arithmetic: the window-relative origin / the projective row)
             H9 hml = hm;
             double& anchor = MODE == MODE_TRANSLATE ? (INTERIOR && LDS ? pxw : px0) : hml.h[MODE == MODE_CAR ? 0 : 7];
-            SPt cur = spt_load(pts + c * kChunk, anchor);
+            // (one running pointer per point-group, advanced once per chunk; the chunk's four prefetches name it with
+            // immediate offsets, where an address rebuilt from the chunk index took three scalar instructions per chunk
+            // and two more per prefetch)
+            const Pt* __restrict__ q = pts + c * kChunk;
+            SPt cur = spt_load(q, anchor);
             spt_wait(cur);
-            for (; c < n_full; c += kPointGroups) {
-                const Pt* __restrict__ q = pts + c * kChunk;
+            for (; c < n_full; c += kPointGroups, q += kPointGroups * kChunk) {
 #pragma unroll
                 for (int k = 0; k < kChunk; ++k) {
                     // (past the group's last chunk this reads up to kPointGroups chunks ahead: inside the allocation
                     // -- DevBuf::reserve pads by 25 % + 256 B -- and never used)
-                    SPt nxt = spt_load(k + 1 < kChunk ? q + k + 1 : q + kPointGroups * kChunk, anchor);
+                    SPt nxt = spt_load_next(q, k, anchor);
                     point_lag<MODE, ORDER, TS, LDS, ROUND, RESID, INTERIOR, PITCH, CLEAN>(
                         acc, win, img, pitch, ox, oy, W, H, wmax, hmax, px0, py0, pxw, pyw, hml, cu, spt_f64(cur, 0),
                         spt_f64(cur, 1), spt_f64(cur, 2), spt_f64(cur, 3), pivot_b);
@@ -717,7 +756,9 @@ __device__ __forceinline__ void tile_points(Acc& acc, unsigned win, const TS* __
                         if (k == 2) acc.aa += spt_f64(cur, 3);
                         if (k == kChunk - 1) acc.n += kChunk;
                     }
-                    spt_wait(nxt);  // (already drained by the gather's wait unless no lane sampled)
+                    // (an interior LDS visit gathers unconditionally and its wait has drained the prefetch; elsewhere a
+                    // wave none of whose lanes sampled has met no wait yet)
+                    spt_wait<INTERIOR && LDS>(nxt);
                     cur = nxt;
                 }
             }
