@@ -278,6 +278,9 @@ SYMBOLS = [
     ("coreg_despike_small", C.c_int, [_P, C.POINTER(DespikeParams), C.POINTER(C.c_int64)]),
     ("coreg_set_reference_despike", C.c_int, [_P, C.POINTER(DespikeParams)]),
     ("coreg_last_reference_despike", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("coreg_despike_sum_planes_be", C.c_int,
+     [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(DespikeParams), _P, _P, _P]),
+    ("coreg_despike_sum_planes_last_ms", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("coreg_resample_carrington", C.c_int, [_P, _WP, C.POINTER(CarrGrid), C.c_double, C.c_int, _P]),
     ("coreg_resample_helioprojective", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
     ("coreg_resample_helioprojective_f64", C.c_int, [_P, _WP, _WP, C.c_int, _P]),
@@ -377,6 +380,8 @@ SYMBOLS = [
     ("coreg_multi_set_reference_smoothing", C.c_int, [_P, _P, C.c_int32, _P, C.c_int32]),
     ("coreg_multi_despike_small", C.c_int, [_P, C.POINTER(DespikeParams), C.POINTER(C.c_int64)]),
     ("coreg_multi_set_reference_despike", C.c_int, [_P, C.POINTER(DespikeParams)]),
+    ("coreg_multi_despike_sum_planes_be", C.c_int,
+     [_P, _P, C.c_int32, C.c_int64, C.c_int32, C.c_int32, _P, C.c_int32, C.POINTER(DespikeParams), _P, _P, _P]),
     ("coreg_multi_set_reference_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_multi_set_small_rotation", C.c_int, [_P, C.POINTER(DiffRot)]),
     ("coreg_multi_sweep_carrington", C.c_int,
@@ -606,6 +611,42 @@ class _ImageIntake:
         resample (coreg_set_reference_despike); None for none (the default).  It stays until set again."""
         fn = getattr(self._lib, self._prefix + "set_reference_despike")
         self._chk(fn(getattr(self, self._ptr), None if params is None else C.byref(DespikeParams.of(params))))
+
+    def despike_sum_planes(self, planes, plane_index, params, rows=None):
+        """The planes `plane_index` of a cube [n_planes, ny, nx], each despiked on its own by `params` (a dict as for
+        `despike_small`), then summed over the planes in float64, NaN as zero (coreg_despike_sum_planes_be; a MultiHandle
+        runs it on its first device).  `rows` = (first, past the last): the rows processed -- rows outside are never
+        neighbours -- and the rows of the result; None: all.  `planes` may be a (data, header) pair.  A big-endian
+        C-contiguous float32 / float64 cube (a view of a FITS data unit) goes to the library as it is, which reads the
+        selected planes and rows alone; of anything else (native arrays, integer cubes) the selection is copied to ">f4"
+        (floats of at most four bytes) or ">f8" first.  Returns (sum float64 [rows, nx], flag events per pixel int32
+        [rows, nx], flag events per pass as a list).  Nothing resident on the handle is read or changed."""
+        if isinstance(planes, tuple):
+            planes = planes[0]
+        a = np.asarray(planes)
+        if a.ndim != 3:
+            raise ValueError("despike_sum_planes: the planes must be a 3-D array [n_planes, ny, nx]")
+        idx = np.ascontiguousarray(plane_index, dtype=np.int64).ravel()
+        if idx.size and (idx.min() < 0 or idx.max() >= a.shape[0]):
+            raise IndexError("plane index out of range")
+        ny, nx = a.shape[1:]
+        r0, r1 = (0, ny) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= r0 <= r1 <= ny:
+            raise ValueError(f"despike_sum_planes: rows {rows!r} outside the {ny} rows of a plane")
+        as_stored = a.dtype.kind == "f" and a.dtype.byteorder == ">" and a.dtype.itemsize in (4, 8) and a.flags.c_contiguous
+        if not as_stored and idx.size:
+            small = a.dtype.kind == "f" and a.dtype.itemsize <= 4
+            a = np.ascontiguousarray(a[idx, r0:r1], dtype=">f4" if small else ">f8")  # (the selection alone)
+            idx, ny, r0, r1 = np.arange(idx.size, dtype=np.int64), r1 - r0, 0, r1 - r0
+        itemsize = a.dtype.itemsize if a.dtype.kind == "f" and a.dtype.itemsize in (4, 8) else 8
+        p = DespikeParams.of(params)
+        out = np.empty((r1 - r0, nx), dtype=np.float64)
+        events = np.empty((r1 - r0, nx), dtype=np.int32)
+        counts = (C.c_int64 * 8)()
+        fn = getattr(self._lib, self._prefix + "despike_sum_planes_be")
+        self._chk(fn(getattr(self, self._ptr), a.ctypes.data + r0 * nx * itemsize, -8 * itemsize, ny * nx, r1 - r0, nx,
+                     idx.ctypes.data, idx.size, C.byref(p), out.ctypes.data, events.ctypes.data, counts))
+        return out, events, [int(v) for v in counts[:max(0, min(8, p.n_iter))]]
 
     def prepare_reference_carrington(self, large, hdr_large, grid: Grid, solar_r, order=2):
         w = wcs_from_header(hdr_large, carrington=True)
@@ -998,6 +1039,12 @@ class CoregHandle(_ImageIntake):
             self._h, cube.ctypes.data, COREG_F32 if cube.dtype == np.float32 else COREG_F64, cube.shape[0], cube.shape[1],
             cube.shape[2], C.byref(f), out.ctypes.data, None if disp is None else disp.ctypes.data))
         return (out, disp) if return_displacement else out
+
+    def despike_sum_planes_last_ms(self) -> float:
+        """coreg_despike_sum_planes_last_ms: the GPU time of the kernels of the last `despike_sum_planes` [ms]."""
+        ms = C.c_double(0.0)
+        self._chk(self._lib.coreg_despike_sum_planes_last_ms(self._h, C.byref(ms)))
+        return float(ms.value)
 
     def pixels_destretch_last_ms(self) -> float:
         ms = C.c_double(0.0)

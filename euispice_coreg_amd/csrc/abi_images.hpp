@@ -598,6 +598,22 @@ int coreg_last_reference_despike(coreg_handle* h, int64_t* n_flagged8) {
     return despike_read_counts(h, DESPIKE_SLOT_REFERENCE, h->ref_despike_passes, n_flagged8);
 }
 
+// The planes of a cube despiked one by one and summed over the planes.  It needs no resident image and touches none: the
+// work runs in buffers of its own (host_despike_planes.hpp).
+int coreg_despike_sum_planes_be(coreg_handle* h, const void* base, int32_t bitpix, int64_t plane_stride, int32_t H, int32_t W,
+                                const int64_t* plane_index, int32_t n_sel, const coreg_despike_params* params,
+                                double* out_sum, int32_t* out_events, int64_t* n_flagged) {
+    if (!h) return COREG_EINVAL;
+    return despike_sum_planes(h, base, bitpix, plane_stride, H, W, plane_index, n_sel, params, out_sum, out_events, n_flagged);
+}
+
+int coreg_despike_sum_planes_last_ms(coreg_handle* h, double* ms) {
+    if (!h || !ms) return COREG_EINVAL;
+    if (h->dp_last_ms < 0) return fail(h, COREG_ESTATE, "coreg_despike_sum_planes_be has not run");
+    *ms = h->dp_last_ms;
+    return COREG_OK;
+}
+
 int coreg_get_small(coreg_handle* h, void* out, int dtype) {
     if (!h) return COREG_EINVAL;
     if (!h->small.p) return fail(h, COREG_ESTATE, "coreg_set_small has not been called");

@@ -39,6 +39,7 @@ using namespace coreg;
 #include "host_upload.hpp"       // uploads, FITS decode, reference crop
 #include "host_smooth.hpp"       // NaN-aware separable smoothing of a resident image: plan + two launches
 #include "host_despike.hpp"      // median/MAD despiking of a resident image: plan + one launch per pass
+#include "host_despike_planes.hpp" // ... of a stack of planes, fused with their sum: plan, upload, launches, read-back
 #include "host_plan.hpp"         // lag checks, the planners' view of the handle, tile groups, precompute
 #include "host_fix_launch.hpp"   // re-evaluation work space, k_finalize, fix kernels of a launch
 #include "sweep_variant.hpp"     // the list of k_sweep instantiations and the rule that picks one (no HIP in it)
@@ -201,6 +202,8 @@ int coreg_set_option(coreg_handle* h, const char* name, int64_t value) {
     } else if (n == "mi_chunks") {
         if (value < 0 || value > kMiMaxChunks) return fail(h, COREG_EINVAL, "mi_chunks must be in [0, 64]");
         h->opt_mi_chunks = value;
+    } else if (n == "despike_planes_overlap") {
+        h->opt_despike_planes_overlap = value ? 1 : 0;  // 0: coreg_despike_sum_planes_be's last pass without its second LDS window
     } else if (n == "lds_bytes") {
         // 160 KiB per CU minus the kernel's static LDS
         if (value < 1024 || value > 159 * 1024) return fail(h, COREG_EINVAL, "lds_bytes must be in [1 KiB, 159 KiB]");

@@ -109,6 +109,16 @@ struct coreg_handle {
     coreg_despike_params ref_despike = {};
     bool has_ref_despike = false;
     int ref_despike_passes = 0;
+    // despiking and summing a stack of planes (host_despike_planes.hpp): buffers of its own, so that a call leaves the
+    // resident images and the reference despiking as they were -- the page-locked staging of the selected planes, the
+    // stack as the file stores it, the two stacks its passes before the last write in turn, the sum, the event map and
+    // the flag events per pass uint64 [8], the time of the last call's kernels; "despike_planes_overlap" 0: the last pass
+    // stages every plane before it decides it (what the overlap is timed against)
+    PinBuf dp_pin;
+    DevBuf dp_raw, dp_a, dp_b, dp_sum, dp_events, dp_counts;
+    Event dp_ev[2];          // around the passes of a call (created by the first one)
+    double dp_last_ms = -1;  // the passes of the last call by those events, upload and read-back left out; < 0: no call yet
+    int64_t opt_despike_planes_overlap = 1;
     CarrTables tabs;
     std::vector<double> tabs_key;
     bool tabs_uploaded = false;  // the device tables are those of `tabs`

@@ -1027,6 +1027,16 @@ int coreg_multi_set_reference_despike(coreg_multi* m, const coreg_despike_params
     if (!m) return COREG_EINVAL;
     return multi_run(m, [&](int k) { return coreg_set_reference_despike(m->h[k], params); });
 }
+// (no device keeps anything of it: the first device does the work)
+int coreg_multi_despike_sum_planes_be(coreg_multi* m, const void* base, int32_t bitpix, int64_t plane_stride, int32_t H,
+                                      int32_t W, const int64_t* plane_index, int32_t n_sel, const coreg_despike_params* params,
+                                      double* out_sum, int32_t* out_events, int64_t* n_flagged) {
+    if (!m) return COREG_EINVAL;
+    return multi_on(m, 0, [&](coreg_handle* h) {
+        return coreg_despike_sum_planes_be(h, base, bitpix, plane_stride, H, W, plane_index, n_sel, params, out_sum, out_events,
+                                           n_flagged);
+    });
+}
 
 int coreg_multi_set_reference_on_grid(coreg_multi* m, const void* ref, int dtype, int32_t gy, int32_t gx) {
     if (!m) return COREG_EINVAL;

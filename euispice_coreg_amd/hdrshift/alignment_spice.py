@@ -9,6 +9,14 @@ Differences from the reference, all deliberate:
     branch follows the sign of CRVAL1, against the user's limits);
   * the sunpy branch (alignment_spice.py:300-303) is not implemented;
   * inputs may be FITS paths or (data, header) pairs (then pass `level=`).
+
+Beyond the reference: `despike_planes=` (level 2 only; `utils.despiking.despike_planes_params`: True, a number of sigmas or
+a dict).  A cosmic-ray hit lands in one wavelength plane, and in the sum over the planes its contrast is diluted by the
+noise of all the others, where `despike_small=` -- which sees the summed image -- cannot find it.  With the keyword every
+selected plane is despiked on its own on the GPU, between the slit edges only (rows outside are never neighbours), and the
+planes are summed there (include/coreg_hip.h: coreg_despike_sum_planes_be); everything after the sum is unchanged.
+`last_despiked_planes` holds the flag events per pass, `despiked_plane_events` their int32 map on the 2-D image's grid
+(zero in rows that were not processed).  Without the keyword the host sum runs, bit for bit as before.
 """
 from __future__ import annotations
 
@@ -18,11 +26,27 @@ import numpy as np
 
 from .. import _lib
 from ..utils import fits_io, header as hdrutil, spice_header, wcs_tan
+from ..utils.despiking import despike_planes_params
 from .alignment import Alignment, apply_min_overlap, library_method, parse_bins
 
 
 def _angstrom(v):
     return float(v.to("angstrom").value) if hasattr(v, "to") else float(v)
+
+
+def despiked_plane_sum(planes, sel, rule, rows, device=None, slot=0):
+    """The planes `sel` of `planes` [n_planes, ny, nx] despiked one by one by `rule` over the rows [rows[0], rows[1]) and
+    summed over the planes on the GPU (`CoregHandle.despike_sum_planes`): (image float64 [ny, nx], NaN outside the rows;
+    flag events per pixel int32 [ny, nx], zero outside the rows; flag events per pass)."""
+    ny, nx = planes.shape[1:]
+    r0, r1 = rows
+    image = np.full((ny, nx), np.nan, dtype=np.float64)
+    events = np.zeros((ny, nx), dtype=np.int32)
+    counts = [0] * int(rule["n_iter"])
+    if r1 > r0:
+        h = _lib.shared_handle(-1 if device is None else device, slot)
+        image[r0:r1], events[r0:r1], counts = h.despike_sum_planes(planes, sel, rule, rows=(r0, r1))
+    return image, events, counts
 
 
 class AlignmentSpice(Alignment):
@@ -32,7 +56,8 @@ class AlignmentSpice(Alignment):
                  small_fov_window=-1, parallelism=False, counts_cpu_max=40, display_progress_bar=False,
                  path_save_figure=None, wavelength_interval_to_sum="all", sub_fov_window="all", level=None,
                  cdelt_semantics="intended", device=None, differential_rotation="reference", min_overlap=None,
-                 smooth_small=None, smooth_large=None, smooth_unit="pixel", despike_small=None, despike_large=None):
+                 smooth_small=None, smooth_large=None, smooth_unit="pixel", despike_small=None, despike_large=None,
+                 despike_planes=None):
         super().__init__(large_fov_known_pointing=large_fov_known_pointing, small_fov_to_correct=small_fov_to_correct,
                          lag_crval1=lag_crval1, lag_crval2=lag_crval2, lag_cdelt1=lag_cdelt1, lag_cdelt2=lag_cdelt2,
                          lag_crota=lag_crota, display_progress_bar=display_progress_bar, lag_solar_r=lag_solar_r,
@@ -46,6 +71,9 @@ class AlignmentSpice(Alignment):
         self.cut_from_center = None
         self.wavelength_interval_to_sum = wavelength_interval_to_sum
         self.level = level
+        self.despike_planes = despike_planes_params(despike_planes, "despike_planes")
+        self.last_despiked_planes = None   # flag events per pass of the last level-2 preparation with `despike_planes`
+        self.despiked_plane_events = None  # ... per pixel of the 2-D image, int32
 
     # ------------------------------------------------------------------------------------------------------------
     def _level(self):
@@ -121,6 +149,8 @@ class AlignmentSpice(Alignment):
         if level == 2:
             self._prepare_spice_from_l2(cube, hdr)
         elif level == 3:
+            if self.despike_planes is not None:
+                raise ValueError("despike_planes: a level-3 map has no wavelength planes to despike (level 2 only)")
             self._prepare_spice_from_l3(cube, hdr, coeff)
         else:
             raise ValueError("level must be 2 or 3")
@@ -171,7 +201,15 @@ class AlignmentSpice(Alignment):
                              "or 'all' str ")
         # big-endian float planes straight from the memory-mapped data unit: the library's threaded host routine (same
         # additions in the same order); anything else (native arrays handed over in memory, integer cubes): NumPy
-        self.data_small = _lib.nansum_planes_be(cube[0], sel)
+        self.last_despiked_planes = self.despiked_plane_events = None
+        if self.despike_planes is not None:
+            # every selected plane despiked on its own between the slit edges, then the same sum, on the GPU; what follows
+            # sets the rows outside [ymin, ymax) to NaN again
+            r0, r1, _ = slice(ymin, ymax).indices(cube.shape[2])
+            self.data_small, self.despiked_plane_events, self.last_despiked_planes = despiked_plane_sum(
+                cube[0], sel, self.despike_planes, (r0, max(r0, r1)), self.device, self._handle_slot)
+        else:
+            self.data_small = _lib.nansum_planes_be(cube[0], sel)
         if self.data_small is None:
             self.data_small = np.zeros(cube.shape[2:], dtype=np.float64) if len(sel) == 0 else None
             for plane in cube[0][sel]:
@@ -245,13 +283,14 @@ class AlignementSpiceIterativeContextRaster(AlignmentSpice):
     def __init__(self, large_fov_list_paths, small_fov_to_correct, threshold_time, lag_crval1, lag_crval2, lag_cdelt1,
                  lag_cdelt2, lag_crota, small_fov_value_min=None, parallelism=False, small_fov_value_max=None,
                  counts_cpu_max=40, large_fov_window=-1, small_fov_window=-1, use_tqdm=False, path_save_figure=None,
-                 cdelt_semantics="intended", device=None, min_overlap=None):
+                 cdelt_semantics="intended", device=None, min_overlap=None, despike_planes=None):
         super().__init__(large_fov_known_pointing="No_specific_path", small_fov_to_correct=small_fov_to_correct,
                          lag_crval1=lag_crval1, lag_crval2=lag_crval2, lag_cdelt1=lag_cdelt1, lag_cdelt2=lag_cdelt2,
                          lag_crota=lag_crota, lag_solar_r=None, parallelism=parallelism, counts_cpu_max=counts_cpu_max,
                          large_fov_window=large_fov_window, small_fov_window=small_fov_window,
                          display_progress_bar=use_tqdm, path_save_figure=path_save_figure,
-                         cdelt_semantics=cdelt_semantics, device=device, min_overlap=min_overlap)
+                         cdelt_semantics=cdelt_semantics, device=device, min_overlap=min_overlap,
+                         despike_planes=despike_planes)
         self.small_fov_value_min = small_fov_value_min
         self.small_fov_value_max = small_fov_value_max
         self.step_figure = False
@@ -308,6 +347,8 @@ class AlignementSpiceIterativeContextRaster(AlignmentSpice):
         self.coordinate_frame = "final_helioprojective"
         self.extend_pixel_size = extend_pixel_size
         level = self._level()
+        if level == 3 and self.despike_planes is not None:
+            raise ValueError("despike_planes: a level-3 map has no wavelength planes to despike (level 2 only)")
         if level == 3:
             raise NotImplementedError("AlignementSpiceIterativeContextRaster: level-3 input (the reference's L3 path "
                                       "never sets the unflattened header it composes the context from)")

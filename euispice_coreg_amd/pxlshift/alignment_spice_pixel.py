@@ -5,19 +5,27 @@ slit edges, with a 2-D header in degrees whose CDELT1 is shortened by the appare
 step; the sweep is `AlignmentPixels.find_best_parameters`.  Level-3 input raises NotImplementedError.
 
 Beyond the reference: `row_offset`, the first row of the L2 window that the small image holds, and
-`write_destretched_fits`, the L2 file with the planes of the chosen windows resampled by a `LocalShiftField`.
+`write_destretched_fits`, the L2 file with the planes of the chosen windows resampled by a `LocalShiftField`; and
+`despike_planes=` (`utils.despiking.despike_planes_params`): every wavelength plane is despiked on its own on the GPU over
+the rows [ylim, ylen - ylim) and the planes are summed there (include/coreg_hip.h: coreg_despike_sum_planes_be) in place of
+the host nansum; `last_despiked_planes` holds the flag events per pass, `despiked_plane_events` their int32 map on the small
+image's grid.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from ..utils import fits_io, header as hdrutil, spice_header
+from ..utils.despiking import despike_planes_params
 from .alignment_pixels import AlignmentPixels, large_fov_centre, set_pixels_shift_cards
 
 
 class AlignmentSpicePixel(AlignmentPixels):
 
-    def __init__(self, fsi_path, fsi_window, spice_path, spice_window, index_amplitude=None, device=None):
+    def __init__(self, fsi_path, fsi_window, spice_path, spice_window, index_amplitude=None, device=None,
+                 despike_planes=None):
+        self.despike_planes = despike_planes_params(despike_planes, "despike_planes")
+        self.last_despiked_planes = self.despiked_plane_events = None
         self.fsi_path, self.spice_path = fsi_path, spice_path
         self.fsi_window, self.spice_window = fsi_window, spice_window
         name = spice_path if isinstance(spice_path, str) else ""
@@ -75,7 +83,14 @@ class AlignmentSpicePixel(AlignmentPixels):
         ylim = max(ymin, ylen - ymax - 1)
         self.row_offset = int(ylim)  # row 0 of the small image is row `row_offset` of the window
         # (a reduction over the outer axis adds the planes one after another, as the reference's nansum does)
-        self.data_small = np.nansum(np.asarray(cube[0][:, ylim:(ylen - ylim), :], dtype=np.float64), axis=0)
+        if self.despike_planes is not None:
+            from ..hdrshift.alignment_spice import despiked_plane_sum
+            r0, r1, _ = slice(ylim, ylen - ylim).indices(ylen)
+            image, events, self.last_despiked_planes = despiked_plane_sum(
+                cube[0], np.arange(cube.shape[1]), self.despike_planes, (r0, max(r0, r1)), self.device)
+            self.data_small, self.despiked_plane_events = image[r0:max(r0, r1)], events[r0:max(r0, r1)]
+        else:
+            self.data_small = np.nansum(np.asarray(cube[0][:, ylim:(ylen - ylim), :], dtype=np.float64), axis=0)
         self.hdr_small["CRPIX1"] = (self.data_small.shape[1] + 1) / 2
         self.hdr_small["CRPIX2"] = (self.data_small.shape[0] + 1) / 2
         self.hdr_small["NAXIS1"] = self.data_small.shape[1]

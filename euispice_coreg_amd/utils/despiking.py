@@ -63,6 +63,20 @@ def despike_params(arg, what="despike"):
     return p
 
 
+def despike_planes_params(arg, what="despike_planes"):
+    """The parameters of a `despike_planes=` keyword (the wavelength planes of a SPICE window despiked one by one before
+    they are summed; include/coreg_hip.h: coreg_despike_sum_planes_be): as `despike_params`, except that True and a bare
+    number of sigmas stand for replace="median", not "nan".  A plane pixel set to NaN is a zero term of the sum over the
+    planes: where the other planes hold the line, the summed image gets a dip of one plane's worth where the line was, which
+    no later step can tell from structure.  The median of the pixel's neighbours in its own plane keeps the term.  A dict
+    says what it wants: without a "replace" key it gets `despike_params`' default, "nan"."""
+    if arg is True:
+        arg = {"replace": "median"}
+    elif _is_number(arg):
+        arg = {"nsigma": arg, "replace": "median"}
+    return despike_params(arg, what)
+
+
 def despike_tag(p):
     """The parameters as a flat tuple (what names them in the tag of a resident prepared reference); () for None."""
     return () if p is None else ("despike",) + tuple(p[k] for k in sorted(p))

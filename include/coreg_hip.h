@@ -344,6 +344,39 @@ int coreg_despike_small(coreg_handle* h, const coreg_despike_params* params, int
 int coreg_set_reference_despike(coreg_handle* h, const coreg_despike_params* params /* NULL: none */);
 int coreg_last_reference_despike(coreg_handle* h, int64_t* n_flagged8);
 
+/* The planes of a cube despiked one by one, then summed over the planes: a cosmic-ray hit lands in one wavelength plane of a
+ * spectrometer window, and in the sum over the planes its contrast is diluted by the noise of every other plane.
+ * Input: n_sel planes [H][W] of big-endian float32 (bitpix -32) or float64 (-64), as a FITS data unit stores them.  Plane k
+ * starts at element plane_index[k] * plane_stride from `base`; the caller points `base` at the first row it wants (this is
+ * how a row range of a [wavelength, y, x] cube is addressed: plane_stride = ny * nx, H = the rows of the range).  The planes
+ * are taken in the order given; duplicates and any order are allowed.  Only the selected planes, and of them the H rows, go
+ * to the device; the byte swap is the kernel's load.
+ * Despiking: every plane on its own by the rule above -- params->n_iter passes, each taking all its decisions on its own
+ * input; the window is spatial, (2R + 1)^2 inside the plane and clipped at the plane's edges (at the first and last row of
+ * the range: rows outside it are never neighbours), no window crosses planes; non-finite pixels are never neighbours and
+ * never change; a flagged pixel becomes NaN or the median rounded to the planes' dtype.
+ * Sum: out_sum[j,i] is a float64 accumulation over k = 0 .. n_sel - 1 in that order, started at +0.0; the term is +0.0
+ * where the despiked pixel is NaN and (double)v otherwise, so +-Inf pass through (as np.nansum); no reassociation, no
+ * contraction: the result equals np.nansum(float64(despiked stack), axis=0), NaN where +Inf meets -Inf.  The sign of a
+ * zero is not promised.
+ * out_events[j,i] (or NULL): flag events at the pixel over all passes and all selected planes; n_flagged[p] (or NULL), p <
+ * n_iter: flag events of pass p; the events sum to the counts.
+ * The call uploads, runs on the handle's stream, reads back and waits; its buffers belong to the handle and are reused.  It
+ * needs no resident image and leaves the resident images and the reference despiking as they were.  n_sel = 0: an all +0.0
+ * sum, no events, zero counts, nothing launched.  COREG_EINVAL with a message, before any GPU work and with the outputs
+ * untouched: the limits of the rule above; bitpix other than -32 / -64; H or W < 1 or H * W > 2^31 - 1; plane_stride <
+ * H * W; n_sel < 0 or > 4096; a negative plane index; base, out_sum or (n_sel > 0) plane_index NULL.
+ * Not done here: windows that reach across wavelength, writing a despiked cube. */
+int coreg_despike_sum_planes_be(coreg_handle* h, const void* base, int32_t bitpix, int64_t plane_stride, int32_t H, int32_t W,
+                                const int64_t* plane_index, int32_t n_sel, const coreg_despike_params* params,
+                                double* out_sum /* [H][W] */, int32_t* out_events /* [H][W] or NULL */,
+                                int64_t* n_flagged /* [n_iter] or NULL */);
+/* the GPU time of the kernels of the handle's last coreg_despike_sum_planes_be call [ms], upload and read-back left out (0
+ * for a call without a plane); COREG_ESTATE before the first call.  Handle option "despike_planes_overlap" (default 1): 0 makes
+ * the last pass stage every plane before it decides it, without its second window in LDS -- the same bits; kept so that what
+ * the overlap buys can be timed */
+int coreg_despike_sum_planes_last_ms(coreg_handle* h, double* ms);
+
 /* One resample of the small image through ONE header (= function_to_apply of one lag-point):
  * carrington:      alignment.py:889-901   out float64 [n_lat][n_lon], NaN outside
  * helioprojective: alignment.py:1018-1029 out float32 [hdr_target.naxis2][hdr_target.naxis1] */
@@ -876,6 +909,11 @@ int coreg_multi_set_reference_smoothing(coreg_multi* m, const double* wy, int32_
 /* coreg_despike_small / coreg_set_reference_despike on every device's context (the counts are the first device's) */
 int coreg_multi_despike_small(coreg_multi* m, const coreg_despike_params* params, int64_t* n_flagged);
 int coreg_multi_set_reference_despike(coreg_multi* m, const coreg_despike_params* params);
+/* coreg_despike_sum_planes_be on the first device (no device keeps anything of the call) */
+int coreg_multi_despike_sum_planes_be(coreg_multi* m, const void* base, int32_t bitpix, int64_t plane_stride, int32_t H,
+                                      int32_t W, const int64_t* plane_index, int32_t n_sel,
+                                      const coreg_despike_params* params, double* out_sum, int32_t* out_events,
+                                      int64_t* n_flagged);
 /* coreg_set_reference_rotation / coreg_set_small_rotation on every device's context */
 int coreg_multi_set_reference_rotation(coreg_multi* m, const coreg_diffrot* rot);
 int coreg_multi_set_small_rotation(coreg_multi* m, const coreg_diffrot* rot);
