@@ -1,7 +1,7 @@
 // The plan of one median/MAD despiking (coreg_despike_small, coreg_set_reference_despike, coreg_pixels_despike_*, DESIGN
 // section 8): the parameter checks with their code and message, the launch geometry -- which work item and thread owns which
 // pixel, and where its window stands in the item's LDS -- and the decision itself.  Plain C++ with no HIP dependency:
-// included by kernels_despike.hpp (k_despike takes its pixels and its decision from the functions below) and used by the
+// included by kernels_despike.hpp (its kernels take their pixels and their decision from the functions below) and used by the
 // host parts of libcoreg_hip.so's one translation unit; tests/native/despike_rules.cpp walks it on the host under
 // sanitizers, the decision function included: the very arithmetic the GPU runs.
 //
@@ -94,7 +94,7 @@ struct DespikePlan {
     const char* msg = nullptr;
     DespikeGeom g = {};
     unsigned grid = 0;  // workgroups: min(items, kDespikeMaxGrid)
-    size_t lds = 0;     // LDS of an item (static in k_despike<T, R>)
+    size_t lds = 0;     // LDS of an item (static in k_despike_image<T, R>)
 };
 
 inline DespikePlan despike_plan(long long H, long long W, const coreg_despike_params* prm) {

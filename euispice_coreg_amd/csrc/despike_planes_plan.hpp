@@ -2,7 +2,7 @@
 // despiked on its own by the rule of despike_plan.hpp, then summed over the planes in float64.  Here: the refusals with
 // their code and message, the launch geometry -- the tiles of despike_plan.hpp; the passes before the last one deal (plane,
 // tile) pairs, the last pass deals tiles and walks the planes in order -- and the one addition of the sum.  Plain C++ with
-// no HIP dependency: included by kernels_despike_planes.hpp and by the host parts of libcoreg_hip.so's one translation
+// no HIP dependency: included by kernels_despike.hpp and by the host parts of libcoreg_hip.so's one translation
 // unit; tests/native/despike_planes_rules.cpp walks it on the host under sanitizers.
 #pragma once
 #include "despike_plan.hpp"

@@ -1,6 +1,6 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the median/MAD despiking of
 // a resident image -- the plan (csrc/despike_plan.hpp: parameter checks, geometry; no GPU work) and one
-// launch of k_despike (csrc/kernels_despike.hpp) per pass on the handle's stream.
+// launch of k_despike_image (csrc/kernels_despike.hpp) per pass on the handle's stream.
 #pragma once
 namespace {
 
@@ -11,10 +11,12 @@ enum DespikeSlot { DESPIKE_SLOT_IMAGE = 0, DESPIKE_SLOT_REFERENCE = 1 };
 template <typename T>
 static void despike_launch(coreg_handle* h, const DespikePlan& p, const coreg_despike_params& prm, const T* src, T* dst,
                            unsigned long long* count) {
-    const dim3 grid(p.grid), block(kDespikeThreads);
-    if (prm.radius == 1) hipLaunchKernelGGL((k_despike<T, 1>), grid, block, 0, h->stream, src, dst, p.g, prm, count);
-    else if (prm.radius == 2) hipLaunchKernelGGL((k_despike<T, 2>), grid, block, 0, h->stream, src, dst, p.g, prm, count);
-    else hipLaunchKernelGGL((k_despike<T, 3>), grid, block, 0, h->stream, src, dst, p.g, prm, count);
+    const auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, dim3(p.grid), dim3(kDespikeThreads), 0, h->stream, src, dst, p.g, prm, count);
+    };
+    if (prm.radius == 1) launch(k_despike_image<T, 1>);
+    else if (prm.radius == 2) launch(k_despike_image<T, 2>);
+    else launch(k_despike_image<T, 3>);
 }
 
 // H x W pixels at `src` (float32 or float64, rows packed; never written) despiked by prm->n_iter passes, each on the result

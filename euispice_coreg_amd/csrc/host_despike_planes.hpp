@@ -1,34 +1,33 @@
 // Part of libcoreg_hip.so's ONE translation unit (coreg_hip.hip includes the parts in order): the planes of a cube despiked
 // one by one and summed over the planes (coreg_despike_sum_planes_be) -- the plan
 // (csrc/despike_planes_plan.hpp: refusals, geometry; no GPU work), the selected planes up as the file stores them, one
-// launch per pass on the handle's stream (csrc/kernels_despike_planes.hpp), the sum, the event map and the counts back.
+// launch per pass on the handle's stream (csrc/kernels_despike.hpp), the sum, the event map and the counts back.
 #pragma once
 namespace {
 
 template <typename T>
 static void despike_planes_launch_pass(coreg_handle* h, const DespikePlanesPlan& p, const coreg_despike_params& prm, const T* src,
                                        bool be, T* dst, int* events, unsigned long long* count) {
-    const dim3 grid(p.grid_pairs), block(kDespikeThreads);
-#define COREG_DP_PASS(R) \
-    hipLaunchKernelGGL((k_despike_planes_pass<T, R>), grid, block, 0, h->stream, src, be, dst, p.g, p.plane_px, p.pairs, prm, events, count)
-    if (prm.radius == 1) COREG_DP_PASS(1);
-    else if (prm.radius == 2) COREG_DP_PASS(2);
-    else COREG_DP_PASS(3);
-#undef COREG_DP_PASS
+    const auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, dim3(p.grid_pairs), dim3(kDespikeThreads), 0, h->stream, src, be, dst, p.g, p.plane_px, p.pairs, prm,
+                           events, count);
+    };
+    if (prm.radius == 1) launch(k_despike_planes_pass<T, 1>);
+    else if (prm.radius == 2) launch(k_despike_planes_pass<T, 2>);
+    else launch(k_despike_planes_pass<T, 3>);
 }
 
 template <typename T>
 static void despike_planes_launch_sum(coreg_handle* h, const DespikePlanesPlan& p, const coreg_despike_params& prm, const T* src,
                                       bool be, bool add_events, double* sum, int* events, unsigned long long* count) {
-    const dim3 grid(p.grid_tiles), block(kDespikeThreads);
     const bool overlap = h->opt_despike_planes_overlap != 0;
-#define COREG_DP_SUM(R)                                                                                                      \
-    hipLaunchKernelGGL((k_despike_planes_sum<T, R>), grid, block, 0, h->stream, src, be, overlap, p.g, p.plane_px, p.n_sel, prm, \
-                       add_events, sum, events, count)
-    if (prm.radius == 1) COREG_DP_SUM(1);
-    else if (prm.radius == 2) COREG_DP_SUM(2);
-    else COREG_DP_SUM(3);
-#undef COREG_DP_SUM
+    const auto launch = [&](auto k) {
+        hipLaunchKernelGGL(k, dim3(p.grid_tiles), dim3(kDespikeThreads), 0, h->stream, src, be, overlap, p.g, p.plane_px, p.n_sel, prm,
+                           add_events, sum, events, count);
+    };
+    if (prm.radius == 1) launch(k_despike_planes_sum<T, 1>);
+    else if (prm.radius == 2) launch(k_despike_planes_sum<T, 2>);
+    else launch(k_despike_planes_sum<T, 3>);
 }
 
 // the passes of a call on the stack at h->dp_raw (big-endian, packed): those before the last write h->dp_a and h->dp_b in

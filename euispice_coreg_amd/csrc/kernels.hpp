@@ -32,5 +32,5 @@
 #include "kernels_pixels_mi.hpp" // ... its mutual-information score: joint histograms in LDS, one pass
 #include "kernels_pixels_lct.hpp" // ... its apodized windows: weighted Pearson sums, two passes
 #include "kernels_smooth.hpp"     // NaN-aware separable smoothing: row pass (num, den), column pass (num / den)
-#include "kernels_despike.hpp"    // median/MAD despiking: one pass per launch, window in LDS, median and MAD by sorting network
-#include "kernels_despike_planes.hpp" // ... of a stack of planes: passes over (plane, tile) pairs, the last one fused with the sum over the planes
+#include "kernels_despike.hpp"    // median/MAD despiking of an image and of a stack of planes, one set of device functions: window in LDS,
+                                  // median and MAD by sorting network; a pass per launch, a stack's last pass fused with the sum over the planes

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """
-Time of the median/MAD despiking of the resident image to align (coreg_despike_small: one pass of k_despike and the pivot)
-beside the correlation sweep of the same process.  A record of what the kernel costs, nothing is asserted about the times.
+Time of the median/MAD despiking of the resident image to align (coreg_despike_small: one pass of k_despike_image and the
+pivot) beside the correlation sweep of the same process.  A record of what the kernel costs, nothing is asserted about the
+times.
 
 Cases: a 2048 x 2048 float32 image and a 4096 x 4096 float64 image (unit noise about 500, 0.5 % NaN pixels, 0.5 % spikes),
 radius 1, 2 and 3, one pass, the other parameters at their defaults.  One child process under a time limit.  The handle

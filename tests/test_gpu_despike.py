@@ -5,44 +5,16 @@ operations, so every pixel-level comparison is an equality: np.array_equal(..., 
 pass.  The shapes are those at which a tiled window kernel goes wrong: images smaller than a window, one row, one column,
 one pixel past the kernel's tile in both axes (taken from csrc/despike_plan.hpp).
 """
-import os
-import re
-
 import numpy as np
 import pytest
 
 from tests import despike_oracle as DO
 from tests import helpers as H
+from tests.despike_cases import TILE_H, TILE_W, image, rule
 
 pytestmark = pytest.mark.gpu
 
-_PLAN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "euispice_coreg_amd", "csrc", "despike_plan.hpp")
-
-
-def _plan_constant(name):
-    with open(_PLAN) as f:
-        return int(re.search(r"constexpr int %s = (\d+);" % name, f.read()).group(1))
-
-
-TILE_H, TILE_W = _plan_constant("kDespikeTileH"), _plan_constant("kDespikeTileW")
 SHAPES = [(1, 1), (1, 40), (40, 1), (5, 7), (TILE_H + 1, TILE_W + 1)]
-
-
-def image(shape, seed, dtype, kind="noise"):
-    """Pixels about 100 with unit noise and a spike on every 11th pixel or so (some of them side by side); float64 ones
-    are not float32-exact (they stay float64 on the device)."""
-    rng = np.random.default_rng(seed)
-    if kind == "integers":  # ties everywhere, and medians on half-integers
-        v = rng.integers(0, 4, shape).astype(np.float64)
-        v[rng.uniform(size=shape) < 0.08] += 40.0
-        return v.astype(dtype)
-    if kind == "constant":
-        return np.full(shape, 7.0, dtype=dtype)
-    v = 100.0 + rng.normal(0.0, 1.0, shape)
-    hit = rng.uniform(size=shape) < 0.09
-    v[hit] += rng.uniform(20.0, 4000.0, int(hit.sum()))
-    v[rng.uniform(size=shape) < 0.03] -= 60.0  # negative spikes: sign = both sees them
-    return v.astype(np.float32) if dtype == np.float32 else v + 1e-9 * np.pi
 
 
 def holes(v, kind):
@@ -59,12 +31,6 @@ def holes(v, kind):
     elif kind == "all_nan":
         v[:] = np.nan
     return v
-
-
-def rule(R, n_iter, shape=(99, 99), **kw):
-    """min_neighbours 5, or as many as an interior pixel of an image of `shape` has when that is fewer."""
-    most = min(shape[0], 2 * R + 1) * min(shape[1], 2 * R + 1) - 1
-    return dict(radius=R, n_iter=n_iter, min_neighbours=max(1, min(5, most)), **kw)
 
 
 def check_all_three(h, v, what, **prm):

@@ -7,8 +7,6 @@ is read from csrc/despike_plan.hpp); the oracle walks pixels in Python, so every
 evaluations (planes x pixels x passes).
 """
 import ctypes as C
-import os
-import re
 import warnings
 
 import numpy as np
@@ -17,49 +15,13 @@ import pytest
 from tests import despike_oracle as DO
 from tests import despike_planes_oracle as PO
 from tests import helpers as H
+from tests.despike_cases import TILE_H, TILE_W, image, rule, stack
 from tests.test_despike_planes_cpu import HIT_RULE, N_HITS, hit_cube
 
 pytestmark = pytest.mark.gpu
 
-_PLAN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "euispice_coreg_amd", "csrc", "despike_plan.hpp")
-
-
-def _plan_constant(name):
-    with open(_PLAN) as f:
-        return int(re.search(r"constexpr int %s = (\d+);" % name, f.read()).group(1))
-
-
-TILE_H, TILE_W = _plan_constant("kDespikeTileH"), _plan_constant("kDespikeTileW")
 SHAPES = [(1, 1), (1, 40), (40, 1), (5, 7), (TILE_H + 1, TILE_W + 1), (2 * TILE_H + 3, TILE_W + 5)]
 BIG = SHAPES[-1]  # several tiles, ragged in both axes
-
-
-def stack(n, shape, seed, dtype, kind="noise"):
-    """n planes about 100 with unit noise, a spike on every 11th pixel or so and a few negative ones, each plane with its
-    own; float64 values are not float32-exact.  kind "integers": ties and half-integer medians; "constant": 7 everywhere."""
-    rng = np.random.default_rng(seed)
-    full = (n,) + tuple(shape)
-    if kind == "integers":
-        v = rng.integers(0, 4, full).astype(np.float64)
-        v[rng.uniform(size=full) < 0.08] += 40.0
-        return v.astype(dtype)
-    if kind == "constant":
-        return np.full(full, 7.0, dtype=dtype)
-    v = 100.0 + rng.normal(0.0, 1.0, full)
-    hit = rng.uniform(size=full) < 0.09
-    v[hit] += rng.uniform(20.0, 4000.0, int(hit.sum()))
-    v[rng.uniform(size=full) < 0.03] -= 60.0
-    if dtype == np.float32:
-        return v.astype(np.float32)
-    v = v + 1e-9 * np.pi
-    assert not np.array_equal(v, v.astype(np.float32).astype(np.float64))
-    return v
-
-
-def rule(R, n_iter, shape=(99, 99), **kw):
-    """min_neighbours 5, or as many as an interior pixel of a plane of `shape` has when that is fewer."""
-    most = min(shape[0], 2 * R + 1) * min(shape[1], 2 * R + 1) - 1
-    return dict(radius=R, n_iter=n_iter, min_neighbours=max(1, min(5, most)), **kw)
 
 
 def check(h, planes, what, index=None, **prm):
@@ -102,6 +64,33 @@ def test_planes_against_the_oracle(gpu_handle, shape, dtype):
 def test_every_radius_with_every_pass_count(gpu_handle, R, n_iter, dtype):
     v = stack(3, (TILE_H + 1, TILE_W + 1), 40 + 3 * R + n_iter, dtype)
     assert sum(check(gpu_handle, v, f"R={R} n_iter={n_iter}", **rule(R, n_iter, replace="median" if n_iter == 2 else "nan"))) > 0
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("R", [1, 2, 3])
+def test_an_image_is_a_stack_of_one_plane(gpu_handle, R, dtype):
+    """coreg_despike_small on a resident image and coreg_despike_sum_planes_be on the same pixels as a one-plane big-endian
+    cube: the sum is the despiked image (a NaN a zero term), the counts per pass are equal, and the event map, which the
+    resident image has none of, holds the number of passes in which the oracle flags the pixel."""
+    h = gpu_handle
+    shape = (TILE_H + 1, TILE_W + 1)
+    v = image(shape, 60 + R, dtype)
+    prm = rule(R, 2, shape, replace="median", sign="both")
+    h.set_small(v)
+    counts = h.despike_small(prm)
+    got = h.get_small(v.shape, v.dtype)
+    total, events, plane_counts = h.despike_sum_planes(PO.be(v[None]), [0], prm)
+    assert np.array_equal(total, np.where(np.isnan(got), 0.0, got.astype(np.float64)))
+    assert plane_counts == counts
+    want_events = np.zeros(shape, dtype=np.int32)
+    out = v
+    for _ in range(prm["n_iter"]):
+        new, n = DO.despike_pass(out, **{k: x for k, x in prm.items() if k != "n_iter"})
+        flagged = ~((new == out) | (np.isnan(new) & np.isnan(out)))  # (a flag event changes the pixel: |d| > 0)
+        assert int(flagged.sum()) == n
+        want_events += flagged
+        out = new
+    assert want_events.any() and np.array_equal(events, want_events)
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
